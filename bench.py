@@ -20,10 +20,17 @@ the tail of one batch's kernel with the head of another's.  `value` is that decl
 `two_lanes`); the same loop timed with one batch in flight is reported beside it (`single_lane`) and is never `value`: two
 lanes win by 2-4 % on most boxes of the pool, on some the single stream does by ~1 %.
 
-The timed K-step loop is repeated (default 5 times, barrier + synchronize on both sides of each) and
-`value` is the median repeat; every repeat's time is in the line.  `value` is the HBM-resident rate;
-`host_pipeline` (pinned host tiles in -> pinned host masks out, every rank with its own staging
-buffers) is measured for every N beside it.  Rank 0 prints ONE JSON line.
+A plain run times the K-step loop once (barrier + synchronize on both sides) and prints `value` and
+`ms_per_step` from it.  `--full` adds everything else, as one run: the loop repeated (default 5
+times, `value` the median repeat, every repeat's time in the line), the one-batch-in-flight figure,
+per-kernel times and the roofline, `host_pipeline` (pinned host tiles in -> pinned host masks out,
+every rank with its own staging buffers), the real-crop path, parity against the golden masks and
+the CPU baseline.  `value` is the HBM-resident rate either way.  Rank 0 prints ONE JSON line.
+
+`--dump-outputs DIR` writes what the last step of the headline loop returned to its caller: the
+per-class pixel counts of all 32 tiles (`counts.npy`, float64 [32, 5]) and the class maps of a fixed
+seeded sample of 16 of them (`masks.npy`, float32 [16, 512, 1024]; 32 MiB), rank 0's only.  The
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -48,7 +55,13 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="times the K-step loop is timed (median reported)")
+    ap.add_argument("--repeats", type=int, default=None, help="times the K-step loop is timed (median reported); default 1, "
+                                                              "5 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements and checks (one lane, per-kernel times, host pipeline, real crops, "
+                         "parity, CPU baseline); a plain run does only what `value` and `ms_per_step` need")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--lanes", type=int, default=LANES, help="batches in flight (1 = one workspace, one stream: what the "
                                                              "rocprofv3 passes of tools/profile_round.sh use, so that "
                                                              "kernel durations are not stretched by a co-running batch)")
@@ -85,11 +98,20 @@ def load_weights():
 
 
 def make_batches(rank):
-    """NBATCH x BATCH tiles; the first four tiles of rank 0 are the golden seeds 0..3 (in-line parity)."""
+    """NBATCH x BATCH tiles; the first four tiles of rank 0 are the golden seeds 0..3 (in-line parity).  Generated on a thread
+    pool (numpy's array arithmetic releases the GIL): 0.16 s a tile on one core would be most of a plain run's set-up."""
+    from concurrent.futures import ThreadPoolExecutor
     import numpy as np
     from glomeruli_segmentation_amd.synth import synth_tile
     base = rank * NBATCH * BATCH
-    return np.stack([synth_tile(base + i) for i in range(NBATCH * BATCH)]).reshape(NBATCH, BATCH, H, W, 3)
+    out = np.empty((NBATCH * BATCH, H, W, 3), dtype=np.uint8)
+
+    def one(i):
+        out[i] = synth_tile(base + i)
+
+    with ThreadPoolExecutor(max(1, min(16, host_cores()))) as ex:
+        list(ex.map(one, range(NBATCH * BATCH)))
+    return out.reshape(NBATCH, BATCH, H, W, 3)
 
 
 def host_cores():
@@ -354,14 +376,24 @@ def run_rank(args):
             out.append(el)
         return out
 
-    reps_local = [timed(args.steps) for _ in range(max(args.repeats, 1))]
-    mode["lanes"] = 1                      # the same loop with one batch in flight
-    timed(args.steps)
-    single_local = [timed(args.steps) for _ in range(max(args.repeats, 1))]
-    mode["lanes"] = LANES
-    timed(args.steps)                      # leaves `totals` from a pass in the default mode
-    reps_lanes, reps_single = reduce_max(reps_local), reduce_max(single_local)
-    elapsed_lanes, single = float(np.median(reps_lanes)), float(np.median(reps_single))
+    repeats = max(args.repeats if args.repeats is not None else (5 if args.full else 1), 1)
+    reps_local = [timed(args.steps) for _ in range(repeats)]
+    dump = None
+    if args.dump_outputs and rank == 0:
+        # the last step of the headline loop: its batch's class maps (a fixed sample of the tiles) and per-class counts
+        last = args.steps - 1
+        nb = tiles_np.shape[1]
+        pick = np.sort(np.random.default_rng(0).choice(nb, min(16, nb), replace=False))
+        dump = {"masks": mask[last % NBATCH].cpu().numpy()[pick].astype(np.float32),
+                "counts": hist[last % nslots].cpu().numpy().astype(np.float64)}
+    if args.full:
+        mode["lanes"] = 1                      # the same loop with one batch in flight
+        timed(args.steps)
+        single_local = [timed(args.steps) for _ in range(repeats)]
+        mode["lanes"] = LANES
+        timed(args.steps)                      # leaves `totals` from a pass in the default mode
+    reps_lanes = reduce_max(reps_local)
+    elapsed_lanes = float(np.median(reps_lanes))
     # `value` is bound to ONE declared configuration -- LANES batches in flight (two by default) -- not to the better of two noisy
     # measurements; the single-stream figure is reported beside it
     reps, elapsed = reps_lanes, elapsed_lanes
@@ -369,20 +401,23 @@ def run_rank(args):
     per_rank_ms = gather_f64(float(np.median(reps_local)) / args.steps * 1e3)
     pixel_totals = [int(v) for v in totals.tolist()]   # all-reduced in the last repeat
 
-    # same K steps again, one batch in flight, with a HIP event pair around every kernel on the launch stream: per-kernel
-    # durations for the roofline line (the event packets lengthen kernel boundaries, so this pass is
-    # not the one quoted as throughput; its wall time is reported beside it)
-    mode["lanes"] = 1
-    eng.profile(True)
-    elapsed_prof = timed(args.steps)
-    prof = eng.profile_read()
-    eng.profile(False)
-    mode["lanes"] = LANES
+    host = real = None
+    if args.full:
+        reps_single = reduce_max(single_local)
+        single = float(np.median(reps_single))
+        # same K steps again, one batch in flight, with a HIP event pair around every kernel on the launch stream: per-kernel
+        # durations for the roofline line (the event packets lengthen kernel boundaries, so this pass is
+        # not the one quoted as throughput; its wall time is reported beside it)
+        mode["lanes"] = 1
+        eng.profile(True)
+        elapsed_prof = timed(args.steps)
+        prof = eng.profile_read()
+        eng.profile(False)
+        mode["lanes"] = LANES
 
     # PCIe-inclusive rate (never `value`): pinned host uint8 tiles -> pinned host masks through the
     # H2D / compute / D2H pipeline of gs_espnet_segment_host, every rank with its own buffers
-    host = None
-    if not args.no_host_pipeline:
+    if args.full and not args.no_host_pipeline:
         nb = tiles_np.shape[1]
         per_call = 32 if not args.dry_run else NBATCH                 # batches per call: one set of pinned buffers, cycled
         calls = max(1, -(-args.host_batches // per_call)) if not args.dry_run else 1
@@ -419,8 +454,7 @@ def run_rank(args):
 
     # the path REAL crops take (VisualizeResults_iou.py:100-156 with crops that are not network-sized): the 28 crop sizes of the
     # example slide, pageable numpy crops in -> crop-size maps + counts out through gs_espnet_segment_crops_host
-    real = None
-    if not args.no_real_crops and not args.dry_run:
+    if args.full and not args.no_real_crops and not args.dry_run:
         from glomeruli_segmentation_amd.synth import synth_tile
         ex = np.load(os.path.join(REPO, "tests", "golden", "merge.npz"))["example_boxes"]
         base = [synth_tile(5000 + rank * 100 + k, int(b[3] - b[1]), int(b[2] - b[0]), blobs=4) for k, b in enumerate(ex)]
@@ -453,24 +487,6 @@ def run_rank(args):
         n = world
         total_tiles = n * tiles_np.shape[1] * args.steps
         value = total_tiles / elapsed
-        dom = next((k for k in prof if k["name"] == DOMINANT), None)
-        kernels = {k["name"]: {"avg_ms": round(k["total_ms"] / max(k["launches"], 1), 4), "launches": k["launches"]}
-                   for k in prof}
-        roof = None
-        if dom:
-            traffic, traffic_detail = traffic_of_dominant()
-            avg_s = dom["total_ms"] / dom["launches"] * 1e-3
-            achieved = dom["flops_per_tile"] * BATCH / avg_s / 1e12
-            roof = {"bound": "mfma", "kernel": DOMINANT, "achieved": round(achieved, 2), "peak": PEAK_F32_MFMA_TFLOPS,
-                    "unit": "TFLOP/s", "frac": round(achieved / PEAK_F32_MFMA_TFLOPS, 4), "traffic": traffic,
-                    "traffic_is": "static: read from the committed profiles/ file named in traffic_detail (rocprofv3 --pmc passes of "
-                                  "the builder's run of this command), NOT measured in this run",
-                    "traffic_detail": traffic_detail,
-                    "flop_per_launch": dom["flops_per_tile"] * BATCH,
-                    "avg_launch_ms": round(avg_s * 1e3, 4),
-                    "launches_timed": dom["launches"], "instrumented_ms_per_step": round(elapsed_prof / args.steps * 1e3, 3),
-                    "whole_net_frac": round(value / n * FLOP_PER_TILE / 1e12 / PEAK_F32_MFMA_TFLOPS, 4),
-                    "whole_net_frac_single_lane": round(total_tiles / single / n * FLOP_PER_TILE / 1e12 / PEAK_F32_MFMA_TFLOPS, 4)}
         out = {
             "metric": "patches/sec (1024x512 RGB) ESPNet p=2 q=8 5 classes, HBM-resident, two batches in flight", "value": round(value, 2),
             "unit": "patches/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
@@ -478,33 +494,56 @@ def run_rank(args):
             "vs_baseline": None, "dtype": "f32", "data": "dry-run (no device work)" if args.dry_run else "synthetic",
             "config": {"workload": "ESPNet p=2 q=8 encoder+decoder, batch=32 synthetic 1024x512 uint8 BGR tiles per GPU, "
                                    "normalise+forward+argmax+counts, inputs resident in HBM, steps rotate through %d distinct batches, "
-                                   "%d batch(es) in flight (engine lanes, one HIP stream each) for `value`; the one-batch-in-flight "
-                                   "figure is reported beside it" % (NBATCH, in_flight),
+                                   "%d batch(es) in flight (engine lanes, one HIP stream each) for `value`%s"
+                                   % (NBATCH, in_flight, "; the one-batch-in-flight figure is reported beside it" if args.full else ""),
                        "global_batch": n * BATCH, "tile": [H, W], "weights": "espnet_fold1 (tests/golden)",
                        "parallelism": "tile-range per rank x%d" % n},
             "batches_in_flight": in_flight,
             "two_lanes": {"value": round(total_tiles / elapsed_lanes, 2), "ms_per_step": round(elapsed_lanes / args.steps * 1e3, 3),
                           "seconds": [round(r, 6) for r in reps_lanes],
                           "note": "the K steps alternating between %d lanes (workspaces), each on its own stream" % LANES},
-            "single_lane": {"value": round(total_tiles / single, 2), "ms_per_step": round(single / args.steps * 1e3, 3),
-                            "seconds": [round(r, 6) for r in reps_single],
-                            "note": "the same K steps with one batch in flight (one workspace, one stream)"},
             "repeats": {"n": len(reps), "statistic": "median of max-over-ranks", "seconds": [round(r, 6) for r in reps]},
             "per_rank_ms_per_step": [round(v, 3) for v in per_rank_ms],
             "pixel_totals_all_ranks": pixel_totals,
-            "roofline": roof,
-            "kernels_avg_ms": kernels,
         }
+        if args.full:
+            dom = next((k for k in prof if k["name"] == DOMINANT), None)
+            kernels = {k["name"]: {"avg_ms": round(k["total_ms"] / max(k["launches"], 1), 4), "launches": k["launches"]}
+                       for k in prof}
+            roof = None
+            if dom:
+                traffic, traffic_detail = traffic_of_dominant()
+                avg_s = dom["total_ms"] / dom["launches"] * 1e-3
+                achieved = dom["flops_per_tile"] * BATCH / avg_s / 1e12
+                roof = {"bound": "mfma", "kernel": DOMINANT, "achieved": round(achieved, 2), "peak": PEAK_F32_MFMA_TFLOPS,
+                        "unit": "TFLOP/s", "frac": round(achieved / PEAK_F32_MFMA_TFLOPS, 4), "traffic": traffic,
+                        "traffic_is": "static: read from the committed profiles/ file named in traffic_detail (rocprofv3 --pmc passes of "
+                                      "the builder's run of this command), NOT measured in this run",
+                        "traffic_detail": traffic_detail,
+                        "flop_per_launch": dom["flops_per_tile"] * BATCH,
+                        "avg_launch_ms": round(avg_s * 1e3, 4),
+                        "launches_timed": dom["launches"], "instrumented_ms_per_step": round(elapsed_prof / args.steps * 1e3, 3),
+                        "whole_net_frac": round(value / n * FLOP_PER_TILE / 1e12 / PEAK_F32_MFMA_TFLOPS, 4),
+                        "whole_net_frac_single_lane": round(total_tiles / single / n * FLOP_PER_TILE / 1e12 / PEAK_F32_MFMA_TFLOPS, 4)}
+            out["single_lane"] = {"value": round(total_tiles / single, 2), "ms_per_step": round(single / args.steps * 1e3, 3),
+                                  "seconds": [round(r, 6) for r in reps_single],
+                                  "note": "the same K steps with one batch in flight (one workspace, one stream)"}
+            out["roofline"] = roof
+            out["kernels_avg_ms"] = kernels
         if host is not None:
             out["host_pipeline"] = host
         if real is not None:
             out["real_crops"] = real
         if cpus is not None:
             out["rank0_cpus"] = len(cpus)
-        if not args.dry_run:
+        if args.full and not args.dry_run:
             out["parity"] = parity_vs_golden(mask[0, :4].cpu().numpy())
             if n == 1 and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(sd, tiles_np[0], mean, std)
+        if dump is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in dump.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
         print(json.dumps(out))
         sys.stdout.flush()
     if dist is not None:

@@ -424,13 +424,39 @@ def test_bench_two_ranks_on_one_gpu(torch_mod):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(GS_BENCH_BACKEND="gloo", GS_BENCH_ONE_GPU="1")
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "2",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     j = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert j["n_gpus"] == 2 and len(j["per_rank_ms_per_step"]) == 2
     assert j["parity"]["miou_vs_reference"] >= 0.999
     assert sum(j["pixel_totals_all_ranks"]) == 2 * 2 * 32 * 512 * 1024
     assert len(j["host_pipeline"]["per_rank_patches_per_s"]) == 2
+
+
+def test_bench_dump_outputs_are_the_steps_outputs(torch_mod, tmp_path):
+    """plain `bench.py --steps 5 --dump-outputs DIR`: the last step is batch 0 again (four batches rotate), whose first tiles are
+    the golden seeds; the dumped class maps are theirs, and every sampled map agrees with its dumped per-class counts"""
+    import json
+    import subprocess
+    import sys
+    from conftest import REPO
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    j = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert j["steps"] == 5 and j["repeats"]["n"] == 1 and j["ms_per_step"] > 0 and "host_pipeline" not in j
+    masks, counts = np.load(str(tmp_path / "masks.npy")), np.load(str(tmp_path / "counts.npy"))
+    assert masks.shape == (16, 512, 1024) and counts.shape == (32, 5)
+    assert (counts.sum(axis=1) == 512 * 1024).all()
+    pick = np.sort(np.random.default_rng(0).choice(32, 16, replace=False))     # bench.py's fixed sample of the 32 tiles
+    for k, t in enumerate(pick):
+        assert (np.bincount(masks[k].astype(np.int64).ravel(), minlength=5) == counts[t]).all(), t
+    z = load_golden("masks_fold1.npz")
+    for k, t in enumerate(pick[pick < 4]):                                     # sorted: the golden seeds come first
+        ref = z["mask_%d" % t]
+        edge = np.unpackbits(z["edge_%d" % t]).reshape(ref.shape).astype(bool)
+        assert not ((masks[k] != ref) & ~edge).any(), t
 
 
 def test_driver_model_type_2(torch_mod, tmp_path):

@@ -162,8 +162,8 @@ def test_bench_spawns_one_process_per_gpu():
     with n_gpus 2, per-rank times and the all-reduced totals (--dry-run: control flow only, gloo, no device work)"""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run"],
-                       env=env, capture_output=True, text=True, timeout=300)
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run",
+                        "--full"], env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -176,6 +176,35 @@ def test_bench_spawns_one_process_per_gpu():
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--dry-run"],
                        env=dict(env, WORLD_SIZE="1", RANK="0"), capture_output=True, text=True, timeout=300)
     assert p.returncode != 0 and "WORLD_SIZE" in p.stderr
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """a plain `bench.py` times the K steps once and carries only the headline (the secondary legs are --full's);
+    --dump-outputs writes the last step's outputs as float npy files, the same ones for the same arguments"""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("out%d" % run)
+        p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dry-run",
+                            "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in j, k
+        assert j["steps"] == 3 and j["repeats"]["n"] == 1 and len(j["repeats"]["seconds"]) == 1
+        assert j["pixel_totals_all_ranks"] == [3] * 5                # three timed steps, one pixel per class each
+        assert abs(j["ms_per_step"] - j["repeats"]["seconds"][0] / 3 * 1e3) < 1e-2
+        for k in ("single_lane", "roofline", "kernels_avg_ms", "host_pipeline", "real_crops", "parity", "cpu_baseline"):
+            assert k not in j, k
+        got = {f: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))}
+        assert sorted(got) == ["counts.npy", "masks.npy"]
+        assert got["masks.npy"].dtype == np.float32 and got["counts.npy"].dtype == np.float64
+        assert sum(a.nbytes for a in got.values()) <= 64 << 20
+        dumps.append(got)
+    assert all(np.array_equal(dumps[0][f], dumps[1][f]) for f in dumps[0])
 
 
 def test_product_library_has_no_diagnostic_switches():
@@ -1005,8 +1034,8 @@ def _last_json(text):
 
 
 def test_eight_ranks_bench_dry_run_and_one_rank_failing():
-    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--dry-run"],
-                       env=_clean_env(), capture_output=True, text=True, timeout=600)
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--dry-run",
+                        "--full"], env=_clean_env(), capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     j = _last_json(p.stdout)
     assert j["n_gpus"] == 8 and j["scaling"] == "weak" and len(j["per_rank_ms_per_step"]) == 8

@@ -1,12 +1,13 @@
 #!/bin/bash
 # On the GPU box: bench the shipped library and each named variant (variants_so/libglomseg_<name>.so), one JSON per run
-# under gpurun_out/.  tools/ab.sh tag name1 name2 ...
+# under $GS_RUN_DIR (default runs/).  tools/ab.sh tag name1 name2 ...
 tag=$1; shift
-mkdir -p gpurun_out
+out=${GS_RUN_DIR:-runs}
+mkdir -p $out
 run() {
     name=$1; lib=$2
-    GLOMSEG_EXPERIMENT=1 GLOMSEG_ALLOW_DIAG=1 GLOMSEG_LIB=$lib timeout -k 10 300 python bench.py --steps 20 --warmup 3 --repeats 3 --no-cpu-baseline --no-host-pipeline --no-real-crops > gpurun_out/ab_${tag}_$name.json 2> gpurun_out/ab_${tag}_$name.err || { echo "variant $name failed"; tail -5 gpurun_out/ab_${tag}_$name.err; return 1; }
-    python - "$name" gpurun_out/ab_${tag}_$name.json <<'PY'
+    GLOMSEG_EXPERIMENT=1 GLOMSEG_ALLOW_DIAG=1 GLOMSEG_LIB=$lib timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --repeats 3 --no-cpu-baseline --no-host-pipeline --no-real-crops > $out/ab_${tag}_$name.json 2> $out/ab_${tag}_$name.err || { echo "variant $name failed"; tail -5 $out/ab_${tag}_$name.err; return 1; }
+    python - "$name" $out/ab_${tag}_$name.json <<'PY'
 import json,sys
 j=json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 k=j["kernels_avg_ms"]

@@ -5,22 +5,23 @@
 tag=$1; shift
 rounds=3
 if [[ $1 =~ ^[0-9]+$ ]]; then rounds=$1; shift; fi
-mkdir -p gpurun_out
+out=${GS_RUN_DIR:-runs}      # one JSON per run lands here
+mkdir -p $out
 names=(shipped "$@")
 for r in $(seq 1 $rounds); do
     for name in "${names[@]}"; do
         lib=variants_so/libglomseg_$name.so
         [ $name = shipped ] && lib=glomeruli_segmentation_amd/libglomseg.so
-        GLOMSEG_EXPERIMENT=1 GLOMSEG_ALLOW_DIAG=1 GLOMSEG_LIB=$lib timeout -k 10 300 python bench.py --steps 40 --warmup 5 --repeats 5 --no-cpu-baseline --no-host-pipeline --no-real-crops > gpurun_out/ab2_${tag}_${name}_$r.json 2> gpurun_out/ab2_${tag}_${name}_$r.err || { echo "variant $name failed"; tail -5 gpurun_out/ab2_${tag}_${name}_$r.err; exit 1; }
+        GLOMSEG_EXPERIMENT=1 GLOMSEG_ALLOW_DIAG=1 GLOMSEG_LIB=$lib timeout -k 10 300 python bench.py --full --steps 40 --warmup 5 --repeats 5 --no-cpu-baseline --no-host-pipeline --no-real-crops > $out/ab2_${tag}_${name}_$r.json 2> $out/ab2_${tag}_${name}_$r.err || { echo "variant $name failed"; tail -5 $out/ab2_${tag}_${name}_$r.err; exit 1; }
     done
 done
-python - "$tag" "$rounds" "${names[@]}" <<'PY'
+python - "$out" "$tag" "$rounds" "${names[@]}" <<'PY'
 import json, statistics, sys
-tag, rounds, names = sys.argv[1], int(sys.argv[2]), sys.argv[3:]
+out, tag, rounds, names = sys.argv[1], sys.argv[2], int(sys.argv[3]), sys.argv[4:]
 for name in names:
     two, one, kern, agree = [], [], {}, []
     for r in range(1, rounds + 1):
-        j = json.loads(open("gpurun_out/ab2_%s_%s_%d.json" % (tag, name, r)).read().strip().splitlines()[-1])
+        j = json.loads(open("%s/ab2_%s_%s_%d.json" % (out, tag, name, r)).read().strip().splitlines()[-1])
         two.append(j["two_lanes"]["ms_per_step"]); one.append(j["single_lane"]["ms_per_step"]); agree.append(j["parity"]["pixel_agreement"])
         for k, v in j["kernels_avg_ms"].items():
             kern.setdefault(k, []).append(v["avg_ms"])

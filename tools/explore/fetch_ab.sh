@@ -6,7 +6,7 @@ name=$1
 out=gpurun_out/fetch_ab_$name
 mkdir -p $out
 export TMPDIR=/tmp
-B="python3 bench.py --steps 10 --warmup 2 --repeats 1 --lanes 1 --no-cpu-baseline --no-host-pipeline --no-real-crops"
+B="python3 bench.py --full --steps 10 --warmup 2 --repeats 1 --lanes 1 --no-cpu-baseline --no-host-pipeline --no-real-crops"
 for which in shipped $name; do
   if [ $which != shipped ]; then export GLOMSEG_EXPERIMENT=1 GLOMSEG_ALLOW_DIAG=1 GLOMSEG_LIB=variants_so/libglomseg_$name.so; fi
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/${which}_f -o f -- $B > /dev/null 2> $out/${which}_f.err || exit 1

@@ -5,7 +5,7 @@ tag=${1:-mem}
 out=gpurun_out/pmc_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-B="python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline"
+B="python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline"
 i=0
 while read -r line; do
     [ -z "$line" ] && continue

@@ -9,7 +9,7 @@ out=gpurun_out/pmc_$tag
 mkdir -p $out
 export TMPDIR=/tmp
 if [ -n "$2" ]; then export GLOMSEG_EXPERIMENT=1 GLOMSEG_ALLOW_DIAG=1 GLOMSEG_LIB=$2; fi
-B="python3 bench.py --steps 6 --warmup 2 --repeats 1 --lanes 1 --no-cpu-baseline --no-host-pipeline --no-real-crops"
+B="python3 bench.py --full --steps 6 --warmup 2 --repeats 1 --lanes 1 --no-cpu-baseline --no-host-pipeline --no-real-crops"
 i=0
 while read -r line; do
     [ -z "$line" ] && continue
