@@ -15,7 +15,7 @@ if os.environ.get("GLOMSEG_LIB") and os.environ.get("GLOMSEG_EXPERIMENT") == "1"
 GS_OK = 0
 GS_IN_U8_BGR_NHWC = 0
 GS_IN_F32_NCHW = 1
-ABI_VERSION = 5
+ABI_VERSION = 6
 GS_BUILD_DIAG = 1
 MAX_CROPS_PER_CALL = 64
 
@@ -47,6 +47,17 @@ class PasteTarget(ctypes.Structure):
 class CropOverlay(ctypes.Structure):
     _fields_ = [("palette_rgb", ctypes.c_void_p), ("n_colours", ctypes.c_int32), ("wa", ctypes.c_float), ("wb", ctypes.c_float),
                 ("out_bgr", ctypes.POINTER(ctypes.c_void_p))]
+
+
+class EvalBox(ctypes.Structure):
+    _fields_ = [("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("x1", ctypes.c_int32), ("y1", ctypes.c_int32),
+                ("raster_w", ctypes.c_int32), ("raster_h", ctypes.c_int32), ("offset", ctypes.c_int64)]
+
+
+class EvalSet(ctypes.Structure):
+    _fields_ = [("rasters", ctypes.c_void_p), ("raster_bytes", ctypes.c_int64), ("boxes", ctypes.c_void_p),
+                ("n_boxes", ctypes.c_int32), ("win_ptr", ctypes.c_void_p), ("win_idx", ctypes.c_void_p), ("n_idx", ctypes.c_int32),
+                ("small_map", ctypes.c_void_p)]
 
 
 class KernelTime(ctypes.Structure):
@@ -95,6 +106,7 @@ PROTOTYPES = {
     "gs_wsi_paste_max_lut": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "gs_overlay_classmap": (_I, [_P, _P, _I, _I, _P, _I, ctypes.c_float, ctypes.c_float, _P, _P]),
     "gs_confusion_u8": (_I, [_P, _P, ctypes.c_longlong, _I, _P, _P]),
+    "gs_wsi_eval_windows": (_I, [_I, _I, _I, _I, ctypes.POINTER(EvalSet), ctypes.POINTER(EvalSet), _P, _P, _I, _I, _P, _P, _P]),
     "gs_conv2d_nhwc": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P]),
     "gs_roialign": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
     "gs_nms": (_I, [_P, _P, _I, ctypes.c_float, ctypes.c_float, _I, _P, _P, _P]),

@@ -54,10 +54,10 @@ def _axis_lut(size, limit, window=WINDOW, ds=MAGNIFICATION):
     return lut
 
 
-def reference_window_luts(slide_width, slide_height):
-    """(sx, sy) tables for gs_wsi_paste_max_lut.  The x windows are skipped when xmax > slide_width (never true, :378)
-    and the y windows when ymax > slide_WIDTH (:386, the reference's typo, kept)."""
-    return _axis_lut(slide_width, slide_width), _axis_lut(slide_height, slide_width)
+def reference_window_luts(slide_width, slide_height, window=WINDOW):
+    """(sx, sy) tables for gs_wsi_paste_max_lut (and gs_wsi_eval_windows).  The x windows are skipped when xmax > slide_width
+    (never true, :378) and the y windows when ymax > slide_WIDTH (:386, the reference's typo, kept)."""
+    return _axis_lut(slide_width, slide_width, window), _axis_lut(slide_height, slide_width, window)
 
 
 class SlideCompositor:
@@ -152,8 +152,8 @@ def build_parser():
     path is the prediction branch (:430-431, generate_pred_wsi).  There the reference itself never reads --iou_threshold,
     --output_file, --start or --end (they are used by scan_files, the ground-truth branch, :108-118): they are accepted so
     that the reference's command lines (README.md:268-281, example/README.md:108-133) run unchanged, and have no effect.  The
-    three ground-truth directories select the evaluation branch (:427-434), which needs the GT tooling that is out of scope
-    (annotation XML, labelme shapes): accepted by the parser, refused by main() with an explanation."""
+    three ground-truth directories select the evaluation branch (:427-434): accepted by the parser, refused by main() with a
+    pointer to wsi_eval, which implements that branch with this same parser."""
     p = ArgumentParser(description='merge cropped glomerular segmented images')
     p.add_argument('--staining', dest='staining', type=str, required=True)
     p.add_argument('--merged_detection_result_csv', dest='input_csv', type=str, required=True)
@@ -190,6 +190,20 @@ def slide_size(wsi_dir, file_key, target_meta):
     if m and m["width"] > 0:
         return m["width"], m["height"]
     raise RuntimeError("size of slide %s unknown: OpenSlide is not installed and the target list has no metadata line for it" % file_key)
+
+
+def small_slide_bgr(wsi_dir, file_key, map_h, map_w):
+    """the 1/8 slide image the maps are blended over (BGR uint8 [map_h,map_w,3]): the PNG-branch slide under wsi_dir/file_key,
+    cropped / padded to the map; black when there is none."""
+    from PIL import Image
+    small = np.zeros((map_h, map_w, 3), dtype=np.uint8)
+    pngs = glob.glob(os.path.join(wsi_dir, file_key, "*.PNG")) + glob.glob(os.path.join(wsi_dir, file_key, "*.png"))
+    if pngs:
+        with Image.open(pngs[0]) as im:
+            rgb = np.asarray(im.convert("RGB"))
+        hh, ww = min(map_h, rgb.shape[0]), min(map_w, rgb.shape[1])
+        small[:hh, :ww] = rgb[:hh, :ww, ::-1]
+    return small
 
 
 def generate_pred_wsi(args, out=sys.stdout):
@@ -235,14 +249,7 @@ def generate_pred_wsi(args, out=sys.stdout):
             comp.paste(cm, b[0], b[1])
             used += 1
         mh, mw = comp.map.shape
-        small = np.zeros((mh, mw, 3), dtype=np.uint8)
-        pngs = glob.glob(os.path.join(args.wsi_dir, key, "*.PNG")) + glob.glob(os.path.join(args.wsi_dir, key, "*.png"))
-        if pngs:          # the 1/8 slide image of the PNG branch, cropped / padded to the map
-            with Image.open(pngs[0]) as im:
-                rgb = np.asarray(im.convert("RGB"))
-            hh, ww = min(mh, rgb.shape[0]), min(mw, rgb.shape[1])
-            small[:hh, :ww] = rgb[:hh, :ww, ::-1]
-        blended = comp.overlay(small).cpu().numpy()
+        blended = comp.overlay(small_slide_bgr(args.wsi_dir, key, mh, mw)).cpu().numpy()
         results[key] = {"map": comp.map.cpu().numpy(), "crops": used}
         if not args.no_save:
             Image.fromarray(np.ascontiguousarray(blended[:, :, ::-1])).save(os.path.join(args.output_dir, key + "_pred.jpg"),
@@ -257,8 +264,9 @@ def main(argv=None):
     # the reference takes the evaluation branch only when ALL three ground-truth directories are given (:427); with any of
     # them missing it composes the prediction WSI and ignores the rest
     if args.seg_gt_json_dir is not None and args.gt_png_dir is not None and args.ob_gt_xml_dir is not None:
-        print("the ground-truth evaluation branch (scan_files: annotation XML, labelme shapes, the TSV of --output_file) is outside "
-              "the rebuilt path; leave the three *_gt_* directories unset to compose the prediction WSI", file=sys.stderr)
+        print("the ground-truth evaluation branch (scan_files: annotation XML, labelme shapes, the TSV of --output_file) is the "
+              "command `python -m glomeruli_segmentation_amd.wsi_eval` with the same flags; leave the three *_gt_* directories unset "
+              "to compose the prediction WSI", file=sys.stderr)
         return 2
     generate_pred_wsi(args)
     return 0

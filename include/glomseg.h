@@ -244,6 +244,41 @@ gs_status gs_overlay_classmap(const uint8_t *region_bgr, const uint8_t *class_ma
 gs_status gs_confusion_u8(const uint8_t *pred, const uint8_t *gt, long long n, int classes,
                           unsigned long long *hist /*[classes*classes] device, accumulated into*/, void *hip_stream);
 
+/* WSI-level evaluation against ground truth (eval_wsi_segmentation.py:162-213, the scan_files branch; ABI 6).  For one slide
+ * and the reference's window walk (:180-195: windows of `window` px, the last one per axis reaching the slide edge, windows with
+ * ymax > slide_w skipped -- the reference's typo, kept), the label of pixel (x,y) in window w is 0 or the max of
+ * raster_b[y-y0][x-x0] over the member boxes b of w whose placement rectangle holds the pixel (:301-312), for the ground-truth
+ * and the prediction set alike.  hist_win[w][classes*g + p] counts the window's pixels by (ground truth g, prediction p)
+ * (iouEval.fast_hist, IOUEval.py:19-21); it is overwritten, integer, bit-reproducible.  A set's small_map (uint8 [map_h,map_w],
+ * or NULL) receives the label at level-0 (sx_lut[X], sy_lut[Y]) in the window holding that pixel (the 1/8 map of
+ * generate_whole_img, :215-241; tables as for gs_wsi_paste_max_lut, -1 leaves the cell 0).  Nothing at level 0 is
+ * materialised: tiles that no member box touches are counted as (0,0) without a pixel loop.
+ * Membership is the caller's: win_ptr[w] .. win_ptr[w+1] index win_idx, which names boxes of the set, for window
+ * w = yi * (slide_w / window + 1) + xi of the (slide_w / window + 1) x (slide_h / window + 1) walk (windows the walk skips
+ * are ignored).  Every pointer in the sets is a device pointer; the two gs_eval_set structs themselves are host memory.
+ * err_word: 4 device ints of scratch.  The entry waits for its launch (not capturable): a member whose raster is not the size
+ * of its placement rectangle or lies outside raster_bytes, a malformed list, or a label >= classes (:315) is GS_ERR_INVALID
+ * with the reason in gs_last_error(); no byte outside a raster is read. */
+typedef struct gs_eval_box {
+    int32_t x0, y0, x1, y1;       /* placement rectangle, level-0 pixels, half-open; may reach outside the slide */
+    int32_t raster_w, raster_h;   /* the raster's own size: must equal the rectangle's */
+    int64_t offset;               /* byte offset of the raster (uint8 [raster_h][raster_w]) in rasters */
+} gs_eval_box;
+typedef struct gs_eval_set {
+    const uint8_t *rasters;
+    int64_t raster_bytes;
+    const gs_eval_box *boxes;
+    int32_t n_boxes;
+    const int32_t *win_ptr;       /* [n_windows + 1] */
+    const int32_t *win_idx;       /* [n_idx] box indices */
+    int32_t n_idx;
+    uint8_t *small_map;           /* [map_h][map_w] 1/8 class map out, or NULL */
+} gs_eval_set;
+gs_status gs_wsi_eval_windows(int slide_w, int slide_h, int window, int classes, const gs_eval_set *gt, const gs_eval_set *pred,
+                              const int *sx_lut, const int *sy_lut, int map_h, int map_w,
+                              unsigned long long *hist_win /*[n_windows][classes*classes] device*/, int *err_word,
+                              void *hip_stream);
+
 /* Host-side polygon extraction for the per-crop labelme JSON (boundary_extractor.py:33-47): borders of a binary
  * uint8 image (Suzuki-Abe border following, every outer and hole border = RETR_LIST; simple != 0 keeps only the
  * points where the direction changes = CHAIN_APPROX_SIMPLE), perimeter and Ramer-Douglas-Peucker simplification of
