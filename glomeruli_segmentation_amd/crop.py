@@ -15,8 +15,8 @@ Without OpenSlide -- this image -- the PNG branch of the detector's command line
 196-234): the slide is a PNG at 1/downsample of level 0 under <wsi_dir>/<slide>/, its downsample stands in the target list's
 metadata line, and a level-0 region is that PNG sampled at floor(level-0 coordinate / downsample) -- a stand-in for the
 pyramid's level 0 that keeps every file contract (names, sizes, channel order).  The ground-truth branch (`scan_files`:
-annotation XML + labelme shapes -> label PNGs, :388-392) needs the GT tooling that is out of scope:
-its three directories are parsed, and refused with an explanation when the reference would take that branch.
+annotation XML + labelme shapes -> label PNGs and recall, :388-392) is `python -m glomeruli_segmentation_amd.crop_gt` with
+these flags: its directories are parsed here, and refused with a pointer to that command when the reference would take it.
 """
 import glob
 import os
@@ -122,8 +122,9 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     # the reference takes the ground-truth branch unless the JSON or the XML directory is missing (:388)
     if args.seg_gt_json_dir is not None and args.ob_gt_xml_dir is not None:
-        print("the ground-truth branch (scan_files: annotation XML + labelme shapes -> label PNGs) is outside the rebuilt path; "
-              "leave --segmentation_gt_json_dir / --object_detection_gt_xml_dir unset to write the crops only", file=sys.stderr)
+        print("the ground-truth branch (scan_files: annotation XML + labelme shapes -> label PNGs and recall) is the command "
+              "`python -m glomeruli_segmentation_amd.crop_gt` with the same flags; leave --segmentation_gt_json_dir / "
+              "--object_detection_gt_xml_dir unset to write the crops only", file=sys.stderr)
         return 2
     output_org_files(args)
     return 0

@@ -110,15 +110,17 @@ def membership(cores, slide_w, slide_h, window):
 
 
 # --------------------------------------------------------------------------- annotation input
-def read_xml_boxes(path):
-    """AnnotationHandler.read_annotation (annotation_handler.py:35-56): [x1, y1, x2, y2] floats per <object>"""
-    boxes = []
+def read_xml_boxes(path, names=False):
+    """AnnotationHandler.read_annotation (annotation_handler.py:35-56): [x1, y1, x2, y2] floats per <object>; with names=True
+    also the <name> text of each object (gt_name_list), as (boxes, names)"""
+    boxes, labels = [], []
     for obj in ElementTree.parse(path).findall('object'):
         bb = obj.find('bndbox')
         if bb is None:
             raise ValueError("Unknown object is found in:" + os.path.basename(path))
         boxes.append([float(bb.find(k).text) for k in ('xmin', 'ymin', 'xmax', 'ymax')])
-    return boxes
+        labels.append(obj.find('name').text if obj.find('name') is not None else None)
+    return (boxes, labels) if names else boxes
 
 
 def slide_key(body, staining, patient_id):
