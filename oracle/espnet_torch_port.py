@@ -50,30 +50,52 @@ def _esp(x, sd, p):                                    # Model.py:187-214
 
 
 @torch.no_grad()
-def espnet_forward(x, sd, p=2, q=8):
-    """x: fp32 [N,3,H,W] CPU tensor -> logits [N,classes,H,W]."""
+def espnet_forward(x, sd, p=2, q=8, stages=None):
+    """x: [N,3,H,W] CPU tensor -> logits [N,classes,H,W], in the dtype of x and sd (fp32, or fp64 through
+    cast_state_dict).  stages: a dict that receives the activations under the C oracle's stage names
+    (oracle/espnet_oracle.py), plus "combine_t" = BR(cat([level3_C, up_l3])), which the HIP engine also keeps."""
+    def rec(k, v):
+        if stages is not None:
+            stages[k] = v
+        return v
     e = "encoder."
-    out0 = _cbr(x, sd, e + "level1", 2)
-    inp1 = F.avg_pool2d(x, 3, 2, 1)
-    inp2 = F.avg_pool2d(inp1, 3, 2, 1)
-    out0_cat = _br(torch.cat([out0, inp1], 1), sd, e + "b1")
-    out1_0 = _down(out0_cat, sd, e + "level2_0")
+    out0 = rec("level1", _cbr(x, sd, e + "level1", 2))
+    inp1 = rec("sample1", F.avg_pool2d(x, 3, 2, 1))
+    inp2 = rec("sample2", F.avg_pool2d(inp1, 3, 2, 1))
+    out0_cat = rec("b1", _br(torch.cat([out0, inp1], 1), sd, e + "b1"))
+    out1_0 = rec("level2_0", _down(out0_cat, sd, e + "level2_0"))
     out1 = out1_0
     for i in range(p):
-        out1 = _esp(out1, sd, e + "level2.%d" % i)
-    out1_cat = _br(torch.cat([out1, out1_0, inp2], 1), sd, e + "b2")
-    out2_0 = _down(out1_cat, sd, e + "level3_0")
+        out1 = rec("level2.%d" % i, _esp(out1, sd, e + "level2.%d" % i))
+    out1_cat = rec("b2", _br(torch.cat([out1, out1_0, inp2], 1), sd, e + "b2"))
+    out2_0 = rec("level3_0", _down(out1_cat, sd, e + "level3_0"))
     out2 = out2_0
     for i in range(q):
-        out2 = _esp(out2, sd, e + "level3.%d" % i)
-    out2_cat = _br(torch.cat([out2_0, out2], 1), sd, e + "b3")
-    out2_c = F.conv_transpose2d(_bn(F.conv2d(out2_cat, _t(sd, e + "classifier.conv.weight")), sd, "br"),
-                                _t(sd, "up_l3.0.weight"), None, 2)
-    out1_c = F.conv2d(out1_cat, _t(sd, "level3_C.conv.weight"))
-    t = _cbr(_br(torch.cat([out1_c, out2_c], 1), sd, "combine_l2_l3.0"), sd, "combine_l2_l3.1")
-    comb = _br(F.conv_transpose2d(t, _t(sd, "up_l2.0.weight"), None, 2), sd, "up_l2.1")
-    feat = _cbr(torch.cat([comb, out0_cat], 1), sd, "conv")
-    return F.conv_transpose2d(feat, _t(sd, "classifier.weight"), None, 2)
+        out2 = rec("level3.%d" % i, _esp(out2, sd, e + "level3.%d" % i))
+    out2_cat = rec("b3", _br(torch.cat([out2_0, out2], 1), sd, e + "b3"))
+    enc_cls = rec("enc_classifier", F.conv2d(out2_cat, _t(sd, e + "classifier.conv.weight")))
+    out2_c = rec("up_l3", F.conv_transpose2d(rec("br", _bn(enc_cls, sd, "br")), _t(sd, "up_l3.0.weight"), None, 2))
+    out1_c = rec("level3_C", F.conv2d(out1_cat, _t(sd, "level3_C.conv.weight")))
+    t = rec("combine_t", _br(torch.cat([out1_c, out2_c], 1), sd, "combine_l2_l3.0"))
+    t = rec("combine_l2_l3", _cbr(t, sd, "combine_l2_l3.1"))
+    comb = rec("up_l2", _br(F.conv_transpose2d(t, _t(sd, "up_l2.0.weight"), None, 2), sd, "up_l2.1"))
+    feat = rec("conv", _cbr(torch.cat([comb, out0_cat], 1), sd, "conv"))
+    return rec("classifier", F.conv_transpose2d(feat, _t(sd, "classifier.weight"), None, 2))
+
+
+def cast_state_dict(sd, dtype=torch.float64):
+    """{key: numpy array | tensor} -> {key: CPU tensor}, floating-point entries cast to dtype (counters stay integers)."""
+    out = {}
+    for k in sd:
+        v = _t(sd, k)
+        out[k] = v.to(dtype) if v.is_floating_point() else v
+    return out
+
+
+def forward64(tiles_u8, sd, mean, std, p=2, q=8, stages=None):
+    """uint8 [N,H,W,3] BGR -> float64 logits [N,classes,H,W].  Preprocessing stays in fp32, exactly as the reference and
+    the HIP stem compute it; the normalised input is then upcast and the whole network runs in float64."""
+    return espnet_forward(preprocess(tiles_u8, mean, std).to(torch.float64), cast_state_dict(sd), p, q, stages)
 
 
 def preprocess(tiles_u8, mean, std):

@@ -1,0 +1,414 @@
+"""Every kernel form forward_impl (csrc/espnet.hip) can pick, checked against a float64 reference.
+
+forward_impl does not run one kernel per layer: per launch it picks a conv_mfma_kernel instantiation from the batch size,
+the tile size and the device's CU count.  forms() restates that choice.  test_dispatch_tripwire holds the restatement to
+the source text, test_cases_cover_every_form makes the GPU cases reach every form forms() can return, and each GPU case
+checks three tiles of its batch -- every stage the engine still holds after the forward, the logits, the mask and the
+counts -- against oracle/espnet_torch_port.py run in float64.
+
+One bound per stage: max|got - ref64| <= tau * max(1, max|ref64|).  test_bounds_discriminate shows on the CPU that the
+fp32 C oracle passes them on every case's shape, and that they reject a 1e-4 change of one element in a stage's last
+column, a zeroed d16 tap row and a dropped K-tail channel.
+"""
+import os
+import re
+from collections import namedtuple
+
+import numpy as np
+import pytest
+
+from conftest import REPO, load_weights, random_state_dict
+from test_gpu_parity import DEC_STAGE_TOL, ENC_STAGE_TOL, LOGIT_TOL
+
+CSRC = os.path.join(REPO, "glomeruli_segmentation_amd", "csrc")
+RANDOM_MEAN_STD = ((120.0, 130.0, 110.0), (60.0, 55.0, 70.0))
+
+# ---------------------------------------------------------------------------------------------- the dispatch, restated
+# the shipped defaults of espnet_config.h the dispatch reads (test_dispatch_tripwire pins each one)
+CONFIG = {"CFG_SMALL2_WAVES": 4, "CFG_SMALL3_WAVES": 8, "L2SP": 4, "CFG_L3_DOWN_P2": 1, "CFG_L3_LAST_P2": 1,
+          "CFG_L3_W16": 0, "CFG_L2_DOWN_SKIP": 1, "CFG_LAZY_B2": 1, "CFG_FUSE_L2": 1, "CFG_FUSE_L3": 2,
+          "CFG_L3_FUSE_P4": 0}
+# pixels per lane of the configurations whose vector mapping the width decides (the 9th template argument)
+PIXELS_PER_LANE = {"CFG_L2_BR_P4": "L2SP", "CFG_L2_BR_P4S": "L2SP", "CFG_L2_BR_P2S": "2", "CFG_L3_BR": "4",
+                   "CFG_L3_BR_P2R": "2"}
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def padded_classes(classes):
+    return 5 if classes == 5 else cdiv(classes, 4) * 4                                  # Model::cp, espnet.hip:998
+
+
+def forms(n, H, W, p, q, classes, num_cus):
+    """launch class -> the form forward_impl runs for it (espnet.hip:529-831).  "+F_VEC" is the vector pixel mapping;
+    launch_vec (espnet.hip:48-54) takes it when the output width is a multiple of the form's pixels per lane."""
+    small2_waves, small3_waves, l2sp = CONFIG["CFG_SMALL2_WAVES"], CONFIG["CFG_SMALL3_WAVES"], CONFIG["L2SP"]
+    H2, W2, H3, W3, W1 = H // 4, W // 4, H // 8, W // 8, W // 2
+
+    def vec(ok):
+        return "+F_VEC" if ok else ""
+    f = {}
+    small2 = n * H2 * cdiv(W2, 64) * 2 <= num_cus * small2_waves and W2 % 2 == 0        # :529
+    if p > 0:   # lazy b2 (:530-531); the down-sampler and every ESP block but the last compute the next 1x1 reduce
+        if small2:
+            f["l2_down"] = "CFG_L2_BR_P2S+F_VEC"                                        # :539-540
+        elif W2 % l2sp == 0:
+            f["l2_down"] = "CFG_L2_BR_P4S+F_VEC+F_SKIP_PAD"                             # :542-544
+        else:
+            f["l2_down"] = "CFG_L2_BR_P4"                                               # :546
+        esp = "CFG_L2_BR_P2S+F_VEC" if small2 else "CFG_L2_BR_P4" + vec(W2 % l2sp == 0)  # :575-585
+        if p > 1:
+            f["l2_esp_fused"] = esp
+        f["l2_esp_last"] = esp
+        f["l3_reduce"] = ("CFG_L3_C1S_BNL_P1" if n * H3 * cdiv(W3, 128) * 4 <= num_cus * 8     # :618-621
+                          else "CFG_L3_C1S_BNL")
+    else:       # p = 0: nothing to fuse into; b2 runs as a kernel of its own (:595-600)
+        f["l2_down"] = "unfused CFG_L2_BR_P4" + vec(W2 % l2sp == 0)                     # :557
+        f["cat_b2"] = "cat_b2_kernel"
+        f["l3_reduce"] = "CFG_L3_C1S"                                                   # :623
+    small3 = n * H3 * cdiv(W3, 64) * 2 <= num_cus * small3_waves                        # :608
+    if q > 0:
+        fused = "CFG_L3_BR_P1R" if small3 else "CFG_L3_BR_P2R+F_VEC" if W3 % 2 == 0 else "CFG_L3_BR_P2F"
+        f["l3_down"] = fused                                                            # :628-641
+        if q > 1:
+            f["l3_esp_fused"] = fused                                                   # :661-682
+        f["l3_esp_last"] = ("CFG_L3_BR_P1R" if small3 else "CFG_L3_BR_P2R+F_VEC" if W3 % 2 == 0   # :684-698
+                            else "CFG_L3_BR_P2")
+    else:
+        f["l3_down"] = "unfused CFG_L3_BR" + vec(W3 % 4 == 0)                           # :643
+    cp = padded_classes(classes)
+    if cp < 12:
+        f["dec3"] = "dec3_kernel"                                                       # :769-782
+    elif cp <= 16:
+        f["dec3"] = "MFMA MT16" + vec(W2 % 8 == 0)                                      # :753-754
+    else:
+        f["dec3"] = "MFMA MT32" + vec(W2 % 4 == 0)                                      # :755-756
+    if cp == 5:
+        f["dec_conv"] = "dec_tail_kernel"                                               # :786-816
+    elif cp <= 16:
+        f["dec_conv"] = "MFMA MT16" + vec(W1 % 8 == 0)                                  # :826-827
+    else:
+        f["dec_conv"] = "MFMA MT32" + vec(W1 % 4 == 0)                                  # :828-829
+    return f
+
+
+def edges(H, W):
+    """the shape edges of the large forms: a lone last row of the level-3 stride-2 reduce's row pairs (odd H/8) and a
+    ragged last 64-pixel level-3 task (W/8 not a multiple of 64)"""
+    out = set()
+    if (H // 8) % 2:
+        out.add("lone_row")
+    if (W // 8) % 64:
+        out.add("ragged_task")
+    return out
+
+
+# every conv_mfma launch site of forward_impl in source order: its configuration, plus F_VEC / F_SKIP_PAD where its flags
+# name them ("launch_vec": the vector mapping is chosen from the width, espnet.hip:48-54)
+LAUNCH_SITES = [
+    "CFG_L2_C1S",                                                                                   # :501
+    "launch_vec CFG_L2_BR_P2S", "CFG_L2_BR_P4S+F_VEC+F_SKIP_PAD", "launch_vec CFG_L2_BR_P4",        # :540-546
+    "launch_vec CFG_L2_BR_P4", "launch_vec CFG_L2_BR_P4", "launch_vec CFG_L2_BR_P4",                # :548-555
+    "launch_vec CFG_L2_BR_P4",                                                                      # :557
+    "CFG_L2_C1",                                                                                    # :570
+    "launch_vec CFG_L2_BR_P2S", "launch_vec CFG_L2_BR_P4",                                          # :577-579
+    "launch_vec CFG_L2_BR_P2S", "launch_vec CFG_L2_BR_P4", "launch_vec CFG_L2_BR_P4",               # :583-587
+    "CFG_L3_C1S_BNL_P1", "CFG_L3_C1S_BNL", "CFG_L3_C1S",                                            # :619-623
+    "CFG_L3_BR_P1R", "CFG_L3_BR_W16", "CFG_L3_BR_P2R+F_VEC", "CFG_L3_BR+F_VEC", "CFG_L3_BR_P2F",    # :629-641
+    "launch_vec CFG_L3_BR",                                                                         # :643
+    "CFG_L3_C1",                                                                                    # :656
+    "CFG_L3_BR_P1R", "CFG_L3_BR_W16", "CFG_L3_BR+F_VEC", "CFG_L3_BR_P2R+F_VEC", "CFG_L3_BR_P2F",    # :663-682
+    "CFG_L3_BR_P1R", "CFG_L3_BR_W16", "CFG_L3_BR_P2R+F_VEC", "CFG_L3_BR+F_VEC", "CFG_L3_BR_P2",     # :685-698
+    "launch_vec 16, 8, 2 * CLS, 9, 1, 1, CLS, CLS, 8, 3", "launch_vec 32, 8, 2 * CLS, 9, 1, 1, CLS, CLS, 4, 3",  # :754-756
+    "launch_vec 16, 8, CINP, 9, 1, 1, CLS, CLS, 8, 3", "launch_vec 32, 8, CINP, 9, 1, 1, CLS, CLS, 4, 3",        # :827-829
+]
+
+# the predicates forms() restates, as espnet.hip spells them (whitespace aside), and how often each occurs there
+PREDICATES = [
+    ("static constexpr bool no_vec() { return false; }", 1),                                        # :42
+    ("if (ca.W % cfg[8] == 0 && !no_vec())", 1),                                                    # :51
+    ("a.H = out.H; a.W = out.W;", 1),                                                               # :419-420
+    ("const bool small2 = CFG_SMALL2_WAVES > 0 && (long long)n * H2 * cdiv(W2, 64) * 2 <= "
+     "(long long)m->num_cus * CFG_SMALL2_WAVES && W2 % 2 == 0 && !no_vec();", 1),                   # :529
+    ("const bool fuse_b2 = m->p > 0;", 1),                                                          # :530
+    ("const bool lazy_b2 = fuse_b2 && CFG_LAZY_B2;", 1),                                            # :531
+    ("if (ca.W % L2SP == 0 && !no_vec())", 1),                                                      # :543
+    ("const bool small3 = (long long)n * H3 * cdiv(W3, 64) * 2 <= (long long)m->num_cus * CFG_SMALL3_WAVES "
+     "&& !no_vec();", 1),                                                                           # :608
+    ("if ((long long)n * H3 * cdiv(W3, 128) * 4 <= (long long)m->num_cus * 8)", 1),                 # :618
+    ("if (ca.W % 2 == 0 && !no_vec())", 3),                                                         # :634, :676, :691
+    ("if (ca.W % 4 == 0 && !no_vec())", 3),                                                         # :639, :669, :696
+    ("if constexpr (CLS >= 12)", 1),                                                                # :748
+    ("if constexpr (CLS <= 16)", 2),                                                                # :753, :826
+    ("if constexpr (CLS == 5)", 1),                                                                 # :786
+    ("m.cp = classes == 5 ? 5 : (classes + 3) / 4 * 4;", 1),                                        # :998
+    ('auto next2 = [&](int i) { return (CFG_FUSE_L2 && i < p) ? e + "level2." + std::to_string(i) : std::string(); };',
+     1),                                                                                            # :1037
+    ('auto next3 = [&](int i) { return ((CFG_FUSE_L3 == 2 || (CFG_FUSE_L3 == 1 && i == 0)) && i < q) ? e + "level3." + '
+     'std::to_string(i) : std::string(); };', 1),                                                   # :1038
+]
+
+
+def _flat(text):
+    return " ".join(text.split())
+
+
+def _read(name):
+    with open(os.path.join(CSRC, name)) as fh:
+        return fh.read()
+
+
+def launch_sites(body):
+    out = []
+    for m in re.finditer(r"launch_(conv_mfma|vec)<(.*?)>\(", _flat(body)):
+        if m.group(1) == "vec":
+            out.append("launch_vec " + m.group(2).split(", ", 1)[1])
+        else:
+            cfg, flags = m.group(2).split(", ", 1)
+            out.append(cfg + "".join("+" + f for f in ("F_VEC", "F_SKIP_PAD") if re.search(r"\b%s\b" % f, flags)))
+    return out
+
+
+def test_dispatch_tripwire():
+    """forms() restates the dispatch as the source reads today.  A changed predicate, launch site or default fails here,
+    so that the restatement and the GPU cases are updated with it instead of silently losing coverage."""
+    src = _read("espnet.hip")
+    flat = _flat(src)
+    for text, count in PREDICATES:
+        assert flat.count(_flat(text)) == count, text
+    body = src[src.index("static gs_status forward_impl("):src.index("static gs_status forward_any(")]
+    assert launch_sites(body) == LAUNCH_SITES
+    cfg = _read("espnet_config.h")
+    for name, value in CONFIG.items():
+        m = re.search(r"#ifndef %s\n#define %s (\S+)" % (name, name), cfg)
+        assert m and m.group(1) == str(value), name
+    for name, p in PIXELS_PER_LANE.items():
+        m = re.search(r"#define %s\s+([^/\n]+)" % name, cfg)
+        assert m and m.group(1).split(",")[8].strip() == p, name
+
+
+# ---------------------------------------------------------------------------------------------- the cases
+Case = namedtuple("Case", "name weights classes p q H W n256 targets edges")
+L2_SMALL, L3_SMALL = "CFG_L2_BR_P2S+F_VEC", "CFG_L3_BR_P1R"
+L2_SKIP, L2_VEC, P2R = "CFG_L2_BR_P4S+F_VEC+F_SKIP_PAD", "CFG_L2_BR_P4+F_VEC", "CFG_L3_BR_P2R+F_VEC"
+CASES = [
+    Case("A", "fold1", 5, 2, 8, 512, 1024, 1,       # every small-batch form at full size
+         {"l2_down": L2_SMALL, "l2_esp_fused": L2_SMALL, "l2_esp_last": L2_SMALL, "l3_reduce": "CFG_L3_C1S_BNL_P1",
+          "l3_down": L3_SMALL, "l3_esp_fused": L3_SMALL, "l3_esp_last": L3_SMALL}, set()),
+    Case("B", "fold1", 5, 2, 8, 512, 1024, 9,       # the headline forms
+         {"l2_down": L2_SKIP, "l2_esp_fused": L2_VEC, "l2_esp_last": L2_VEC, "l3_reduce": "CFG_L3_C1S_BNL",
+          "l3_down": P2R, "l3_esp_fused": P2R, "l3_esp_last": P2R}, set()),
+    Case("C", "fold1", 5, 2, 8, 264, 1000, 16,      # H/8 = 33, W/8 = 125: the odd-width forms, non-vector level 2
+         {"l2_down": "CFG_L2_BR_P4", "l2_esp_fused": "CFG_L2_BR_P4", "l2_esp_last": "CFG_L2_BR_P4",
+          "l3_reduce": "CFG_L3_C1S_BNL", "l3_down": "CFG_L3_BR_P2F", "l3_esp_fused": "CFG_L3_BR_P2F",
+          "l3_esp_last": "CFG_L3_BR_P2"}, {"lone_row", "ragged_task"}),
+    Case("D", "fold1", 5, 2, 8, 136, 1040, 21,      # W/8 = 130 = 2 * 64 + 2, H/8 = 17
+         {"l2_down": L2_SKIP, "l3_reduce": "CFG_L3_C1S_BNL", "l3_down": P2R, "l3_esp_fused": P2R, "l3_esp_last": P2R},
+         {"lone_row", "ragged_task"}),
+    Case("E", "random", 20, 2, 3, 512, 1024, 9,     # the MT 32 decoder forms at a large batch
+         {"l3_reduce": "CFG_L3_C1S_BNL", "l3_esp_fused": P2R, "dec3": "MFMA MT32+F_VEC",
+          "dec_conv": "MFMA MT32+F_VEC"}, set()),
+    Case("F", "random", 12, 2, 2, 264, 1000, 16,    # MFMA dec3, non-vector MT 16 decoder convs
+         {"l3_reduce": "CFG_L3_C1S_BNL", "l3_down": "CFG_L3_BR_P2F", "dec3": "MFMA MT16", "dec_conv": "MFMA MT16"},
+         {"lone_row", "ragged_task"}),
+    Case("G", "random", 7, 0, 1, 264, 1000, 16,     # p = 0: unfused b2, non-lazy stride-2 reduce; the only L3 block is the last
+         {"l2_down": "unfused CFG_L2_BR_P4", "cat_b2": "cat_b2_kernel", "l3_reduce": "CFG_L3_C1S",
+          "l3_down": "CFG_L3_BR_P2F", "l3_esp_last": "CFG_L3_BR_P2", "dec3": "dec3_kernel", "dec_conv": "MFMA MT16"},
+         {"lone_row", "ragged_task"}),
+    Case("H", "random", 5, 3, 0, 512, 1024, 9,      # q = 0: the unfused level-3 down-sampler
+         {"l2_down": L2_SKIP, "l3_reduce": "CFG_L3_C1S_BNL", "l3_down": "unfused CFG_L3_BR+F_VEC"}, set()),
+    Case("I", "random", 16, 0, 2, 512, 1024, 9,     # the vector forms of the unfused level-2 down-sampler and of MT 16
+         {"l2_down": "unfused CFG_L2_BR_P4+F_VEC", "l3_down": P2R, "dec3": "MFMA MT16+F_VEC",
+          "dec_conv": "MFMA MT16+F_VEC"}, set()),
+    Case("J", "random", 20, 1, 0, 264, 1000, 16,    # the non-vector unfused level-3 down-sampler and MT 32 dec3
+         {"l2_esp_last": "CFG_L2_BR_P4", "l3_reduce": "CFG_L3_C1S_BNL", "l3_down": "unfused CFG_L3_BR",
+          "dec3": "MFMA MT32", "dec_conv": "MFMA MT32+F_VEC"}, {"lone_row", "ragged_task"}),
+]
+
+
+def batch_for(case, num_cus):
+    """the smallest batch whose launches take the case's target forms on a device with num_cus CUs"""
+    for n in range(1, 8 * num_cus + 1):
+        f = forms(n, case.H, case.W, case.p, case.q, case.classes, num_cus)
+        if all(f.get(k) == v for k, v in case.targets.items()):
+            return n
+    raise AssertionError("case %s: no batch reaches %s on %d CUs" % (case.name, case.targets, num_cus))
+
+
+def reachable_forms(num_cus):
+    """every (launch class, form) forms() returns at legal tile sizes (multiples of 8), depths and class counts"""
+    out = set()
+    for n in (1, 2, 4, 9, 16, 21, 32):
+        for H in (8, 136, 264, 512):
+            for W in range(8, 1048, 8):
+                for p, q in ((0, 0), (0, 1), (0, 2), (1, 0), (1, 1), (2, 2), (2, 8), (3, 0)):
+                    for classes in (2, 5, 7, 12, 16, 20):
+                        out.update(forms(n, H, W, p, q, classes, num_cus).items())
+    return out
+
+
+def test_case_batches_at_256_cus():
+    assert {c.name: batch_for(c, 256) for c in CASES} == {c.name: c.n256 for c in CASES}
+    for c in CASES:
+        assert c.edges <= edges(c.H, c.W), c.name
+
+
+def test_cases_cover_every_form():
+    hit = set()
+    for c in CASES:
+        hit.update(forms(batch_for(c, 256), c.H, c.W, c.p, c.q, c.classes, 256).items())
+    every = reachable_forms(256)
+    assert hit == every, ("not covered: %s" % sorted(every - hit), "not reachable: %s" % sorted(hit - every))
+
+
+def case_weights(case):
+    from glomeruli_segmentation_amd.synth import FOLD_MEAN_STD
+    if case.weights == "fold1":
+        mean, std = FOLD_MEAN_STD[1]
+        return load_weights(1), mean, std
+    mean, std = RANDOM_MEAN_STD
+    return random_state_dict(case.p, case.q, classes=case.classes, seed=4000 + ord(case.name)), mean, std
+
+
+def case_tile(case, k):
+    """tile k of the case's batch: synthetic in even slots, noise in odd ones, no seed used twice"""
+    from glomeruli_segmentation_amd.synth import noise_tile, synth_tile
+    return (noise_tile if k % 2 else synth_tile)(100 * ord(case.name) + k, case.H, case.W)
+
+
+def checked_images(n):
+    """the first, the last and a middle noise tile"""
+    return sorted({0, min((n // 2) | 1, n - 1), n - 1})
+
+
+def engine_stages(case):
+    """the stages EspnetEngine.read_stage still holds after a forward: forward_impl drops a stage when its ping-pong buffer
+    is written again (level2.<i>, level3.<i>), the last level-2 block stores only into b2, and combine_t exists when the
+    class count needs no padding planes"""
+    p, q = case.p, case.q
+    names = ["b1", "sample2", "level2_0"] + ["level2.%d" % i for i in range(max(0, p - 3), p - 1)]
+    names += ["b2", "level3_0"] + ["level3.%d" % i for i in range(max(0, q - 2), q)] + ["up_l3"]
+    if padded_classes(case.classes) == case.classes:
+        names.append("combine_t")
+    return names + ["up_l2", "conv"]
+
+
+def reference(case, sd, mean, std, tiles):
+    """float64 stages (engine_stages) and logits of uint8 tiles [k,H,W,3], each [k,C,h,w]"""
+    from oracle import espnet_torch_port as port
+    stages = {}
+    logits = port.forward64(tiles, sd, mean, std, case.p, case.q, stages)
+    out = {name: stages[name].numpy() for name in engine_stages(case)}
+    out["logits"] = logits.numpy()
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- bounds
+# tau per stage family, relative to max(1, max|ref64|): about four times the fp32 C oracle's own worst error against
+# float64 over all the cases' shapes, a synthetic and a noise tile each (measured: sample2 4e-9, b1 4.5e-7, level-2
+# stages and b2 <= 1.7e-6, everything after <= 3.2e-6).  The fold-1 cases are also held to test_gpu_parity's absolute
+# bounds.
+TAU = {"sample2": 2e-8, "b1": 2e-6, "level2_0": 6e-6, "level2": 6e-6, "b2": 6e-6, "level3_0": 1.2e-5, "level3": 1.2e-5,
+       "up_l3": 1.2e-5, "combine_t": 1.2e-5, "up_l2": 1.2e-5, "conv": 1.2e-5, "logits": 1.2e-5}
+DECODER_STAGES = ("up_l3", "combine_t", "up_l2", "conv")
+
+
+def bound(case, name, ref):
+    b = TAU[name.split(".")[0]] * max(1.0, float(np.abs(ref).max()))
+    if case.weights == "fold1":
+        b = min(b, LOGIT_TOL if name == "logits" else DEC_STAGE_TOL if name in DECODER_STAGES else ENC_STAGE_TOL)
+    return b
+
+
+def stage_errors(case, got, ref):
+    """name -> (max|got - ref|, bound) for every stage of ref"""
+    out = {}
+    for name, r in ref.items():
+        g = np.asarray(got[name], dtype=np.float64)
+        assert g.shape == r.shape, (case.name, name, g.shape, r.shape)
+        out[name] = (float(np.abs(g - r).max()), bound(case, name, r))
+    return out
+
+
+def over(errors):
+    return {name: eb for name, eb in errors.items() if not eb[0] <= eb[1]}
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: c.name)
+def test_bounds_discriminate(case):
+    """On the case's shape the fp32 C oracle passes the bounds, and they reject (a) a 1e-4 * max|ref| change of one element
+    in the last column of any stage, (b) the reference with the bottom tap row of a level-3 d16 weight zeroed -- what a
+    wrong F_SKIP_PAD decision computes -- and (c) with the last input channel of a level-3 reduce dropped, a K-tail bug."""
+    from oracle import espnet_oracle as orc
+    sd, mean, std = case_weights(case)
+    tile = case_tile(case, 0)
+    ref = {name: v[0] for name, v in reference(case, sd, mean, std, tile[None]).items()}
+    st = {}
+    st["logits"] = orc.espnet_forward(orc.preprocess(tile, mean, std), sd, case.p, case.q, st)
+    st["combine_t"] = orc.br(np.concatenate([st["level3_C"], st["up_l3"]], 0), sd, "combine_l2_l3.0")
+    fp32 = {name: st[name] for name in ref}
+    errors = stage_errors(case, fp32, ref)
+    print("case %s, fp32 C oracle vs float64, error / bound: %s" % (
+        case.name, ", ".join("%s %.1e/%.1e" % (k, e, b) for k, (e, b) in errors.items())))
+    assert not over(errors), over(errors)
+    for name, v in fp32.items():
+        bumped = v.copy()
+        bumped[-1, v.shape[1] // 2, -1] += 1e-4 * float(np.abs(ref[name]).max())
+        assert name in over(stage_errors(case, {name: bumped}, {name: ref[name]})), name
+    blk = "encoder.level3.0" if case.q else "encoder.level3_0"
+    for key, part in ((blk + ".d16.conv.weight", (slice(None), slice(None), 2)), (blk + ".c1.conv.weight", (slice(None), -1))):
+        w = np.array(sd[key])
+        w[part] = 0
+        wrong = reference(case, dict(sd, **{key: w}), mean, std, tile[None])
+        assert over(stage_errors(case, {name: v[0] for name, v in wrong.items()}, ref)), key
+
+
+# ---------------------------------------------------------------------------------------------- the GPU cases
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", CASES, ids=lambda c: c.name)
+def test_kernel_form_against_float64(case):
+    """The case's batch on the HIP path, sized from the device's CU count to take its target forms.  Tiles 0, n-1 and a
+    middle one: every stage the engine still holds and the logits within the bounds of float64, the mask the first-max
+    argmax of the returned logits and off the float64 argmax only where its top-2 margin is below the logit bound, the
+    counts its bincount; the mask-only kernels give the same mask and counts."""
+    import torch
+    from glomeruli_segmentation_amd.engine import EspnetEngine
+    assert torch.cuda.is_available(), "the gpu-marked tests need a HIP device"
+    num_cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n = batch_for(case, num_cus)
+    hit = forms(n, case.H, case.W, case.p, case.q, case.classes, num_cus)
+    assert all(hit[k] == v for k, v in case.targets.items()) and case.edges <= edges(case.H, case.W)
+    sd, mean, std = case_weights(case)
+    tiles = np.stack([case_tile(case, k) for k in range(n)])
+    picks = checked_images(n)
+    ref = reference(case, sd, mean, std, tiles[picks])
+    eng = EspnetEngine(sd, classes=case.classes, p=case.p, q=case.q)
+    try:
+        t = torch.from_numpy(tiles).cuda()
+        mask, hist, logits = eng.segment(t, mean, std, want_logits=True)
+        torch.cuda.synchronize()
+        worst = {}
+        for j, k in enumerate(picks):
+            got = {name: eng.read_stage(name, image=k) for name in ref if name != "logits"}
+            got["logits"] = logits[k].cpu().numpy()
+            errors = stage_errors(case, got, {name: v[j] for name, v in ref.items()})
+            for name, eb in errors.items():
+                worst[name] = max(worst.get(name, eb), eb)
+            bad = over(errors)
+            assert not bad, "case %s, image %d of %d: %s" % (case.name, k, n, bad)
+            m = mask[k].cpu().numpy()
+            assert np.array_equal(m, got["logits"].argmax(0).astype(np.uint8)), (case.name, k)   # first maximum wins
+            assert np.array_equal(hist[k].cpu().numpy(), np.bincount(m.ravel(), minlength=case.classes)), (case.name, k)
+            r = ref["logits"][j]
+            top2 = np.partition(r, r.shape[0] - 2, axis=0)[-2:]
+            flips = (m != r.argmax(0)) & (top2[1] - top2[0] >= errors["logits"][1])
+            assert not flips.any(), (case.name, k, int(flips.sum()))
+        m2, h2, _ = eng.segment(t, mean, std)                                    # the mask-only kernels
+        assert torch.equal(m2, mask) and torch.equal(h2, hist)
+        eng.check_device_faults()
+    finally:
+        eng.close()
+    print("case %s: n %d on %d CUs, forms %s; worst error / bound: %s" % (
+        case.name, n, num_cus, hit, ", ".join("%s %.1e/%.1e" % (k, e, b) for k, (e, b) in worst.items())))

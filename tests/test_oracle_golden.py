@@ -98,6 +98,28 @@ def test_torch_port_matches_golden(sd1):
         assert np.abs(out - z["logits_" + tag]).max() <= TOL
 
 
+def test_torch_port_float64_stages(sd1):
+    """the float64 port, the truth of tests/test_kernel_forms.py: fp32 preprocessing bit for bit, every stage within fp32
+    rounding of the C oracle's and within TOL of the reference's own activations"""
+    import torch
+    from oracle import espnet_torch_port as port
+    z = load_golden("stages_fold1.npz")
+    mean, std = FOLD_MEAN_STD[1]
+    assert np.array_equal(port.preprocess(z["tile"][None], mean, std)[0].numpy(), z["input"])
+    s64 = {}
+    out = port.forward64(z["tile"][None], sd1, mean, std, stages=s64)
+    assert out.dtype == torch.float64 and all(v.dtype == torch.float64 for v in s64.values())
+    s32 = {}
+    orc.espnet_forward(orc.preprocess(z["tile"], mean, std), sd1, stages=s32)
+    assert set(s32) <= set(s64)
+    for k, v in s32.items():
+        ref = s64[k][0].numpy()
+        assert np.abs(v - ref).max() <= 2e-6 * max(1.0, float(np.abs(ref).max())), k
+        if k in z.files:
+            assert np.abs(ref - z[k]).max() <= TOL, k
+    assert np.abs(out[0].numpy() - z["logits"]).max() <= TOL
+
+
 @pytest.mark.parametrize("p,q", [(2, 3), (1, 2), (3, 1), (1, 1)])
 def test_other_depths_against_the_reference(p, q):
     """ESPNet(5, p, q) of the REFERENCE with seeded random weights (tests/golden/make_golden_depths.py): the oracle's graph
