@@ -107,7 +107,6 @@ struct ConvArgs {
     // for channels that arrive normalised, and a last all-zero slot.  k-groups [bnl_s0, bnl_s1) hold the raw channels: BN of
     // their zero halo would not be zero, so a tap row above the image takes the zero slot and column -1 is re-zeroed.
     int bnl_s0, bnl_s1;
-    int lds_tile_off;   // F_XMERGE: float offset of the per-wave LDS tiles (after the weight image)
     // GS_DIAG builds only:
     int stagger;   // units of 1024 cycles by which waves WAVES/2.. start late (0 = off)
     int prio_mode; // wave priority of the two halves of a workgroup: 0 alternates per dilation, 1 per task (shipped), 2 off, 3 fixed
@@ -116,7 +115,6 @@ struct ConvArgs {
     int strips;    // pixel strips per output row
     int total_tasks;
     int wu;        // waves of a workgroup that take tasks (launch_conv_mfma: WAVES unless the launch has fewer tasks than wave slots)
-    int rev_n;     // 1: images are taken last to first (the launch reads what its producer wrote most recently first)
 };
 
 typedef unsigned u32x3_t __attribute__((ext_vector_type(3)));
@@ -193,7 +191,6 @@ constexpr int F_RES = 2;     // add the residual input before BN (ESP block, Mod
 constexpr int F_NOSTORE = 4; // skip the primary store (the block output is only consumed through out2)
 constexpr int F_DUAL = 8;     // second store into a concat buffer through a second BN+PReLU: the b2 / b3
                              // "BR over a torch.cat" stages (Model.py:359) fused into the producers
-constexpr int F_XMERGE = 256;   // TAPS == 3 only: the three horizontal taps are folded into the MFMA rows (see kernel)
 constexpr int F_S2PAIR = 512;   // STRIDE == 2, TAPS == 9: the three horizontal taps of an output pixel (inputs 2x-1..2x+1)
                                 // come from one 12-byte load instead of three stride-2 dword loads, which cost the
                                 // texture-address unit 16 cycles each (4 for a unit-stride one)
@@ -216,7 +213,6 @@ constexpr int F_A_GLOBAL = 131072;
 // accumulates W_c1[:, ch] * out[ch] into a second accumulator set that is stored to the next block's reduced map when the
 // task ends.  Removes the separate 1x1 kernel and its re-read of the whole block output.
 constexpr int F_FUSE1X1 = 262144;
-constexpr int F_RES_RING = 524288;   // residual values through a half-slot register ring (see the kernel)
 // Stride-2 3x3 reduces: output rows y and y+1 share input row 2y+1.  Odd output rows walk their three tap rows bottom-up,
 // so that neighbouring tasks (neighbouring waves of one workgroup) ask for the shared row at the same moment -- the end of
 // the even row's k-loop, and of the odd row's -- instead of a whole task apart, when it has long left the caches.
@@ -227,11 +223,6 @@ constexpr int F_S2_FLIP = 1048576;
 // (G == NSTEP) such a chunk is skipped (wave-uniform), and the operand ring is refilled with the next LIVE chunk instead.
 constexpr int F_SKIP_PAD = 4194304;
 constexpr int F_BNLOAD = 8388608;  // see ConvArgs::bnl_s0
-// Branch kernels whose chunk is a whole dilation (level 2): the epilogue of concat slot d -- residual add, BN, PReLU, stores, the
-// fused 1x1's matrix instructions -- is not run in one piece between two dilations (a stretch in which this wave feeds the matrix
-// pipe nothing) but register by register BETWEEN the k-steps of dilation d + 1, from a snapshot of the accumulator (HFF keeps
-// adding into the accumulator itself).  The last slot of a task still runs in one piece.
-constexpr int F_EPI_PIPE = 16777216;
 constexpr int F_X_NOLOAD = 16;  // GS_DIAG timing experiments only (results are garbage): no activation loads in the loop
 constexpr int F_X_NOLDS = 32;   // GS_DIAG: no LDS weight reads in the loop
 constexpr int F_X_NOEPI = 64;   // GS_DIAG: no epilogue at all
@@ -250,11 +241,10 @@ constexpr int F_X_ALL = F_X_NOLOAD | F_X_NOLDS | F_X_NOEPI | F_X_STAMP | F_X_STA
 struct ConvImage {
     int nrow, cout, w, bn, tab, total;
 };
-constexpr ConvImage conv_image(int CINP, int TAPS, int NDIL, int NOUT1, int NOUT, bool bn, bool dual = false, bool xmerge = false,
-                               int fuse_nacc = 0)
+constexpr ConvImage conv_image(int CINP, int TAPS, int NDIL, int NOUT1, int NOUT, bool bn, bool dual = false, int fuse_nacc = 0)
 {
     ConvImage im{};
-    im.nrow = xmerge ? 3 * NOUT1 : (NOUT1 > NOUT ? NOUT1 : NOUT);
+    im.nrow = NOUT1 > NOUT ? NOUT1 : NOUT;
     im.cout = NOUT1 + (NDIL - 1) * NOUT;
     im.w = NDIL * TAPS * CINP * im.nrow;
     im.bn = (bn ? 3 * im.cout : 0) + (dual ? 3 * im.cout : 0);
@@ -263,42 +253,6 @@ constexpr ConvImage conv_image(int CINP, int TAPS, int NDIL, int NOUT1, int NOUT
     return im;
 }
 
-// Waves per SIMD the register allocator must leave room for in the level-2 branch kernels (16x16x4, four pixels per
-// lane).  Round 1 shipped a 9-step operand ring at four waves per SIMD (<= 128 VGPRs); with the fused 1x1 those forms
-// need ~135.  Measured at batch 32 (profiles/README.md): the 27-step ring (G = 9: a whole dilation in flight, ~200-240
-// VGPRs, two waves per SIMD) runs the down-sampler in 0.239 ms against 0.246 and the fused ESP block in 0.1996 against
-// 0.204; forcing four waves onto the fused forms spills and loses 5 %.  So: no floor (1) and the deep ring.
-#ifndef CFG_L2_MINW
-#define CFG_L2_MINW 1
-#endif
-// F_RES_RING: the register ring holds 1 / CFG_RES_RING_DIV of a slot's residual values (2: 24 registers spilled in the
-// fused level-3 ESP kernel, 0.190 ms; 4: no spill but the residual latency shows, 0.192 ms)
-#ifndef CFG_RES_RING_DIV
-#define CFG_RES_RING_DIV 1   // round 6: with the 13-step operand ring (CFG_L3_RING) a whole slot's residual fits (196 registers): requested at
-                             // the top of its dilation (CFG_RES_TOP), no refill inside the epilogue
-#endif
-// ---- round-6 switches of the branch kernels' epilogue and k-step; each measured interleaved on one box with the same bits
-// (profiles/README.md, "Round 6", section 3); the defaults are what ships
-#ifndef CFG_RES_TOP
-#define CFG_RES_TOP 1       // a slot's residual requested at the top of its own dilation: level-2 ESP launch 0.1975 -> 0.194 ms (r06_ab_combo.txt)
-#endif
-#ifndef CFG_EPI_PRIO
-#define CFG_EPI_PRIO 0      // wave priority inside the epilogue (2 or 3 = above both task priorities): level-3 ESP -2 % alone, +0.5 % beside the
-                            // 13-step ring (r06_ab_epiprio.txt, r06_ab_combo.txt): off
-#endif
-#ifndef CFG_EPI_SPLIT
-#define CFG_EPI_SPLIT 0     // the fused 1x1's matrix instructions in one piece behind the slot's arithmetic: 0.1850 -> 0.1878 ms (r06_ab_sp2.txt): off
-#endif
-#ifndef CFG_EPI_PRELOAD
-#define CFG_EPI_PRELOAD 0   // 16x16x4 forms: a slot's BN constants all read up front: ESP unchanged, down-sampler 0.182 -> 0.196 (r06_ab_epi_preload.txt): off
-#endif
-#ifndef CFG_REFILL_MID
-#define CFG_REFILL_MID 0    // ring refill between the matrix instructions of the next step: level-3 ESP 0.1805 -> 0.1788, step +-0.3 % (r06_ab_refill_mid.txt): off
-#endif
-#ifndef CFG_X_EPI
-#define CFG_X_EPI 0   // GS_DIAG timing experiments on the epilogue's memory instructions (results wrong): 1 no residual loads, 2 no result
-                      // stores, 4 residual loads of the even registers only, 8 result stores of the even registers only
-#endif
 #ifndef CFG_STAGE_ROT
 #define CFG_STAGE_ROT 17   // 0 = every workgroup stages the weight image in the same order
 #endif
@@ -312,32 +266,31 @@ constexpr ConvImage conv_image(int CINP, int TAPS, int NDIL, int NOUT1, int NOUT
 #ifndef CFG_L2_RING
 #define CFG_L2_RING 27
 #endif
-constexpr int conv_ring_depth(int MT, int TAPS, int NDIL, int P, int G, int FLAGS)
+constexpr int conv_ring_depth(int MT, int TAPS, int NDIL, int P, int G)
 {
-    return (MT == 32 && TAPS == 9 && NDIL == 5 && (P == 2 || (P == 1 && CFG_L3_RING != 39)) && G == 13) ? CFG_L3_RING
+    return (MT == 32 && TAPS == 9 && NDIL == 5 && (P == 1 || P == 2) && G == 13) ? CFG_L3_RING
            : (MT == 16 && TAPS == 9 && NDIL == 5 && P == 4 && G == 9) ? CFG_L2_RING
                                                                     : G * (TAPS == 9 ? 3 : 1);
 }
-constexpr int conv_min_waves(int MT, int TAPS, int NDIL, int P, int FLAGS)
-{
-    return (MT == 16 && TAPS == 9 && NDIL == 5 && P == 4) ? CFG_L2_MINW : 1;
-}
 
 #define M_KL_OF(MT_) (Mfma<MT_>::KL)
+// The level-2 branch kernels (16x16x4, four pixels per lane) get no occupancy floor from __launch_bounds__.  Round 1 shipped
+// a 9-step operand ring at four waves per SIMD (<= 128 VGPRs); with the fused 1x1 those forms need ~135.  Measured at batch
+// 32 (profiles/README.md): the 27-step ring (G = 9: a whole dilation in flight, ~200-240 VGPRs, two waves per SIMD) runs the
+// down-sampler in 0.239 ms against 0.246 and the fused ESP block in 0.1996 against 0.204; forcing four waves onto the fused
+// forms spills and loses 5 %.
 template <int MT, int WAVES, int CINP, int TAPS, int STRIDE, int NDIL, int NOUT1, int NOUT, int P, int G, int FLAGS>
-__global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TAPS, NDIL, P, FLAGS) * WAVES / 8 : 2) conv_mfma_kernel(const ConvArgs a)
+__global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_mfma_kernel(const ConvArgs a)
 {
     constexpr bool BNACT = FLAGS & F_BNACT, RES = FLAGS & F_RES, STORE1 = !(FLAGS & F_NOSTORE), DUAL = FLAGS & F_DUAL;
     constexpr bool S2P = FLAGS & F_S2PAIR;
-    constexpr bool XMERGE_ = FLAGS & F_XMERGE;
     constexpr bool VEC = FLAGS & F_VEC;
     constexpr bool AGL = FLAGS & F_A_GLOBAL, FUSE = FLAGS & F_FUSE1X1;
     constexpr bool S2FLIP = FLAGS & F_S2_FLIP;
     constexpr bool SKIP = FLAGS & F_SKIP_PAD;
     constexpr bool BNL = FLAGS & F_BNLOAD;
-    constexpr bool EPI_PIPED = FLAGS & F_EPI_PIPE;
     static_assert(!BNL || ((FLAGS & F_S2PAIR) && !(FLAGS & (F_BNACT | F_A_GLOBAL | F_VEC))), "F_BNLOAD is for the plain stride-2 reduce");
-    static_assert(!SKIP || (TAPS == 9 && STRIDE == 1 && !(FLAGS & (F_S2PAIR | F_XMERGE)) && G * M_KL_OF(MT) == CINP),
+    static_assert(!SKIP || (TAPS == 9 && STRIDE == 1 && !(FLAGS & F_S2PAIR) && G * M_KL_OF(MT) == CINP),
                   "F_SKIP_PAD: unit-stride 3x3 with one tap row per chunk");
     static_assert(!S2FLIP || (STRIDE == 2 && TAPS == 9 && NDIL == 1), "F_S2_FLIP is for the stride-2 3x3 reduce");
     static_assert(kDiag || !(FLAGS & F_X_ALL), "timing / stamp variants exist in -DGS_DIAG builds only");
@@ -348,39 +301,25 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
     using M = Mfma<MT>;
     constexpr int KL = M::KL;
     constexpr int NSTEP = CINP / KL;
-    constexpr int NROW = (FLAGS & F_XMERGE) ? 3 * NOUT1 : (NOUT1 > NOUT ? NOUT1 : NOUT);   // MFMA rows in use
+    constexpr int NROW = NOUT1 > NOUT ? NOUT1 : NOUT;   // MFMA rows in use
     constexpr int COUT = NOUT1 + (NDIL - 1) * NOUT;
-    // TAPS == 3 (with F_XMERGE) is a 3x3 convolution whose few output channels o and three horizontal taps tx
-    // are BOTH put on the MFMA rows (row = tx*NOUT1 + o): the k-loop then walks only (tap row, channel) -- a third
-    // of the k-steps, and 3*NOUT1 of MT rows busy instead of NOUT1 -- and the epilogue adds the three row groups
-    // of a pixel's neighbours through a per-wave LDS tile.  Strips overlap by two columns.
-    constexpr bool XMERGE = FLAGS & F_XMERGE;
     constexpr int TYN = TAPS == 1 ? 1 : 3;
     constexpr int TXN = TAPS == 9 ? 3 : 1;
-    constexpr int XSTEP = XMERGE ? P * MT - 2 : P * MT;   // output pixels a strip produces
+    constexpr int XSTEP = P * MT;   // output pixels a strip produces
     // k-steps of one dilation in the order (row group rg = ty*NSTEP + cin-group, tx): tx fastest.  A
     // chunk is G consecutive row groups x all TXN horizontal taps = D steps, so inside a chunk the tap
     // and slot of every step are compile-time constants and only G (ty, cin-group) pairs are decoded
     // on the scalar unit per chunk (decoding every step cost ~40 SALU instructions per 4 MFMAs).
     constexpr int RGN = TYN * NSTEP;          // row groups per dilation
     constexpr int D = G * TXN;                // steps per chunk
-    constexpr int R = conv_ring_depth(MT, TAPS, NDIL, P, G, FLAGS);   // ring depth
-    // REFILL_MID: the refill of a ring slot is issued BETWEEN the matrix instructions of the NEXT step (behind the first half of
-    // them) instead of behind all of its own step's: a wave issues in order, so `mfma, mfma, load, ds_read, scalar work` leaves
-    // everything but the matrix instructions to the one window behind the second of them; with the refill in the middle both windows
-    // are used.  The slot refilled is the previous step's (its own step's B registers are still to be read), so the ring holds R - 1
-    // steps ahead.
-    constexpr bool MID = CFG_REFILL_MID && TAPS == 9 && NDIL == 5 && P >= 2 && !(FLAGS & (F_S2PAIR | F_BNLOAD | F_EPI_PIPE));
-    constexpr int RB = MID ? 1 : 0;   // steps by which the refill lags
+    constexpr int R = conv_ring_depth(MT, TAPS, NDIL, P, G);   // ring depth
     constexpr int RA = R;   // (ring depth of the A operands)
-    static_assert(D % R == 0 && (R == D || !(FLAGS & (F_S2PAIR | F_BNLOAD | F_EPI_PIPE))), "the ring divides the chunk");
+    static_assert(D % R == 0 && (R == D || !(FLAGS & (F_S2PAIR | F_BNLOAD))), "the ring divides the chunk");
     constexpr int CPD = RGN / G;              // chunks per dilation
     constexpr int NCHUNK = NDIL * CPD;
     static_assert(CINP % KL == 0, "k-steps must tile");
-    static_assert(TAPS == 1 || TAPS == 9 || (TAPS == 3 && XMERGE && NDIL == 1 && STRIDE == 1 && 3 * NOUT1 <= MT), "1x1, 3x3 or row-merged 3x3");
+    static_assert(TAPS == 1 || TAPS == 9, "1x1 or 3x3");
     static_assert(RGN % G == 0, "chunk must divide the row groups of one dilation");
-    static_assert(!EPI_PIPED || (CPD == 1 && NDIL > 1 && TAPS == 9 && (FLAGS & F_BNACT) && !(FLAGS & (F_XMERGE | F_SKIP_PAD | F_RES_RING)) && D >= 4 * Mfma<MT>::NACC),
-                  "F_EPI_PIPE: branch kernels whose chunk is one dilation, with a k-step to spare per accumulator register");
     static_assert(NROW <= MT, "one MFMA row block");
     constexpr int KSTR = 4;   // accumulator rows of k-group kq sit KSTR*kq above those of group 0 (both shapes)
 
@@ -394,13 +333,13 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
     constexpr int WFL = NDIL * TAPS * CINP * NROW;
     constexpr int LDS_SRC0 = AGL ? WFL : 0;
     static_assert(!AGL || WFL % 4 == 0, "LDS-DMA source must stay 16-byte aligned");
-    static_assert(!FUSE || (TAPS == 9 && !XMERGE_ && BNACT), "the fused 1x1 follows a branch kernel's epilogue");
+    static_assert(!FUSE || (TAPS == 9 && BNACT), "the fused 1x1 follows a branch kernel's epilogue");
     const float *bnp = lds + (WFL - LDS_SRC0);   // [scale | shift | alpha][COUT] (x2 with F_DUAL)
     constexpr int BNFL = (BNACT ? 3 * COUT : 0) + (DUAL ? 3 * COUT : 0);
     const float *tab = bnp + BNFL;               // F_FUSE1X1: [NDIL][NACC][64] A operands of the next block's 1x1
     // F_BNLOAD: [scale | shift | alpha][BNL_C] right after the (rounded) image
     constexpr int BNL_C = CINP + M::KL;
-    const float *bnl = lds + (conv_image(CINP, TAPS, NDIL, NOUT1, NOUT, BNACT, DUAL, XMERGE_, FUSE ? M::NACC : 0).total - LDS_SRC0);
+    const float *bnl = lds + (conv_image(CINP, TAPS, NDIL, NOUT1, NOUT, BNACT, DUAL, FUSE ? M::NACC : 0).total - LDS_SRC0);
     const __amdgpu_buffer_rsrc_t rsrc_w =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.wpack), 0, AGL ? WFL * 4 : 0, 0x00020000);
 
@@ -457,9 +396,8 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
     for (int task = t0; task < t1 || !staged; task += tstride) {
         const bool idle = task >= t1;   // a wave without work still has to help stage the weights
         const int tk = idle ? (a.total_tasks - 1) : task;
-        const int n0_ = tk / tasks_per_img;
-        const int n = a.rev_n ? a.N - 1 - n0_ : n0_;
-        const int rem = tk - n0_ * tasks_per_img;
+        const int n = tk / tasks_per_img;
+        const int rem = tk - n * tasks_per_img;
         // F_SKIP_PAD: rows near the top / bottom edge skip tap rows and finish early, and a wave's tasks are the SAME row of
         // images `img_stride` apart -- so every other group of images has its rows rotated by half the height (a bijection
         // per image): a wave then owns one edge row and one middle row, and the saving is spread over all waves
@@ -471,17 +409,16 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
 
         const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<float *>(a.in + (long long)n * a.in_sn), 0, a.in_img_bytes, 0x00020000);
-        const int sbase = (a.in_off + y * STRIDE * a.in_pitch + x0 * STRIDE - (XMERGE ? 1 : 0)) * 4;
+        const int sbase = (a.in_off + y * STRIDE * a.in_pitch + x0 * STRIDE) * 4;
         // the wave's next task (itself when this is the last one: a harmless redundant prefetch)
         const int tn = task + tstride < t1 ? task + tstride : tk;
-        const int n0n_ = tn / tasks_per_img;
-        const int n_n = a.rev_n ? a.N - 1 - n0n_ : n0n_;
-        const int rem_n = tn - n0n_ * tasks_per_img;
+        const int n_n = tn / tasks_per_img;
+        const int rem_n = tn - n_n * tasks_per_img;
         const int y0r_n = rem_n / a.strips;
         const int y_n = SKIP && ((n_n / img_stride) & 1) ? (y0r_n + yrot >= a.H ? y0r_n + yrot - a.H : y0r_n + yrot) : y0r_n;
         const __amdgpu_buffer_rsrc_t rsrc_n = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<float *>(a.in + (long long)n_n * a.in_sn), 0, a.in_img_bytes, 0x00020000);
-        const int sbase_n = (a.in_off + y_n * STRIDE * a.in_pitch + (rem_n - y0r_n * a.strips) * XSTEP * STRIDE - (XMERGE ? 1 : 0)) * 4;
+        const int sbase_n = (a.in_off + y_n * STRIDE * a.in_pitch + (rem_n - y0r_n * a.strips) * XSTEP * STRIDE) * 4;
         const bool flip = S2FLIP && (y & 1), flip_n = S2FLIP && (y_n & 1);   // (wave-uniform)
         const __amdgpu_buffer_rsrc_t rout =
             __builtin_amdgcn_make_buffer_rsrc(a.out + (long long)n * a.out_sn, 0, a.out_img_bytes, 0x00020000);
@@ -521,16 +458,12 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
         // The residual (block input) values of a whole concat slot live in dedicated registers and are
         // requested a full dilation ahead of the epilogue that adds them: fetched next to the store,
         // they cost four exposed HBM round trips per slot (measured 33 us of a 183 us launch).
-        // F_RES_RING: only RR registers' worth of residual values is in flight -- register r's slot is refilled with register
-        // r + RR's values (of this concat slot, or of the next one) as soon as the epilogue has consumed it.  With the
-        // fused 1x1 the kernel has no room for a whole slot (16 x P registers) beside its two accumulator sets.
-        constexpr int RR = !RES ? 1 : (FLAGS & F_RES_RING) ? M::NACC / CFG_RES_RING_DIV : M::NACC;
+        constexpr int RR = RES ? M::NACC : 1;
         float resv[RR][P];
-        constexpr bool RES_TOP = RES && RR == M::NACC && CFG_RES_TOP;
         auto load_res = [&](int di, int r) {   // residual values of accumulator register r of concat slot di
             if (!RES)
                 return;
-            if ((FLAGS & F_X_NOEPIMEM) || (kDiag && ((CFG_X_EPI & 1) || ((CFG_X_EPI & 4) && (r & 1))))) {
+            if (FLAGS & F_X_NOEPIMEM) {
 #pragma unroll
                 for (int p = 0; p < P; ++p)
                     resv[r % RR][p] = __builtin_bit_cast(float, di + r + p);
@@ -553,7 +486,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
                 resv[r % RR][p] = __builtin_bit_cast(
                     float, __builtin_amdgcn_raw_buffer_load_b32(rres, live ? vr[p] : OOB, sr, RAUX));
         };
-        auto prefetch_res = [&](int di) {   // everything the ring holds of slot di
+        auto prefetch_res = [&](int di) {   // the whole slot di
 #pragma unroll
             for (int r = 0; r < RR; ++r)
                 load_res(di, r);
@@ -591,7 +524,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
             int ty0, sidx;
             decode_rg(c - di * CPD, g, ty0, sidx);
             const int ty = S2FLIP && fl ? TYN - 1 - ty0 : ty0;
-            const int toff = TAPS == 9 ? ((ty - 1) * a.in_pitch + (tx - 1)) << di : TAPS == 3 ? (ty - 1) * a.in_pitch : 0;
+            const int toff = TAPS == 9 ? ((ty - 1) * a.in_pitch + (tx - 1)) << di : 0;
             const int soff = sb + (toff + sidx * KL * a.in_sc) * 4;
             if ((FLAGS & F_X_NOLOAD) && staged)   // (timing only: the ring keeps the values of the task's first chunk -- no instruction at all)
                 return;
@@ -626,7 +559,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
             int ty0, sidx;
             decode_rg(c - di * CPD, g, ty0, sidx);
             const int ty = S2FLIP && fl ? TYN - 1 - ty0 : ty0;
-            const int tap = TAPS == 9 ? ty * 3 + tx : TAPS == 3 ? ty : 0;
+            const int tap = TAPS == 9 ? ty * 3 + tx : 0;
             if ((FLAGS & F_X_NOLDS) && staged)   // (timing only: the ring keeps the values of the task's first chunk -- no instruction at all)
                 return;
             if (AGL)
@@ -660,21 +593,6 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
         float bt[BNL ? 2 : 1][P][3];
         static_assert(!BNL || G % 2 == 0, "F_BNLOAD: the two-group operand buffer alternates by row-group parity");
         auto bnl_apply = [&](float &dst, float v, float sc2, float sh2, float al2, float pin2, bool zero) {
-#if defined(GS_DIAG) && defined(CFG_BNL_ABLATE)
-            // timing-only ablations (results wrong): 1 = only wait for the operand (no arithmetic), 2 = the arithmetic on a
-            // value that does not come from the operand (no early wait)
-            if (CFG_BNL_ABLATE == 1) {
-                asm volatile("" : "+v"(v));
-                dst = v;
-                return;
-            }
-            float w = sc2;
-            w = w * sc2 + sh2;
-            w = prelu_med3(w, al2, pin2);
-            asm volatile("" ::"v"(w));
-            dst = v;
-            return;
-#endif
             v = v * sc2 + sh2;
             v = prelu_med3(v, al2, pin2);
             dst = zero ? 0.0f : v;
@@ -691,7 +609,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
                 }
 #pragma unroll
                 for (int tx = 0; tx < TXN; ++tx)
-                    if (g * TXN + tx < R - RB)
+                    if (g * TXN + tx < R)
                         fetch_b(rsrc, sbase, c_first, g, tx, flip);
             }
         }
@@ -707,13 +625,9 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
             const int rot = (int)((blockIdx.x * (unsigned)CFG_STAGE_ROT) % (unsigned)(pieces > 0 ? pieces : 1));
             for (int j0 = wid; j0 < pieces; j0 += WAVES) {
                 const int j = j0 + rot < pieces ? j0 + rot : j0 + rot - pieces;
-#if defined(CFG_X_STAGE_PLAIN)
-                *reinterpret_cast<f32x4 *>(lds + j * 256 + lane * 4) = *reinterpret_cast<const f32x4 *>(a.wpack + LDS_SRC0 + j * 256 + lane * 4);
-#else
                 __builtin_amdgcn_global_load_lds(
                     (const __attribute__((address_space(1))) void *)(a.wpack + LDS_SRC0 + j * 256 + lane * 4),
                     (__attribute__((address_space(3))) void *)(lds + j * 256), 16, 0, 0);
-#endif
             }
             // The barrier (with the `s_waitcnt vmcnt(0) lgkmcnt(0)` in front of it) is UNCONDITIONAL on this path: an LDS-DMA
             // instruction is a FLAT operation to the compiler's wait-count pass, and while one may be pending on ANY path into a
@@ -724,10 +638,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
             // the ring and residual experiments of rounds 1-5 were all measured UNDER those forced drains.
             if ((FLAGS & F_X_STAMP2) && lane == 0)
                 a.stamp[wg * STAMP2_SLOTS + STAMP2_SLOTS - 1] = __builtin_amdgcn_s_memrealtime();
-#if defined(CFG_X_BARRIER_COND)
-            if (pieces > 0)
-#endif
-                __syncthreads();
+            __syncthreads();
             staged = true;
         }
         if (idle)
@@ -756,7 +667,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
             for (int g = 0; g < G; ++g)
 #pragma unroll
                 for (int tx = 0; tx < TXN; ++tx)
-                    if (g * TXN + tx < R - RB)
+                    if (g * TXN + tx < R)
                         fetch_a(c_first, g, tx, flip);
         }
 
@@ -770,8 +681,6 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
                 for (int t = 0; t < 3; ++t)
                     bnl_apply(bt[0][p][t], bl[0][p][t], tsc, tsh, tal, tpin, t == 0 && p == 0 && x0 == 0 && px == 0);
         }
-        if (!RES_TOP)
-            prefetch_res(0);
         if (FUSE) {
 #pragma unroll
             for (int p = 0; p < P; ++p)
@@ -787,14 +696,6 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
                 __builtin_amdgcn_s_setprio(1);
         }
 
-        // One accumulator register (channel row r of both k-groups) of concat slot di on its way out: + residual, BN, PReLU,
-        // store(s), the fused 1x1's matrix instructions.  `src` is the accumulator itself or (F_EPI_PIPE) its snapshot.
-        // SPLIT: a slot's outputs are kept (osave) and the fused 1x1's matrix instructions run in one piece behind the slot's
-        // arithmetic and memory instructions.  Interleaved register by register (the round-2 form), every one of them waited for
-        // a free slot of the matrix pipe -- which the SIMD's other wave keeps busy -- in the middle of a serial stretch of LDS reads
-        // and VALU work: an epilogue took 5-7 us, during which that other wave alone could not keep the pipe busy.
-        constexpr bool SPLIT = FUSE && CFG_EPI_SPLIT && !EPI_PIPED;
-        float osave[SPLIT ? M::NACC : 1][P];
         // the per-register constants of an epilogue step: BN scale / shift / PReLU slope of the lane's channel (twice with F_DUAL)
         // and the fused 1x1's A operand
         struct EpiParams {
@@ -809,7 +710,10 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
             EpiParams q;
             // (read at the top of the register's step, not inside the uniform branch around its MFMAs: the LDS
             // latency then runs under the BN / PReLU arithmetic instead of in front of the matrix instructions)
-            q.a2 = (FUSE && !SPLIT) ? tab[(di * M::NACC + r) * 64 + lane] : 0.0f;
+            // (`&& BNACT` is implied by the static_assert on F_FUSE1X1 and `FUSE ?` alone means the same; it is spelt out only because
+            // the bare form made hipcc schedule one kernel WITHOUT the fused 1x1 differently when the dead epilogue variants were
+            // removed, and that removal was checked by identical assembly.  Safe to simplify with an A/B of the step at hand.)
+            q.a2 = (FUSE && BNACT) ? tab[(di * M::NACC + r) * 64 + lane] : 0.0f;
             if (BNACT) {
                 const float *bp = bnp + (live ? cb + ch0 + kq * KSTR : 0);
                 q.scale = bp[0];
@@ -823,16 +727,15 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
             }
             return q;
         };
-        // EPI_PRELOAD (few accumulator registers: the 16x16x4 forms): a slot's constants are all requested up front -- read register
-        // by register, each of the four steps began with three or four LDS reads and a wait for them
-        constexpr bool EPI_PRELOAD = CFG_EPI_PRELOAD && M::NACC <= 4 && !EPI_PIPED;
-        auto epi_reg = [&](int di, auto r_, const typename M::acc_t *src, bool refill_next, const EpiParams *pre = nullptr) __attribute__((always_inline)) {
+        // One accumulator register (channel row r of both k-groups) of concat slot di on its way out: + residual, BN, PReLU,
+        // store(s), the fused 1x1's matrix instructions.
+        auto epi_reg = [&](int di, auto r_) __attribute__((always_inline)) {
             constexpr int r = decltype(r_)::value;
             const int nout = di == 0 ? NOUT1 : NOUT;
             const int cb = di == 0 ? 0 : NOUT1 + (di - 1) * NOUT;
             const int ch0 = M::row(r, 0);   // channel held by k-group 0; group kq holds ch0 + kq*KSTR
             const bool live = ch0 + kq * KSTR < nout;
-            const EpiParams q = pre ? pre[r] : epi_params(di, r_);
+            const EpiParams q = epi_params(di, r_);
             const float a2 = q.a2;
             const int so = (cb + ch0) * a.out_sc * 4 + sout;
             const int so2 = DUAL ? (a.out2_coff + cb + ch0) * a.out2_sc * 4 + sout2 : 0;
@@ -841,7 +744,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
             const float pin = prelu_pin(alpha), pin2 = prelu_pin(alpha2);
 #pragma unroll
             for (int p = 0; p < P; ++p) {
-                float v = src[p][r];
+                float v = acc[p][r];
                 if (RES)
                     v += resv[r % RR][p];
                 if (BNACT) {
@@ -860,52 +763,17 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
                                                               live ? vo2[p] : OOB, so2, SAUX2);
                 }
             }
-            if (RES && RR < M::NACC) {   // the slot just consumed is refilled at once (uniform control flow)
-                if (r + RR < M::NACC)
-                    load_res(di, r + RR);
-                else if (di + 1 < NDIL)
-                    load_res(di + 1, r + RR - M::NACC);
-            }
-            if (RES && refill_next && di + 1 < NDIL)   // F_EPI_PIPE: register r's residual of the NEXT slot, a dilation ahead of its use
-                load_res(di + 1, r);
-            if (VEC && STORE1 && !(FLAGS & F_X_NOEPIMEM) && !(kDiag && ((CFG_X_EPI & 2) || ((CFG_X_EPI & 8) && (r & 1)))))
+            if (VEC && STORE1 && !(FLAGS & F_X_NOEPIMEM))
                 buf_store_vec<P, SAUX>(rout, live ? ((FLAGS & F_X_STL2) ? ((int)(wg & 255) * 8192 + ((vo[0] + so) & 0x1ff0)) : vo[0] + so) : OOB, o1);
             if (VEC && DUAL)
                 buf_store_vec<P, SAUX2>(rout2, live ? vo2[0] + so2 : OOB, o2);
             if (FUSE && ch0 < nout) {   // (uniform) registers whose two channels are both beyond the slot hold nothing
                 // k = lane's k-group <-> channel cb + ch0 + kq*KSTR; the table row is zero for channels beyond the slot
 #pragma unroll
-                for (int p = 0; p < P; ++p) {
-                    if (SPLIT)
-                        osave[SPLIT ? r : 0][p] = o1[p];
-                    else
-                        acc2[p] = M::run(a2, o1[p], acc2[p]);
-                }
+                for (int p = 0; p < P; ++p)
+                    acc2[p] = M::run(a2, o1[p], acc2[p]);
             }
         };
-        // SPLIT: the fused 1x1's matrix instructions of a whole slot, after the slot's arithmetic, loads and stores (same
-        // accumulation order per accumulator: registers 0, 1, 2, ...)
-        auto epi_fused = [&](int di) __attribute__((always_inline)) {
-            static_for<M::NACC>([&](auto r_) {
-                constexpr int r = decltype(r_)::value;
-                const int nout = di == 0 ? NOUT1 : NOUT;
-                if (M::row(r, 0) < nout) {
-                    const float a2 = tab[(di * M::NACC + r) * 64 + lane];
-#pragma unroll
-                    for (int p = 0; p < P; ++p)
-                        acc2[p] = M::run(a2, osave[SPLIT ? r : 0][p], acc2[p]);
-                }
-            });
-        };
-        typename M::acc_t snap[EPI_PIPED ? P : 1];   // F_EPI_PIPE: the accumulator as the previous dilation left it
-#if defined(GS_DIAG) && defined(CFG_X_S2_EXTRA)
-        typename M::acc_t xacc[BNL ? P : 1];
-        if (BNL) {
-#pragma unroll
-            for (int p = 0; p < P; ++p)
-                xacc[p] = (typename M::acc_t)(0.0f);
-        }
-#endif
 
         for (int c = 0; c < NCHUNK; ++c) {
             if (NDIL > 1 && c % CPD == 0 && prio_mode == 0) {
@@ -917,11 +785,11 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
                 else
                     __builtin_amdgcn_s_setprio(0);
             }
-            // RES_TOP: a slot's residual is requested at the top of its own dilation (a dilation of k-steps ahead of the epilogue that
+            // A slot's residual is requested at the top of its own dilation (a dilation of k-steps ahead of the epilogue that
             // adds it) instead of at the end of the previous slot's epilogue: the same distance, but the values are no longer carried
             // around the loop -- the compiler rotated them through a second register set with a copy and an `s_waitcnt vmcnt(0)` at
             // every dilation boundary
-            if (RES_TOP && c % CPD == 0)
+            if (RES && c % CPD == 0)
                 prefetch_res(c / CPD);
             if (c % CPD == 0 && c < 2 * CPD) {   // d1 and d2 start fresh; d4, d8, d16 keep adding (HFF)
 #pragma unroll
@@ -938,10 +806,12 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
             const __amdgpu_buffer_rsrc_t rs = last ? rsrc_n : rsrc;
             const int sb = last ? sbase_n : sbase;
             const bool fl = last ? flip_n : flip;
-            // refill of the ring slot that step u (MID: step u - 1) of this chunk has just left: the step R (R - 1) later
+            // refill of the ring slot that step u of this chunk has just left: the step R later
             auto refill = [&](int u) __attribute__((always_inline)) {
-                const int v = u + R - RB;
-                if (v < D && (R < D || MID)) {
+                const int v = u + R;
+                // (`R < D` is implied -- u >= 0, so v < D needs R < D -- and kept for the same reason as `FUSE && BNACT` in epi_params:
+                // without it three kernels were scheduled differently.  Safe to drop with an A/B of the step at hand.)
+                if (v < D && R < D) {
                     fetch_b(rsrc, sbase, c, v / TXN, v % TXN, flip);
                     fetch_a(c, v / TXN, v % TXN, flip);
                 } else {
@@ -972,40 +842,10 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
                         else if (!last)
                             bnl_fetch(nx, g + 2 - G, y, flip, nsc, nsh, nal, nraw);
                     }
-#if defined(GS_DIAG) && defined(CFG_X_MFMA_KEEP)
-                    // ceiling experiment (results are garbage): only every CFG_X_MFMA_KEEP-th k-step's matrix instructions
-                    // are issued; the operands of the others are still loaded and waited for
-                    if (u % CFG_X_MFMA_KEEP != 0) {
-#pragma unroll
-                        for (int p = 0; p < P; ++p) {
-                            const float bv = S2P ? bl[S2P ? g : 0][p][S2P ? tx : 0] : bq[S2P ? 0 : u % R][p];
-                            asm volatile("" ::"v"(bv), "v"(aq[u % RA]));
-                        }
-                    } else
-#endif
-#if defined(GS_DIAG) && defined(CFG_X_S2_EXTRA)
-                    // cost experiment for "level3_C as 20 extra rows of the stride-2 reduce" (profiles/r05_ab_level3c_fusion.txt; results
-                    // unchanged, time only): the four taps (ty, tx) in {1,2} x {1,2} -- the four level-2 pixels under a level-3 pixel --
-                    // each issue a second matrix instruction into a second accumulator set, as a second 32-row block would
-                    if (BNL) {
-                        int ty0x, sidxx;
-                        decode_rg(c, g, ty0x, sidxx);
-                        if (ty0x >= 1 && tx >= 1) {
-#pragma unroll
-                            for (int p = 0; p < P; ++p)
-                                xacc[p] = M::run(aq[u % RA], bt[BNL ? g & 1 : 0][p][S2P ? tx : 0], xacc[p]);
-                        }
-                    }
-#endif
 #pragma unroll
                     for (int p = 0; p < P; ++p) {
                         acc[p] = M::run(aq[u % RA], BNL ? bt[BNL ? g & 1 : 0][p][S2P ? tx : 0]
                                                        : S2P ? bl[S2P ? g : 0][p][S2P ? tx : 0] : bq[S2P ? 0 : u % R][p], acc[p]);
-                        if (MID && p == P / 2 - 1) {
-                            __builtin_amdgcn_sched_barrier(0);
-                            refill(u);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
                         if (ahead) {   // element e = tx*P + p of the next group: (pixel e / 3, tap e % 3)
                             const int e = tx * P + p;
                             if (e < 3 * P)
@@ -1013,18 +853,8 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
                                           e == 0 && x0 == 0 && px == 0);
                         }
                     }
-                    if (EPI_PIPED && c > 0) {
-                        // the previous slot's epilogue, one accumulator register after every EPI_EVERY-th k-step (early in the
-                        // dilation: the residual reloads it issues are for this dilation's own slot)
-                        constexpr int EPI_EVERY = D / (2 * M::NACC) > 0 ? D / (2 * M::NACC) : 1;
-                        static_for<M::NACC>([&](auto r_) {   // (u is a constant once the step loops are unrolled: one call survives)
-                            if (u == decltype(r_)::value * EPI_EVERY + EPI_EVERY - 1)
-                                epi_reg(c - 1, r_, snap, true);
-                        });
-                    }
                     // the slot just consumed is refilled with the step R later: of this chunk, or of the next one
-                    if (!MID)
-                        refill(u);
+                    refill(u);
                     // pin the ring order: left alone, hipcc sinks the refill loads to the end of the
                     // chunk, which shrinks the prefetch distance from D steps to a few
                     __builtin_amdgcn_sched_barrier(0);
@@ -1048,85 +878,9 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
             // last chunk of a dilation: write this branch's concat slot (the accumulator keeps
             // running for the fusion adds)
             const int di = c / CPD;
-            if (EPI_PIPED && di + 1 < NDIL) {   // ... between the k-steps of the next dilation, from a snapshot
-#pragma unroll
-                for (int p = 0; p < P; ++p)
-                    snap[EPI_PIPED ? p : 0] = acc[p];
-                continue;
-            }
-            if (XMERGE) {
-                // per-wave LDS tile [MT rows][P*MT columns]; column i is input x' = x0 - 1 + i
-                // row pitch P*MT + 4 floats: the four k-groups of a store write rows 4 apart, which a pitch of 128
-                // floats put on the same 16 banks (4-way conflict on every tile write)
-                constexpr int TS = P * MT + 4;
-                float *tile = lds + a.lds_tile_off + wid * (MT * TS);
-#pragma unroll
-                for (int r = 0; r < M::NACC; ++r)
-#pragma unroll
-                    for (int p = 0; p < P; ++p)
-                        tile[M::row(r, kq) * TS + (VEC ? xl + p : p * MT + px)] = acc[p][r];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                // out[o][x0 + m] = Z[0*NOUT1+o][m] + Z[1*NOUT1+o][m+1] + Z[2*NOUT1+o][m+2], m < XSTEP
-#pragma unroll
-                for (int t = 0; t < (XSTEP + 63) / 64; ++t) {
-                    const int mcol = t * 64 + lane;
-                    const bool ok = mcol < XSTEP && x0 + mcol < a.W;
-                    const int mc = mcol < XSTEP ? mcol : 0;
-#pragma unroll
-                    for (int o = 0; o < NOUT1; ++o) {
-                        float v = tile[o * TS + mc] + tile[(NOUT1 + o) * TS + mc + 1] + tile[(2 * NOUT1 + o) * TS + mc + 2];
-                        if (BNACT) {
-                            v = v * bnp[o] + bnp[COUT + o];
-                            const float al = bnp[2 * COUT + o];
-                            v = prelu_med3(v, al, prelu_pin(al));
-                        }
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rout, ok ? mcol * 4 : OOB,
-                                                              o * a.out_sc * 4 + sout, SAUX);
-                    }
-                }
-                __builtin_amdgcn_wave_barrier();   // the tile is rewritten by this wave's next task
-                continue;
-            }
             // Branch-free epilogue: addresses are (uniform per accumulator register, in an SGPR) + (one
             // per-lane offset), so the whole slot is straight-line VALU + buffer stores.
-#if CFG_EPI_PRIO
-            __builtin_amdgcn_s_setprio(CFG_EPI_PRIO);
-#endif
-            if constexpr (EPI_PRELOAD) {
-                EpiParams pre[M::NACC];
-                static_for<M::NACC>([&](auto r_) { pre[decltype(r_)::value] = epi_params(di, r_); });
-                static_for<M::NACC>([&](auto r_) { epi_reg(di, r_, acc, false, pre); });
-            } else {
-                static_for<M::NACC>([&](auto r_) { epi_reg(di, r_, acc, false); });
-            }
-#if defined(GS_DIAG) && defined(CFG_X_STAMP_A)
-            if (stamp2)   // (diagnostic: the epilogue's end stamp BEFORE the fused matrix instructions)
-                a.stamp[sbase2 + 2 * c + 1] = __builtin_amdgcn_s_memrealtime();
-#endif
-            if (SPLIT) {
-                __builtin_amdgcn_sched_barrier(0);   // (or the scheduler interleaves the two phases again)
-                epi_fused(di);
-            }
-#if CFG_EPI_PRIO
-            if (prio_mode == 1 && ((((task - t0) / tstride) + (second_of_simd ? 1 : 0)) & 1))
-                __builtin_amdgcn_s_setprio(1);
-            else
-                __builtin_amdgcn_s_setprio(0);
-#endif
-#if defined(GS_DIAG) && defined(CFG_X_S2_EXTRA)
-            if (BNL) {   // keep the second set live; it would be stored as 20 more planes (5 classes x 4 level-2 pixels)
-                float keep = 0.0f;
-#pragma unroll
-                for (int p = 0; p < P; ++p)
-#pragma unroll
-                    for (int r = 0; r < M::NACC; ++r)
-                        keep += xacc[p][r];
-                if (keep == 123.456f)
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, keep), rout, vout, sout, 0);
-            }
-#endif
+            static_for<M::NACC>([&](auto r_) { epi_reg(di, r_); });
             if (FUSE && di + 1 == NDIL) {
                 // the block's output is complete for this strip: its 1x1 reduce leaves for the next block's reduced map
 #pragma unroll
@@ -1147,23 +901,18 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? conv_min_waves(MT, TA
                         buf_store_vec<P, 0>(rout3, live3 ? vo3[0] + so3 : OOB, o3);
                 }
             }
-            if (!RES_TOP && RR == M::NACC && di + 1 < NDIL)
-                prefetch_res(di + 1);
             if ((FLAGS & F_X_STAMP) && lane == 0 && task == t0)
                 a.stamp[wg * 8 + 2 + di] = __builtin_amdgcn_s_memrealtime();
-#if !(defined(GS_DIAG) && defined(CFG_X_STAMP_A))
             if (stamp2)
                 a.stamp[sbase2 + 2 * c + 1] = __builtin_amdgcn_s_memrealtime();
-#endif
         }
     }
 }
 
 // number of floats of a configuration's image in the weight blob (see conv_image)
-constexpr int conv_wfloats(int CINP, int TAPS, int NDIL, int NOUT1, int NOUT, bool bn, bool dual = false, bool xmerge = false,
-                           int fuse_nacc = 0)
+constexpr int conv_wfloats(int CINP, int TAPS, int NDIL, int NOUT1, int NOUT, bool bn, bool dual = false, int fuse_nacc = 0)
 {
-    return conv_image(CINP, TAPS, NDIL, NOUT1, NOUT, bn, dual, xmerge, fuse_nacc).total;
+    return conv_image(CINP, TAPS, NDIL, NOUT1, NOUT, bn, dual, fuse_nacc).total;
 }
 
 // Per (kernel instantiation, device): the dynamic-LDS attribute and the occupancy figure.  One process normally drives one
@@ -1177,9 +926,9 @@ template <int MT, int WAVES, int CINP, int TAPS, int STRIDE, int NDIL, int NOUT1
 gs_status launch_conv_mfma(ConvArgs a, int num_cus, hipStream_t stream)
 {
     auto kern = conv_mfma_kernel<MT, WAVES, CINP, TAPS, STRIDE, NDIL, NOUT1, NOUT, P, G, FLAGS>;
-    constexpr ConvImage im = conv_image(CINP, TAPS, NDIL, NOUT1, NOUT, FLAGS & F_BNACT, FLAGS & F_DUAL, FLAGS & F_XMERGE,
+    constexpr ConvImage im = conv_image(CINP, TAPS, NDIL, NOUT1, NOUT, FLAGS & F_BNACT, FLAGS & F_DUAL,
                                         (FLAGS & F_FUSE1X1) ? Mfma<MT>::NACC : 0);
-    a.strips = cdiv(a.W, (FLAGS & F_XMERGE) ? P * MT - 2 : P * MT);
+    a.strips = cdiv(a.W, P * MT);
     a.total_tasks = a.N * a.H * a.strips;
     a.prio_mode = 1;   // measured on the level-3 branch kernel: per dilation 0.171 ms, per task 0.167, off 0.168, fixed 0.166
 #ifdef GS_DIAG
@@ -1191,8 +940,7 @@ gs_status launch_conv_mfma(ConvArgs a, int num_cus, hipStream_t stream)
     constexpr int EXTRA = (FLAGS & F_BNLOAD) ? 3 * (CINP + Mfma<MT>::KL) : 0;   // the on-load BN / PReLU table follows the image
     a.wfloats = im.total + EXTRA;
     const int lds_floats = im.total + EXTRA - ((FLAGS & F_A_GLOBAL) ? im.w : 0);
-    a.lds_tile_off = (lds_floats + 255) / 256 * 256;
-    const size_t lds_bytes = (size_t)(a.lds_tile_off + ((FLAGS & F_XMERGE) ? WAVES * MT * (P * MT + 4) : 0)) * sizeof(float);   // whole 1-KiB DMA pieces (+ tiles)
+    const size_t lds_bytes = (size_t)((lds_floats + 255) / 256 * 256) * sizeof(float);   // whole 1-KiB DMA pieces
     static std::mutex mu;
     static std::map<int, LaunchInfo> by_device;
     int dev = 0;

@@ -528,9 +528,6 @@ static gs_status launch_dec_tail_p(DecTailArgs a, int num_cus, hipStream_t strea
 
 // The exchanging form (EXCH): rows of 65 .. 1024 half-resolution pixels as ceil(W1 / 128) aligned strips taken by teams of waves,
 // ONE launch, no rest strip.
-#ifndef CFG_DEC_TAIL_EXCH
-#define CFG_DEC_TAIL_EXCH 1
-#endif
 static gs_status launch_dec_tail_exch(DecTailArgs a, int num_cus, hipStream_t stream)
 {
     constexpr int WAVES = 8;
@@ -591,7 +588,7 @@ gs_status launch_dec_tail(DecTailArgs a, int num_cus, hipStream_t stream)
 {
     // rows of 65 .. 1024 pixels: aligned 128-column strips, neighbours exchange across the cuts (one launch).  Narrower rows
     // pack several images into a wave, wider ones have more strips than a workgroup has waves: the overlapping strips below.
-    if (CFG_DEC_TAIL_EXCH && a.W1 > 64 && a.W1 <= 1024)
+    if (a.W1 > 64 && a.W1 <= 1024)
         return launch_dec_tail_exch(a, num_cus, stream);
     constexpr int XS = DecTailGeom<5, 8>::XS;
     const int full_strips = a.W1 / XS, rest = a.W1 - full_strips * XS;

@@ -80,7 +80,8 @@ struct Model {
     float *dblob = nullptr;
     // offsets (floats) into dblob
     float stem_params[537] = {0};   // host copy of level1 weights + folded bn1 + folded b1: they travel as kernel arguments
-    long long w1, bn1, b1, b2, b3, wcls, br, wup3, w3c, cbr0, wcc, bncc, wup2, bnu2, wconv, wconv_xm, wclassifier, wtail;
+    long long w1, bn1, b1, b2, b3, wcls, br, wup3, w3c, cbr0, wcc, bncc, wup2, bnu2, wclassifier, wtail;
+    long long wconv = -1;   // the generic decoder tail's conv_mfma image (class counts other than five)
     long long wcc_mfma = -1;   // twelve classes and more: combine_l2_l3.1 as a conv_mfma image (see forward_impl)
     PackedConv l2_0;
     std::vector<PackedConv> l2, l3;
@@ -221,7 +222,7 @@ static bool pack_block(WeightTable &t, BlobBuilder &bb, const std::string &pre, 
     const int rcinp = (n + kl - 1) / kl * kl;
     const int mt = level == 2 ? 16 : 32, nacc = level == 2 ? 4 : 16;
     pc.fused_next = !next.empty();
-    const ConvImage im = conv_image(rcinp, 9, 5, n1, n, true, dual != nullptr, false, pc.fused_next ? nacc : 0);
+    const ConvImage im = conv_image(rcinp, 9, 5, n1, n, true, dual != nullptr, pc.fused_next ? nacc : 0);
     pc.br = bb.reserve(im.total);
     static const char *dn[5] = {".d1", ".d2", ".d4", ".d8", ".d16"};
     for (int di = 0; di < 5; ++di) {
@@ -309,8 +310,8 @@ static gs_status layout_workspace(Model *m, int n, int H, int W)
     m->t3 = dec3_mfma ? make_act(cls, cls, H2, W2, 0, 0, 0, 0) : make_act(1, 1, 8, 8, 0, 0, 0, 0);
     m->ff = make_act(cls, cls, H1, W1, 0, 0, 0, 0);
     // Lazy b2 (p > 0): output1_0 is stored RAW, once, straight into planes 64..127 of output1_cat -- bb[0] becomes a view of
-    // them -- and the consumers of output1_cat apply b2 to those planes on load (CFG_LAZY_B2 above).
-    const bool lazy_b2 = m->p > 0 && CFG_LAZY_B2;
+    // them -- and the consumers of output1_cat apply b2 to those planes on load (espnet_config.h, "Lazy b2").
+    const bool lazy_b2 = m->p > 0;
     if (lazy_b2)
         m->bb[0] = Act();   // no storage of its own
     Act *all[] = {&m->a0c, &m->inp1, &m->inp2, &m->r2[0], &m->r2[1], &m->bb[0], &m->bb[1], &m->bb[2], &m->a1, &m->r3[0], &m->r3[1],
@@ -438,7 +439,7 @@ static inline unsigned blocks_for(long long items) { return (unsigned)((items + 
 #define GS_DIAG_TRY(call) \
     do {                  \
     } while (0)
-#define GS_DIAG_STAMPED(var, path, ca, ...)
+#define GS_DIAG_STAMPED(var, tag, ca, ...)
 #endif
 
 template <int CLS>
@@ -497,13 +498,12 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
     L.run(K_L2_C1S, px2 * (19 * 9 * 12 * 2), [&] {
         GS_DIAG_TRY(diag_reduce_s2(m, 2, conv_args(m->a0, wb + m->l2_0.c1, m->r2[0], nullptr, n), s, dst_));
         ConvArgs ca = conv_args(m->a0, wb + m->l2_0.c1, m->r2[0], nullptr, n);
-        ca.rev_n = CFG_L2_C1S_REV;
-        return launch_conv_mfma<CFG_L2_C1S, F_S2PAIR | POL_L2_C1S | AGL_S2 | S2FLIP_L2>(ca, m->num_cus, s);
+        return launch_conv_mfma<CFG_L2_C1S, F_S2PAIR | POL_L2_C1S | S2FLIP_L2>(ca, m->num_cus, s);
     });
     // b2 = BR(131) over cat([output1, output1_0, inp2]) (Model.py:359) never runs as a kernel: the last ESP block stores
     // only its b2-normalised form (planes 0..63 of output1_cat), the pool kernel writes planes 128..130 normalised, and
-    // output1_0 is stored RAW into planes 64..127 (lazy b2, CFG_LAZY_B2 above: the consumers normalise on load; the eager
-    // form stored it twice, raw for the ESP blocks and normalised for the cat).  With p == 0 the unfused cat kernel runs.
+    // output1_0 is stored RAW into planes 64..127 (lazy b2, espnet_config.h: the consumers normalise on load).  With p == 0
+    // the unfused cat kernel runs.
     auto with_dual = [&](ConvArgs a, int coff) {
         a.out2 = m->a1.base;
         a.out2_sn = m->a1.sn;
@@ -527,34 +527,24 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
     };
     // small batches: 32-pixel level-2 tasks while there are at most CFG_SMALL2_WAVES of them per CU (see small3 below)
     const bool small2 = CFG_SMALL2_WAVES > 0 && (long long)n * H2 * cdiv(W2, 64) * 2 <= (long long)m->num_cus * CFG_SMALL2_WAVES && W2 % 2 == 0 && !no_vec();
-    const bool fuse_b2 = m->p > 0;
-    const bool lazy_b2 = fuse_b2 && CFG_LAZY_B2;
+    const bool lazy_b2 = m->p > 0;
     m->b2_lazy = lazy_b2;
     int rd2 = 0;   // index of the reduced map the next level-2 branch kernel reads
     L.run(K_L2_DOWN, px2 * (12 * 9 * 64 * 2) + (m->l2_0.fused_next ? px2 * (64 * 12 * 2) : 0), [&] {
         ConvArgs ca = conv_args(m->r2[rd2], wb + m->l2_0.br, m->bb[0], nullptr, n);
-        if (lazy_b2) {   // raw output only: b2 is applied by the consumers (level-3 stride-2 reduce, dec2)
-            if (m->l2_0.fused_next)
-            {
-                if (small2)
-                    return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT) | AGL_L2 | FUSE_L2, CFG_L2_BR_P2S>(with_fused(ca, m->r2[rd2 ^ 1], 12), m->num_cus, s);
-                GS_DIAG_STAMPED(162, "gpurun_out/stamps_l2down.txt", with_fused(ca, m->r2[rd2 ^ 1], 12), F_BNACT | (POL_L2_DOWN & F_ST_NT) | AGL_L2 | FUSE_L2 | F_VEC | SKIP_L2, CFG_L2_BR_P4)
+        // the raw output only, with or without ESP blocks behind it: b2 is applied by the consumers (p > 0: the level-3 stride-2
+        // reduce and dec2 on load; p == 0: cat_b2_kernel)
+        if (m->l2_0.fused_next) {
+            if (small2)
+                return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2, CFG_L2_BR_P2S>(with_fused(ca, m->r2[rd2 ^ 1], 12), m->num_cus, s);
+            GS_DIAG_STAMPED(162, "l2down", with_fused(ca, m->r2[rd2 ^ 1], 12), F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2 | F_VEC, CFG_L2_BR_P4)
 #if CFG_L2_DOWN_SKIP
-                if (ca.W % L2SP == 0 && !no_vec())   // tap-row chunks, tap rows in the zero halo skipped (espnet_config.h)
-                    return launch_conv_mfma<CFG_L2_BR_P4S, F_BNACT | (POL_L2_DOWN & F_ST_NT) | AGL_L2 | FUSE_L2 | F_VEC | F_SKIP_PAD>(with_fused(ca, m->r2[rd2 ^ 1], 12), m->num_cus, s);
+            if (ca.W % L2SP == 0 && !no_vec())   // tap-row chunks, tap rows in the zero halo skipped (espnet_config.h)
+                return launch_conv_mfma<CFG_L2_BR_P4S, F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2 | F_VEC | F_SKIP_PAD>(with_fused(ca, m->r2[rd2 ^ 1], 12), m->num_cus, s);
 #endif
-                return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT) | AGL_L2 | FUSE_L2 | EPIPE_L2_DOWN | SKIP_L2, CFG_L2_BR_P4>(with_fused(ca, m->r2[rd2 ^ 1], 12), m->num_cus, s);
-            }
-            return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT) | AGL_L2 | SKIP_L2, CFG_L2_BR_P4>(ca, m->num_cus, s);
+            return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2, CFG_L2_BR_P4>(with_fused(ca, m->r2[rd2 ^ 1], 12), m->num_cus, s);
         }
-        if (fuse_b2) {
-            ca = with_dual(ca, 64);
-            GS_DIAG_TRY(diag_l2_down(m, ca, with_fused(conv_args(m->r2[rd2], wb + m->l2_0.br, m->bb[0], nullptr, n), m->r2[rd2 ^ 1], 12), s, dst_));
-            if (m->l2_0.fused_next)
-                return launch_vec<F_BNACT | F_DUAL | POL_L2_DOWN | AGL_L2 | FUSE_L2 | SKIP_L2, CFG_L2_BR_P4>(with_fused(ca, m->r2[rd2 ^ 1], 12), m->num_cus, s);
-            return launch_vec<F_BNACT | F_DUAL | POL_L2_DOWN | AGL_L2 | SKIP_L2, CFG_L2_BR_P4>(ca, m->num_cus, s);
-        }
-        return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT) | AGL_L2 | SKIP_L2, CFG_L2_BR_P4>(ca, m->num_cus, s);
+        return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT), CFG_L2_BR_P4>(ca, m->num_cus, s);
     });
     bool have_r2 = m->l2_0.fused_next;   // the reduced map of the next block already exists
     rd2 ^= have_r2 ? 1 : 0;
@@ -571,20 +561,19 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
             });
         L.run(K_L2_ESP, px2 * (12 * 9 * 64 * 2) + (fuse_next ? px2 * (64 * 12 * 2) : 0), [&] {
             ConvArgs ca = conv_args(m->r2[rd2], wb + m->l2[i].br, m->bb[nxt], &m->bb[cur2], n);
-            GS_DIAG_TRY(diag_l2_esp(m, ca, with_dual(ca, 0), last, s, dst_));
             if (last) {
                 if (small2)
-                    return launch_vec<F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST | AGL_L2, CFG_L2_BR_P2S>(with_dual(ca, 0), m->num_cus, s);
-                GS_DIAG_STAMPED(163, "gpurun_out/stamps_l2last.txt", with_dual(ca, 0), F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST | AGL_L2 | F_VEC | SKIP_L2, CFG_L2_BR_P4)
-                return launch_vec<F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST | AGL_L2 | EPIPE_L2_ESP | SKIP_L2, CFG_L2_BR_P4>(with_dual(ca, 0), m->num_cus, s);
+                    return launch_vec<F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST, CFG_L2_BR_P2S>(with_dual(ca, 0), m->num_cus, s);
+                GS_DIAG_STAMPED(163, "l2last", with_dual(ca, 0), F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST | F_VEC, CFG_L2_BR_P4)
+                return launch_vec<F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST, CFG_L2_BR_P4>(with_dual(ca, 0), m->num_cus, s);
             }
             if (fuse_next) {
                 if (small2)
-                    return launch_vec<F_BNACT | F_RES | POL_L2_ESP | AGL_L2 | FUSE_L2, CFG_L2_BR_P2S>(with_fused(ca, m->r2[rd2 ^ 1], 12), m->num_cus, s);
-                GS_DIAG_STAMPED(161, "gpurun_out/stamps_l2esp.txt", with_fused(ca, m->r2[rd2 ^ 1], 12), F_BNACT | F_RES | POL_L2_ESP | AGL_L2 | FUSE_L2 | F_VEC | SKIP_L2, CFG_L2_BR_P4)
-                return launch_vec<F_BNACT | F_RES | POL_L2_ESP | AGL_L2 | FUSE_L2 | EPIPE_L2_ESP | SKIP_L2, CFG_L2_BR_P4>(with_fused(ca, m->r2[rd2 ^ 1], 12), m->num_cus, s);
+                    return launch_vec<F_BNACT | F_RES | POL_L2_ESP | FUSE_L2, CFG_L2_BR_P2S>(with_fused(ca, m->r2[rd2 ^ 1], 12), m->num_cus, s);
+                GS_DIAG_STAMPED(161, "l2esp", with_fused(ca, m->r2[rd2 ^ 1], 12), F_BNACT | F_RES | POL_L2_ESP | FUSE_L2 | F_VEC, CFG_L2_BR_P4)
+                return launch_vec<F_BNACT | F_RES | POL_L2_ESP | FUSE_L2, CFG_L2_BR_P4>(with_fused(ca, m->r2[rd2 ^ 1], 12), m->num_cus, s);
             }
-            return launch_vec<F_BNACT | F_RES | POL_L2_ESP | AGL_L2 | SKIP_L2, CFG_L2_BR_P4>(ca, m->num_cus, s);
+            return launch_vec<F_BNACT | F_RES | POL_L2_ESP, CFG_L2_BR_P4>(ca, m->num_cus, s);
         });
         have_r2 = fuse_next;
         rd2 ^= have_r2 ? 1 : 0;
@@ -592,7 +581,7 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
         if (!last)
             set_stage("level2." + std::to_string(i), m->bb[cur2], 64);
     }
-    if (!fuse_b2) {
+    if (!lazy_b2) {
         L.run(K_CAT_B2, 0, [&] {
             hipLaunchKernelGGL(cat_b2_kernel, dim3(blocks_for((long long)n * 131 * H2 * W2)), dim3(256), 0, s, view(m->bb[cur2]),
                                view(m->bb[0]), view(m->inp2), wb + m->b2, view(m->a1), n);
@@ -617,30 +606,27 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
             // tasks (batch 1: 64 -> 256 tasks, 0.180 -> see profiles/r04_latency.json)
             if ((long long)n * H3 * cdiv(W3, 128) * 4 <= (long long)m->num_cus * 8)
                 return launch_conv_mfma<CFG_L3_C1S_BNL_P1, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD>(ca, m->num_cus, s);
-            GS_DIAG_STAMPED(165, "gpurun_out/stamps_l3c1s.txt", ca, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD, CFG_L3_C1S_BNL)
+            GS_DIAG_STAMPED(165, "l3c1s", ca, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD, CFG_L3_C1S_BNL)
             return launch_conv_mfma<CFG_L3_C1S_BNL, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD>(ca, m->num_cus, s);
         }
-        return launch_conv_mfma<CFG_L3_C1S, F_S2PAIR | POL_L3_C1S | AGL_S2 | S2FLIP_L3>(conv_args(m->a1, wb + m->l3_0.c1, m->r3[0], nullptr, n), m->num_cus, s);
+        return launch_conv_mfma<CFG_L3_C1S, F_S2PAIR | POL_L3_C1S | S2FLIP_L3>(conv_args(m->a1, wb + m->l3_0.c1, m->r3[0], nullptr, n), m->num_cus, s);
     });
     L.run(K_L3_DOWN, px3 * (25 * 9 * 128 * 2) + (m->l3_0.fused_next ? px3 * (128 * 25 * 2) : 0), [&] {
         ConvArgs ca = conv_args(m->r3[rd3], wb + m->l3_0.br, m->cc[0], nullptr, n);
         if (m->l3_0.fused_next) {   // no residual here: the four-pixel vector mapping still fits with the second accumulator set
             if (small3)
-                return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | POL_L3_DOWN | AGL_L3 | FUSE_L3 | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
-#if CFG_L3_W16 & 4
-            return launch_conv_mfma<CFG_L3_BR_W16, F_BNACT | POL_L3_DOWN | AGL_L3 | FUSE_L3 | SKIP_L3>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
-#endif
+                return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | POL_L3_DOWN | FUSE_L3 | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
 #if CFG_L3_DOWN_P2
             if (ca.W % 2 == 0 && !no_vec()) {
-                GS_DIAG_STAMPED(164, "gpurun_out/stamps_l3down.txt", with_fused(ca, m->r3[rd3 ^ 1], 25), F_BNACT | POL_L3_DOWN | AGL_L3 | FUSE_L3 | F_VEC | SKIP_L3, CFG_L3_BR_P2R)
-                return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | POL_L3_DOWN | AGL_L3 | FUSE_L3 | F_VEC | SKIP_L3>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
+                GS_DIAG_STAMPED(164, "l3down", with_fused(ca, m->r3[rd3 ^ 1], 25), F_BNACT | POL_L3_DOWN | FUSE_L3 | F_VEC | SKIP_L3, CFG_L3_BR_P2R)
+                return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | POL_L3_DOWN | FUSE_L3 | F_VEC | SKIP_L3>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
             }
 #endif
             if (ca.W % 4 == 0 && !no_vec())
-                return launch_conv_mfma<CFG_L3_BR, F_BNACT | POL_L3_DOWN | AGL_L3 | FUSE_L3 | F_VEC>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
-            return launch_conv_mfma<CFG_L3_BR_P2F, F_BNACT | POL_L3_DOWN | AGL_L3 | FUSE_L3>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
+                return launch_conv_mfma<CFG_L3_BR, F_BNACT | POL_L3_DOWN | FUSE_L3 | F_VEC>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
+            return launch_conv_mfma<CFG_L3_BR_P2F, F_BNACT | POL_L3_DOWN | FUSE_L3>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
         }
-        return launch_vec<F_BNACT | POL_L3_DOWN | AGL_L3, CFG_L3_BR>(ca, m->num_cus, s);
+        return launch_vec<F_BNACT | POL_L3_DOWN, CFG_L3_BR>(ca, m->num_cus, s);
     });
     bool have_r3 = m->l3_0.fused_next;
     set_stage("level3_reduce", m->r3[rd3], 25);      // (debug: valid until the second ESP block overwrites the map)
@@ -660,42 +646,31 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
             GS_DIAG_TRY(diag_l3_esp(m, ca, i, s, dst_));
             if (fuse_next) {
                 if (small3)   // (one pixel per lane: a whole slot's residual fits in registers, requested a dilation ahead)
-                    return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | F_RES | POL_L3_ESP | AGL_L3 | FUSE_L3 | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
-#if CFG_L3_W16 & 1
-                return launch_conv_mfma<CFG_L3_BR_W16, F_BNACT | F_RES | POL_L3_ESP | AGL_L3 | FUSE_L3 | SKIP_L3>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
-#endif
-#if CFG_L3_FUSE_P4
-                // four pixels per lane with the residual through a half-slot register ring (round 2's first fused form)
-                if (ca.W % 4 == 0 && !no_vec())
-                    return launch_conv_mfma<CFG_L3_BR, F_BNACT | F_RES | F_RES_RING | F_VEC | POL_L3_ESP | AGL_L3 | FUSE_L3>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
-#endif
-                // Two consecutive pixels per lane, a 39-step operand ring, the residual through the half-slot register
-                // ring.  A task is then half a row, so the 256 waves of an XCD have TWO images in flight instead of four
+                    return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | F_RES | POL_L3_ESP | FUSE_L3 | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
+                // Two consecutive pixels per lane, a 13-step operand ring (CFG_L3_RING), a whole slot's residual in
+                // registers.  A task is then half a row, so the 256 waves of an XCD have TWO images in flight instead of four
                 // and the reduced maps the taps re-read stay in that XCD's 4 MiB L2: beyond-L2 fetch of a launch
                 // 542 -> 296 MB, 0.1898 -> 0.1834 ms (profiles/README.md).
                 if (ca.W % 2 == 0 && !no_vec()) {
                     if (i == 1) {
-                        GS_DIAG_STAMPED(160, "gpurun_out/stamps_l3esp.txt", with_fused(ca, m->r3[rd3 ^ 1], 25), F_BNACT | F_RES | F_RES_RING | F_VEC | POL_L3_ESP | AGL_L3 | FUSE_L3 | SKIP_L3, CFG_L3_BR_P2R)
+                        GS_DIAG_STAMPED(160, "l3esp", with_fused(ca, m->r3[rd3 ^ 1], 25), F_BNACT | F_RES | F_VEC | POL_L3_ESP | FUSE_L3 | SKIP_L3, CFG_L3_BR_P2R)
                     }
-                    return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | F_RES | F_RES_RING | F_VEC | POL_L3_ESP | AGL_L3 | FUSE_L3 | SKIP_L3>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
+                    return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | F_RES | F_VEC | POL_L3_ESP | FUSE_L3 | SKIP_L3>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
                 }
-                return launch_conv_mfma<CFG_L3_BR_P2F, F_BNACT | F_RES | AGL_L3 | FUSE_L3>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
+                return launch_conv_mfma<CFG_L3_BR_P2F, F_BNACT | F_RES | FUSE_L3>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
             }
             if (small3)
-                return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | F_RES | POL_L3_ESP | AGL_L3 | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(ca, m->num_cus, s);
-#if CFG_L3_W16 & 2
-            return launch_conv_mfma<CFG_L3_BR_W16, F_BNACT | F_RES | POL_L3_ESP | AGL_L3 | SKIP_L3>(ca, m->num_cus, s);
-#endif
+                return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | F_RES | POL_L3_ESP | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(ca, m->num_cus, s);
 #if CFG_L3_LAST_P2
             // the last (unfused) block in the half-row task shape of the fused ones, tap rows in the halo skipped
             if (ca.W % 2 == 0 && !no_vec())
-                return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | F_RES | F_RES_RING | F_VEC | POL_L3_ESP | AGL_L3 | SKIP_L3>(ca, m->num_cus, s);
+                return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | F_RES | F_VEC | POL_L3_ESP | SKIP_L3>(ca, m->num_cus, s);
 #endif
             // four consecutive pixels per lane and 16-byte accesses when the width allows it (0.170 ms per
             // launch at batch 32), else the two-run mapping with its deeper ring (0.175 ms)
             if (ca.W % 4 == 0 && !no_vec())
-                return launch_conv_mfma<CFG_L3_BR, F_BNACT | F_RES | F_VEC | POL_L3_ESP | AGL_L3>(ca, m->num_cus, s);
-            return launch_conv_mfma<CFG_L3_BR_P2, F_BNACT | F_RES | AGL_L3>(ca, m->num_cus, s);
+                return launch_conv_mfma<CFG_L3_BR, F_BNACT | F_RES | F_VEC | POL_L3_ESP>(ca, m->num_cus, s);
+            return launch_conv_mfma<CFG_L3_BR_P2, F_BNACT | F_RES>(ca, m->num_cus, s);
         });
         have_r3 = fuse_next;
         rd3 ^= have_r3 ? 1 : 0;
@@ -784,7 +759,6 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
     set_stage("up_l2", m->ee, ncls);
     // ---- conv CBR(19+c,c,3) + classifier deconv + argmax + counts (Model.py:375-377, VisualizeResults_iou.py:128,151-155)
     if constexpr (CLS == 5) {
-        GS_DIAG_TRY((diag_two_kernel_tail<CLS>(m, L, n, H1, W1, logits, mask, hist, s, set_stage, dst_)));
         L.run(K_DEC_TAIL, px1 * ((19 + CLS) * 9 * CLS * 2) + px1 * (CLS * CLS * 4 * 2), [&] {
             DecTailArgs a{};
             a.in = m->a0c.base;
@@ -1037,7 +1011,7 @@ gs_status gs_espnet_create(const float *blob, const gs_layer_desc *table, int n_
     auto next2 = [&](int i) { return (CFG_FUSE_L2 && i < p) ? e + "level2." + std::to_string(i) : std::string(); };
     auto next3 = [&](int i) { return ((CFG_FUSE_L3 == 2 || (CFG_FUSE_L3 == 1 && i == 0)) && i < q) ? e + "level3." + std::to_string(i) : std::string(); };
     // (lazy b2: the down-sampler has no second store, so its image carries no second BN section)
-    if (!pack_block(t, bb, e + "level2_0", true, 2, m.l2_0, (p > 0 && !CFG_LAZY_B2) ? b2f.data() : nullptr, 64, 131, next2(0))) return GS_ERR_INVALID;
+    if (!pack_block(t, bb, e + "level2_0", true, 2, m.l2_0, nullptr, 0, 0, next2(0))) return GS_ERR_INVALID;
     m.l2.resize(p);
     for (int i = 0; i < p; ++i)
         if (!pack_block(t, bb, e + "level2." + std::to_string(i), false, 2, m.l2[i], i == p - 1 ? b2f.data() : nullptr, 0, 131, next2(i + 1)))
@@ -1153,30 +1127,7 @@ gs_status gs_espnet_create(const float *blob, const gs_layer_desc *table, int n_
         auto cat_ch = [&](int pl) { return pl < cp ? (pl < c ? pl : -1) : (pl - cp < 19 ? c + pl - cp : -1); };
         if (!fold_bn(t, "conv.bn", "conv.act", c, tmp.data())) return GS_ERR_INVALID;
         const std::vector<float> bn_conv = pad_bn(tmp.data(), c, 3, cp, ident);
-        if (cp == 5) {
-            // LDS image [tap][24 planes][c]: plane = cat channel
-            const int npl = 19 + c;
-            m.wconv = bb.reserve(conv_wfloats(npl, 9, 1, c, c, true));
-            float *dst = bb.data.data() + m.wconv;
-            for (int tap = 0; tap < 9; ++tap)
-                for (int pl = 0; pl < npl; ++pl) {
-                    const int wch = pl;
-                    for (int co = 0; co < c; ++co)
-                        dst[((size_t)tap * npl + pl) * c + co] = w[((size_t)co * (19 + c) + wch) * 9 + tap];
-                }
-            std::memcpy(dst + (size_t)9 * npl * c, bn_conv.data(), sizeof(float) * 3 * c);
-            // row-merged form (F_XMERGE): LDS image [ty][plane][row = tx*c + o]
-            m.wconv_xm = bb.reserve(conv_wfloats(npl, 3, 1, c, c, true, false, true));
-            float *dx = bb.data.data() + m.wconv_xm;
-            for (int ty = 0; ty < 3; ++ty)
-                for (int pl = 0; pl < npl; ++pl) {
-                    const int wch = pl;
-                    for (int tx = 0; tx < 3; ++tx)
-                        for (int co = 0; co < c; ++co)
-                            dx[((size_t)ty * npl + pl) * (3 * c) + tx * c + co] = w[((size_t)co * (19 + c) + wch) * 9 + ty * 3 + tx];
-                }
-            std::memcpy(dx + (size_t)3 * npl * 3 * c, bn_conv.data(), sizeof(float) * 3 * c);
-        } else {
+        if (cp != 5) {   // (five classes: dec_tail reads m.wtail, packed below)
             // the generic tail's conv_mfma image [tap][CINP planes][cp rows] + BN: CINP = 19 + cp rounded up to the k-step
             const int cinp = (19 + cp + 3) / 4 * 4;
             m.wconv = bb.reserve(conv_wfloats(cinp, 9, 1, cp, cp, true));
@@ -1189,7 +1140,6 @@ gs_status gs_espnet_create(const float *blob, const gs_layer_desc *table, int n_
                         dst[((size_t)tap * cinp + pl) * cp + co] = w[((size_t)co * (19 + c) + wch) * 9 + tap];
                 }
             std::memcpy(dst + (size_t)9 * cinp * cp, bn_conv.data(), sizeof(float) * 3 * cp);
-            m.wconv_xm = m.wconv;
         }
         if (!(w = t.get("classifier.weight", {c, c, 2, 2}))) return GS_ERR_INVALID;
         {
@@ -1389,21 +1339,21 @@ gs_status gs_espnet_block_forward(gs_espnet *h, int kind, int level, int index, 
         const PackedConv &pc = kind == 1 ? (level == 2 ? m.l2_0 : m.l3_0) : (level == 2 ? m.l2[index] : m.l3[index]);
         gs_status r;
         if (level == 2) {
-            r = kind == 1 ? launch_conv_mfma<CFG_L2_C1S, F_S2PAIR | POL_L2_C1S | AGL_S2 | S2FLIP_L2>(conv_args(src, wb + pc.c1, red, nullptr, 1), m.num_cus, s)
+            r = kind == 1 ? launch_conv_mfma<CFG_L2_C1S, F_S2PAIR | POL_L2_C1S | S2FLIP_L2>(conv_args(src, wb + pc.c1, red, nullptr, 1), m.num_cus, s)
                           : launch_conv_mfma<CFG_L2_C1, POL_L2_C1>(conv_args(src, wb + pc.c1, red, nullptr, 1), m.num_cus, s);
             if (r != GS_OK) return r;
-            r = kind == 1 ? launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT) | AGL_L2 | SKIP_L2, CFG_L2_BR_P4>(conv_args(red, wb + pc.br, dst, nullptr, 1), m.num_cus, s)
-                          : launch_vec<F_BNACT | F_RES | POL_L2_ESP | AGL_L2 | SKIP_L2, CFG_L2_BR_P4>(conv_args(red, wb + pc.br, dst, &src, 1), m.num_cus, s);
+            r = kind == 1 ? launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT), CFG_L2_BR_P4>(conv_args(red, wb + pc.br, dst, nullptr, 1), m.num_cus, s)
+                          : launch_vec<F_BNACT | F_RES | POL_L2_ESP, CFG_L2_BR_P4>(conv_args(red, wb + pc.br, dst, &src, 1), m.num_cus, s);
         } else {
-            r = kind == 1 ? launch_conv_mfma<CFG_L3_C1S, F_S2PAIR | POL_L3_C1S | AGL_S2 | S2FLIP_L3>(conv_args(src, wb + pc.c1, red, nullptr, 1), m.num_cus, s)
+            r = kind == 1 ? launch_conv_mfma<CFG_L3_C1S, F_S2PAIR | POL_L3_C1S | S2FLIP_L3>(conv_args(src, wb + pc.c1, red, nullptr, 1), m.num_cus, s)
                           : launch_conv_mfma<CFG_L3_C1, POL_L3_C1>(conv_args(src, wb + pc.c1, red, nullptr, 1), m.num_cus, s);
             if (r != GS_OK) return r;
             if (kind == 1)
-                r = launch_vec<F_BNACT | POL_L3_DOWN | AGL_L3, CFG_L3_BR>(conv_args(red, wb + pc.br, dst, nullptr, 1), m.num_cus, s);
+                r = launch_vec<F_BNACT | POL_L3_DOWN, CFG_L3_BR>(conv_args(red, wb + pc.br, dst, nullptr, 1), m.num_cus, s);
             else if (dst.W % 4 == 0)
-                r = launch_conv_mfma<CFG_L3_BR, F_BNACT | F_RES | F_VEC | POL_L3_ESP | AGL_L3>(conv_args(red, wb + pc.br, dst, &src, 1), m.num_cus, s);
+                r = launch_conv_mfma<CFG_L3_BR, F_BNACT | F_RES | F_VEC | POL_L3_ESP>(conv_args(red, wb + pc.br, dst, &src, 1), m.num_cus, s);
             else
-                r = launch_conv_mfma<CFG_L3_BR_P2, F_BNACT | F_RES | AGL_L3>(conv_args(red, wb + pc.br, dst, &src, 1), m.num_cus, s);
+                r = launch_conv_mfma<CFG_L3_BR_P2, F_BNACT | F_RES>(conv_args(red, wb + pc.br, dst, &src, 1), m.num_cus, s);
         }
         if (r != GS_OK) return r;
         hipLaunchKernelGGL(unpad_kernel, dim3(blocks_for((long long)nout)), dim3(256), 0, s, view(dst), 0, cout, tmp);

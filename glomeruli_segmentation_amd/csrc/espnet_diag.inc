@@ -1,13 +1,10 @@
 // -DGS_DIAG builds only (included by espnet.hip under #ifdef GS_DIAG): the timing / stamp variants of the forward, selected by
 // the GS_VARIANT environment variable at gs_espnet_create.  Results are wrong by construction unless noted.  Every function
 // returns true when it took the launch over (status in `st`).  0 = the shipped configuration: nothing here runs.
-//    30  the two-kernel decoder tail that dec_tail replaced (row-merged conv + dec4), 171-173 its ablations (results correct for 30)
 //    41  stride-2 reduces with three dword loads per pixel instead of one 12-byte load (results correct)
 //   101  level-3 ESP: no epilogue   102 no epilogue, no operand loads   103 ... and no LDS reads   104 no operand loads
-//   105  level-3 ESP: per-wave stamps -> gpurun_out/stamps.txt (tools/stamps.py; results correct)   109 stores but no residual
-//   160-165  per-chunk stamps of every task of a SHIPPED kernel form -> gpurun_out/stamps_*.txt (tools/stamps3.py; results correct)
-//   150  level-2 branch kernels at eight pixels per lane
-//   151  the b2-normalised second store of the level-2 down-sampler dropped: the ceiling of lazy b2 (eager-b2 builds only)
+//   105  level-3 ESP: per-wave stamps -> $GS_STAMP_DIR/stamps.txt (tools/stamps.py; results correct)   109 stores but no residual
+//   160-165  per-chunk stamps of every task of a SHIPPED kernel form -> $GS_STAMP_DIR/stamps_<tag>.txt (tools/stamps3.py; results correct)
 
 static bool diag_reduce_s2(Model *m, int level, const ConvArgs &ca, hipStream_t s, gs_status &st)
 {
@@ -17,27 +14,22 @@ static bool diag_reduce_s2(Model *m, int level, const ConvArgs &ca, hipStream_t 
     return true;
 }
 
-// `ca` carries the second (b2) output; `fused` is the same launch without it and with the next block's reduced map
-static bool diag_l2_down(Model *m, const ConvArgs &ca, const ConvArgs &fused, hipStream_t s, gs_status &st)
+// Every stamp file of a diagnostic variant (105, 160-165) lands in the directory the GS_STAMP_DIR environment variable names
+// (unset: the working directory); the stamp tools under tools/ set it to their output directory.
+static std::string stamp_path(const std::string &name)
 {
-    if (m->variant == 150) {
-        st = launch_vec<F_BNACT | F_DUAL, CFG_L2_BR>(ca, m->num_cus, s);
-        return true;
-    }
-    if (m->variant == 151 && m->l2_0.fused_next) {
-        st = launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT) | AGL_L2 | FUSE_L2, CFG_L2_BR_P4>(fused, m->num_cus, s);
-        return true;
-    }
-    return false;
+    const char *dir = std::getenv("GS_STAMP_DIR");
+    return std::string(dir ? dir : ".") + "/" + name;
 }
 
 // Per-chunk stamps of EVERY task of every wave of one launch of a SHIPPED kernel form (F_X_STAMP2; results correct) ->
-// `path` (one line per wave: global wave id, then STAMP2_SLOTS stamps; tools/stamps3.py).  The file is written on the third
-// stamped call of the process (after warm-up) and the stream is synchronised there.
+// stamps_<tag>.txt (stamp_path above), one line per
+// wave: global wave id, then STAMP2_SLOTS stamps (tools/stamps3.py).  The file is written on the third stamped call of the
+// process (after warm-up) and the stream is synchronised there.
 //   160 the fused level-3 ESP launch (block 1)   161 the fused level-2 ESP launch   162 the level-2 down-sampler
 //   163 the last level-2 ESP launch   164 the level-3 down-sampler   165 the level-3 stride-2 reduce
 template <int FLAGS, int... C>
-static gs_status launch_stamped(ConvArgs ca, int num_cus, hipStream_t s, const char *path)
+static gs_status launch_stamped(ConvArgs ca, int num_cus, hipStream_t s, const char *tag)
 {
     static unsigned long long *stamp = nullptr;
     static int calls = 0;
@@ -51,7 +43,7 @@ static gs_status launch_stamped(ConvArgs ca, int num_cus, hipStream_t s, const c
         std::vector<unsigned long long> h(nst);
         GS_HIP(hipStreamSynchronize(s));
         GS_HIP(hipMemcpy(h.data(), stamp, nst * 8, hipMemcpyDeviceToHost));
-        if (FILE *f = std::fopen(path, "w")) {
+        if (FILE *f = std::fopen(stamp_path("stamps_" + std::string(tag) + ".txt").c_str(), "w")) {
             for (size_t w = 0; w < nw; ++w) {
                 if (!h[w * STAMP2_SLOTS]) continue;
                 std::fprintf(f, "%zu", w);
@@ -63,13 +55,13 @@ static gs_status launch_stamped(ConvArgs ca, int num_cus, hipStream_t s, const c
     }
     return st;
 }
-#define GS_DIAG_STAMPED(var, path, ca, ...)     \
+#define GS_DIAG_STAMPED(var, tag, ca, ...)     \
     if (m->variant == (var))                   \
-        return launch_stamped<__VA_ARGS__>(ca, m->num_cus, s, path);
+        return launch_stamped<__VA_ARGS__>(ca, m->num_cus, s, tag);
 
 // Level-3 branch kernel:
 //   101 no epilogue   102 no epilogue, no operand loads   103 ... and no LDS reads   104 no operand loads
-//   105 per-wave stamps -> gpurun_out/stamps.txt (tools/stamps.py; results correct)   109 stores but no residual
+//   105 per-wave stamps -> $GS_STAMP_DIR/stamps.txt (tools/stamps.py; results correct)   109 stores but no residual
 static gs_status diag_l3_variants(Model *m, ConvArgs ca, int i, hipStream_t s)
 {
     switch (m->variant) {
@@ -88,7 +80,7 @@ static gs_status diag_l3_variants(Model *m, ConvArgs ca, int i, hipStream_t s)
         if (i == m->q - 1) {
             std::vector<unsigned long long> h(2048 * 8);
             GS_HIP(hipMemcpy(h.data(), stamp, h.size() * 8, hipMemcpyDeviceToHost));
-            if (FILE *f = std::fopen("gpurun_out/stamps.txt", "w")) {
+            if (FILE *f = std::fopen(stamp_path("stamps.txt").c_str(), "w")) {
                 for (int w = 0; w < 2048; ++w) {
                     for (int k = 0; k < 7; ++k) std::fprintf(f, "%llu ", h[w * 8 + k]);
                     std::fprintf(f, "\n");
@@ -102,55 +94,10 @@ static gs_status diag_l3_variants(Model *m, ConvArgs ca, int i, hipStream_t s)
     }
 }
 
-static bool diag_l2_esp(Model *m, const ConvArgs &ca, const ConvArgs &ca_dual, bool last, hipStream_t s, gs_status &st)
-{
-    if (m->variant == 150) {
-        st = last ? launch_vec<F_BNACT | F_RES | F_NOSTORE | F_DUAL, CFG_L2_BR>(ca_dual, m->num_cus, s)
-                  : launch_vec<F_BNACT | F_RES, CFG_L2_BR>(ca, m->num_cus, s);
-        return true;
-    }
-    return false;
-}
-
 static bool diag_l3_esp(Model *m, const ConvArgs &ca, int i, hipStream_t s, gs_status &st)
 {
-    if (m->variant == 0 || m->variant == 30 || (m->variant >= 160 && m->variant <= 169))
+    if (m->variant == 0 || (m->variant >= 160 && m->variant <= 169))
         return false;
     st = diag_l3_variants(m, ca, i, s);
-    return true;
-}
-
-// the decoder tail as round 1 ran it: conv CBR on the row-merged MFMA form, then dec4 (deconvolution + argmax + counts)
-template <int CLS, typename SetStage>
-static bool diag_two_kernel_tail(Model *m, Launcher &L, int n, int H1, int W1, float *logits, uint8_t *mask, unsigned long long *hist,
-                                 hipStream_t s, SetStage &&set_stage, gs_status &st)
-{
-    if (!(m->variant == 30 || (m->variant >= 171 && m->variant <= 173)))
-        return false;
-    const float *wb = m->dblob;
-    const double px1 = (double)H1 * W1;
-    L.run(K_DEC_CONV, px1 * ((19 + CLS) * 9 * CLS * 2), [&] {
-        if (m->variant == 171)   // timing-only ablations
-            return launch_conv_mfma<CFG_DEC_CONV_XM, F_BNACT | F_XMERGE | F_X_NOEPI>(conv_args(m->a0c, wb + m->wconv_xm, m->ff, nullptr, n), m->num_cus, s);
-        if (m->variant == 172)
-            return launch_conv_mfma<CFG_DEC_CONV_XM, F_BNACT | F_XMERGE | F_X_NOLOAD>(conv_args(m->a0c, wb + m->wconv_xm, m->ff, nullptr, n), m->num_cus, s);
-        if (m->variant == 173)
-            return launch_conv_mfma<CFG_DEC_CONV_XM, F_BNACT | F_XMERGE | F_X_NOLOAD | F_X_NOEPI>(conv_args(m->a0c, wb + m->wconv_xm, m->ff, nullptr, n), m->num_cus, s);
-        return launch_conv_mfma<CFG_DEC_CONV_XM, F_BNACT | F_XMERGE | POL_DEC_CONV>(conv_args(m->a0c, wb + m->wconv_xm, m->ff, nullptr, n), m->num_cus, s);
-    });
-    set_stage("conv", m->ff, CLS);
-    L.run(K_DEC4, px1 * (CLS * CLS * 4 * 2), [&] {
-        Dec4Args a{};
-        a.f = view(m->ff);
-        a.wcl = wb + m->wclassifier;
-        a.logits = logits;
-        a.mask = mask;
-        a.hist = hist;
-        a.N = n;
-        a.classes = CLS;
-        hipLaunchKernelGGL((dec4_kernel<CLS, false>), dim3(blocks_for(((long long)H1 * W1 + dec4_px<CLS>() - 1) / dec4_px<CLS>()), n), dim3(256), 0, s, a);
-        return GS_OK;
-    });
-    st = L.st;
     return true;
 }

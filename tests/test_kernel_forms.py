@@ -25,9 +25,13 @@ RANDOM_MEAN_STD = ((120.0, 130.0, 110.0), (60.0, 55.0, 70.0))
 
 # ---------------------------------------------------------------------------------------------- the dispatch, restated
 # the shipped defaults of espnet_config.h the dispatch reads (test_dispatch_tripwire pins each one)
-CONFIG = {"CFG_SMALL2_WAVES": 4, "CFG_SMALL3_WAVES": 8, "L2SP": 4, "CFG_L3_DOWN_P2": 1, "CFG_L3_LAST_P2": 1,
-          "CFG_L3_W16": 0, "CFG_L2_DOWN_SKIP": 1, "CFG_LAZY_B2": 1, "CFG_FUSE_L2": 1, "CFG_FUSE_L3": 2,
-          "CFG_L3_FUSE_P4": 0}
+CONFIG = {"CFG_SMALL2_WAVES": 4, "CFG_SMALL3_WAVES": 8, "CFG_L3_DOWN_P2": 1, "CFG_L3_LAST_P2": 1,
+          "CFG_L2_DOWN_SKIP": 1, "CFG_FUSE_L2": 1, "CFG_FUSE_L3": 2}
+L2SP = 4    # `constexpr int L2SP` there: pixels per lane of the level-2 branch kernels
+# switches whose A/B was lost: removed from the sources, none of these names may come back under csrc/
+DELETED = ("F_EPI_PIPE", "CFG_EPI_SPLIT", "CFG_EPI_PRIO", "CFG_EPI_PRELOAD", "CFG_REFILL_MID", "CFG_L3_W16",
+           "CFG_L3_FUSE_P4", "CFG_AGL_", "CFG_SKIP_PAD_L2", "CFG_RES_RING_DIV", "CFG_RES_TOP", "CFG_L2_MINW", "CFG_LAZY_B2",
+           "CFG_L2_C1S_REV", "rev_n", "F_XMERGE", "wconv_xm")
 # pixels per lane of the configurations whose vector mapping the width decides (the 9th template argument)
 PIXELS_PER_LANE = {"CFG_L2_BR_P4": "L2SP", "CFG_L2_BR_P4S": "L2SP", "CFG_L2_BR_P2S": "2", "CFG_L3_BR": "4",
                    "CFG_L3_BR_P2R": "2"}
@@ -38,59 +42,59 @@ def cdiv(a, b):
 
 
 def padded_classes(classes):
-    return 5 if classes == 5 else cdiv(classes, 4) * 4                                  # Model::cp, espnet.hip:998
+    return 5 if classes == 5 else cdiv(classes, 4) * 4                                  # Model::cp, espnet.hip:972
 
 
 def forms(n, H, W, p, q, classes, num_cus):
-    """launch class -> the form forward_impl runs for it (espnet.hip:529-831).  "+F_VEC" is the vector pixel mapping;
+    """launch class -> the form forward_impl runs for it (espnet.hip:529-805).  "+F_VEC" is the vector pixel mapping;
     launch_vec (espnet.hip:48-54) takes it when the output width is a multiple of the form's pixels per lane."""
-    small2_waves, small3_waves, l2sp = CONFIG["CFG_SMALL2_WAVES"], CONFIG["CFG_SMALL3_WAVES"], CONFIG["L2SP"]
+    small2_waves, small3_waves, l2sp = CONFIG["CFG_SMALL2_WAVES"], CONFIG["CFG_SMALL3_WAVES"], L2SP
     H2, W2, H3, W3, W1 = H // 4, W // 4, H // 8, W // 8, W // 2
 
     def vec(ok):
         return "+F_VEC" if ok else ""
     f = {}
     small2 = n * H2 * cdiv(W2, 64) * 2 <= num_cus * small2_waves and W2 % 2 == 0        # :529
-    if p > 0:   # lazy b2 (:530-531); the down-sampler and every ESP block but the last compute the next 1x1 reduce
+    if p > 0:   # lazy b2 (:530); the down-sampler and every ESP block but the last compute the next 1x1 reduce
         if small2:
-            f["l2_down"] = "CFG_L2_BR_P2S+F_VEC"                                        # :539-540
+            f["l2_down"] = "CFG_L2_BR_P2S+F_VEC"                                        # :538-539
         elif W2 % l2sp == 0:
-            f["l2_down"] = "CFG_L2_BR_P4S+F_VEC+F_SKIP_PAD"                             # :542-544
+            f["l2_down"] = "CFG_L2_BR_P4S+F_VEC+F_SKIP_PAD"                             # :541-543
         else:
-            f["l2_down"] = "CFG_L2_BR_P4"                                               # :546
-        esp = "CFG_L2_BR_P2S+F_VEC" if small2 else "CFG_L2_BR_P4" + vec(W2 % l2sp == 0)  # :575-585
+            f["l2_down"] = "CFG_L2_BR_P4"                                               # :545
+        esp = "CFG_L2_BR_P2S+F_VEC" if small2 else "CFG_L2_BR_P4" + vec(W2 % l2sp == 0)  # :564-574
         if p > 1:
             f["l2_esp_fused"] = esp
         f["l2_esp_last"] = esp
-        f["l3_reduce"] = ("CFG_L3_C1S_BNL_P1" if n * H3 * cdiv(W3, 128) * 4 <= num_cus * 8     # :618-621
+        f["l3_reduce"] = ("CFG_L3_C1S_BNL_P1" if n * H3 * cdiv(W3, 128) * 4 <= num_cus * 8     # :607-610
                           else "CFG_L3_C1S_BNL")
-    else:       # p = 0: nothing to fuse into; b2 runs as a kernel of its own (:595-600)
-        f["l2_down"] = "unfused CFG_L2_BR_P4" + vec(W2 % l2sp == 0)                     # :557
+    else:       # p = 0: nothing to fuse into; b2 runs as a kernel of its own (:584-589)
+        f["l2_down"] = "unfused CFG_L2_BR_P4" + vec(W2 % l2sp == 0)                     # :547
         f["cat_b2"] = "cat_b2_kernel"
-        f["l3_reduce"] = "CFG_L3_C1S"                                                   # :623
-    small3 = n * H3 * cdiv(W3, 64) * 2 <= num_cus * small3_waves                        # :608
+        f["l3_reduce"] = "CFG_L3_C1S"                                                   # :612
+    small3 = n * H3 * cdiv(W3, 64) * 2 <= num_cus * small3_waves                        # :597
     if q > 0:
         fused = "CFG_L3_BR_P1R" if small3 else "CFG_L3_BR_P2R+F_VEC" if W3 % 2 == 0 else "CFG_L3_BR_P2F"
-        f["l3_down"] = fused                                                            # :628-641
+        f["l3_down"] = fused                                                            # :617-627
         if q > 1:
-            f["l3_esp_fused"] = fused                                                   # :661-682
-        f["l3_esp_last"] = ("CFG_L3_BR_P1R" if small3 else "CFG_L3_BR_P2R+F_VEC" if W3 % 2 == 0   # :684-698
+            f["l3_esp_fused"] = fused                                                   # :647-660
+        f["l3_esp_last"] = ("CFG_L3_BR_P1R" if small3 else "CFG_L3_BR_P2R+F_VEC" if W3 % 2 == 0   # :662-673
                             else "CFG_L3_BR_P2")
     else:
-        f["l3_down"] = "unfused CFG_L3_BR" + vec(W3 % 4 == 0)                           # :643
+        f["l3_down"] = "unfused CFG_L3_BR" + vec(W3 % 4 == 0)                           # :629
     cp = padded_classes(classes)
     if cp < 12:
-        f["dec3"] = "dec3_kernel"                                                       # :769-782
+        f["dec3"] = "dec3_kernel"                                                       # :744-757
     elif cp <= 16:
-        f["dec3"] = "MFMA MT16" + vec(W2 % 8 == 0)                                      # :753-754
+        f["dec3"] = "MFMA MT16" + vec(W2 % 8 == 0)                                      # :728-729
     else:
-        f["dec3"] = "MFMA MT32" + vec(W2 % 4 == 0)                                      # :755-756
+        f["dec3"] = "MFMA MT32" + vec(W2 % 4 == 0)                                      # :730-731
     if cp == 5:
-        f["dec_conv"] = "dec_tail_kernel"                                               # :786-816
+        f["dec_conv"] = "dec_tail_kernel"                                               # :761-790
     elif cp <= 16:
-        f["dec_conv"] = "MFMA MT16" + vec(W1 % 8 == 0)                                  # :826-827
+        f["dec_conv"] = "MFMA MT16" + vec(W1 % 8 == 0)                                  # :800-801
     else:
-        f["dec_conv"] = "MFMA MT32" + vec(W1 % 4 == 0)                                  # :828-829
+        f["dec_conv"] = "MFMA MT32" + vec(W1 % 4 == 0)                                  # :802-803
     return f
 
 
@@ -109,45 +113,45 @@ def edges(H, W):
 # name them ("launch_vec": the vector mapping is chosen from the width, espnet.hip:48-54)
 LAUNCH_SITES = [
     "CFG_L2_C1S",                                                                                   # :501
-    "launch_vec CFG_L2_BR_P2S", "CFG_L2_BR_P4S+F_VEC+F_SKIP_PAD", "launch_vec CFG_L2_BR_P4",        # :540-546
-    "launch_vec CFG_L2_BR_P4", "launch_vec CFG_L2_BR_P4", "launch_vec CFG_L2_BR_P4",                # :548-555
-    "launch_vec CFG_L2_BR_P4",                                                                      # :557
-    "CFG_L2_C1",                                                                                    # :570
-    "launch_vec CFG_L2_BR_P2S", "launch_vec CFG_L2_BR_P4",                                          # :577-579
-    "launch_vec CFG_L2_BR_P2S", "launch_vec CFG_L2_BR_P4", "launch_vec CFG_L2_BR_P4",               # :583-587
-    "CFG_L3_C1S_BNL_P1", "CFG_L3_C1S_BNL", "CFG_L3_C1S",                                            # :619-623
-    "CFG_L3_BR_P1R", "CFG_L3_BR_W16", "CFG_L3_BR_P2R+F_VEC", "CFG_L3_BR+F_VEC", "CFG_L3_BR_P2F",    # :629-641
-    "launch_vec CFG_L3_BR",                                                                         # :643
-    "CFG_L3_C1",                                                                                    # :656
-    "CFG_L3_BR_P1R", "CFG_L3_BR_W16", "CFG_L3_BR+F_VEC", "CFG_L3_BR_P2R+F_VEC", "CFG_L3_BR_P2F",    # :663-682
-    "CFG_L3_BR_P1R", "CFG_L3_BR_W16", "CFG_L3_BR_P2R+F_VEC", "CFG_L3_BR+F_VEC", "CFG_L3_BR_P2",     # :685-698
-    "launch_vec 16, 8, 2 * CLS, 9, 1, 1, CLS, CLS, 8, 3", "launch_vec 32, 8, 2 * CLS, 9, 1, 1, CLS, CLS, 4, 3",  # :754-756
-    "launch_vec 16, 8, CINP, 9, 1, 1, CLS, CLS, 8, 3", "launch_vec 32, 8, CINP, 9, 1, 1, CLS, CLS, 4, 3",        # :827-829
+    "launch_vec CFG_L2_BR_P2S", "CFG_L2_BR_P4S+F_VEC+F_SKIP_PAD", "launch_vec CFG_L2_BR_P4",        # :539-545
+    "launch_vec CFG_L2_BR_P4",                                                                      # :547
+    "CFG_L2_C1",                                                                                    # :560
+    "launch_vec CFG_L2_BR_P2S", "launch_vec CFG_L2_BR_P4",                                          # :566-568
+    "launch_vec CFG_L2_BR_P2S", "launch_vec CFG_L2_BR_P4", "launch_vec CFG_L2_BR_P4",               # :572-576
+    "CFG_L3_C1S_BNL_P1", "CFG_L3_C1S_BNL", "CFG_L3_C1S",                                            # :608-612
+    "CFG_L3_BR_P1R", "CFG_L3_BR_P2R+F_VEC", "CFG_L3_BR+F_VEC", "CFG_L3_BR_P2F",                     # :618-627
+    "launch_vec CFG_L3_BR",                                                                         # :629
+    "CFG_L3_C1",                                                                                    # :642
+    "CFG_L3_BR_P1R", "CFG_L3_BR_P2R+F_VEC", "CFG_L3_BR_P2F",                                        # :649-660
+    "CFG_L3_BR_P1R", "CFG_L3_BR_P2R+F_VEC", "CFG_L3_BR+F_VEC", "CFG_L3_BR_P2",                      # :663-673
+    "launch_vec 16, 8, 2 * CLS, 9, 1, 1, CLS, CLS, 8, 3", "launch_vec 32, 8, 2 * CLS, 9, 1, 1, CLS, CLS, 4, 3",  # :729-731
+    "launch_vec 16, 8, CINP, 9, 1, 1, CLS, CLS, 8, 3", "launch_vec 32, 8, CINP, 9, 1, 1, CLS, CLS, 4, 3",        # :801-803
 ]
 
 # the predicates forms() restates, as espnet.hip spells them (whitespace aside), and how often each occurs there
 PREDICATES = [
     ("static constexpr bool no_vec() { return false; }", 1),                                        # :42
     ("if (ca.W % cfg[8] == 0 && !no_vec())", 1),                                                    # :51
-    ("a.H = out.H; a.W = out.W;", 1),                                                               # :419-420
+    ("a.H = out.H; a.W = out.W;", 1),                                                               # :420-421
     ("const bool small2 = CFG_SMALL2_WAVES > 0 && (long long)n * H2 * cdiv(W2, 64) * 2 <= "
      "(long long)m->num_cus * CFG_SMALL2_WAVES && W2 % 2 == 0 && !no_vec();", 1),                   # :529
-    ("const bool fuse_b2 = m->p > 0;", 1),                                                          # :530
-    ("const bool lazy_b2 = fuse_b2 && CFG_LAZY_B2;", 1),                                            # :531
-    ("if (ca.W % L2SP == 0 && !no_vec())", 1),                                                      # :543
+    ("const bool lazy_b2 = m->p > 0;", 2),                                                          # :314, :530
+    ("if (m->l2_0.fused_next) {", 1),                                                               # :537
+    ("if (!lazy_b2) { L.run(K_CAT_B2, 0, [&] {", 1),                                                # :584-585
+    ("if (ca.W % L2SP == 0 && !no_vec())", 1),                                                      # :542
     ("const bool small3 = (long long)n * H3 * cdiv(W3, 64) * 2 <= (long long)m->num_cus * CFG_SMALL3_WAVES "
-     "&& !no_vec();", 1),                                                                           # :608
-    ("if ((long long)n * H3 * cdiv(W3, 128) * 4 <= (long long)m->num_cus * 8)", 1),                 # :618
-    ("if (ca.W % 2 == 0 && !no_vec())", 3),                                                         # :634, :676, :691
-    ("if (ca.W % 4 == 0 && !no_vec())", 3),                                                         # :639, :669, :696
-    ("if constexpr (CLS >= 12)", 1),                                                                # :748
-    ("if constexpr (CLS <= 16)", 2),                                                                # :753, :826
-    ("if constexpr (CLS == 5)", 1),                                                                 # :786
-    ("m.cp = classes == 5 ? 5 : (classes + 3) / 4 * 4;", 1),                                        # :998
+     "&& !no_vec();", 1),                                                                           # :597
+    ("if ((long long)n * H3 * cdiv(W3, 128) * 4 <= (long long)m->num_cus * 8)", 1),                 # :607
+    ("if (ca.W % 2 == 0 && !no_vec())", 3),                                                         # :620, :654, :666
+    ("if (ca.W % 4 == 0 && !no_vec())", 2),                                                         # :625, :671
+    ("if constexpr (CLS >= 12)", 1),                                                                # :723
+    ("if constexpr (CLS <= 16)", 2),                                                                # :728, :800
+    ("if constexpr (CLS == 5)", 1),                                                                 # :761
+    ("m.cp = classes == 5 ? 5 : (classes + 3) / 4 * 4;", 1),                                        # :972
     ('auto next2 = [&](int i) { return (CFG_FUSE_L2 && i < p) ? e + "level2." + std::to_string(i) : std::string(); };',
-     1),                                                                                            # :1037
+     1),                                                                                            # :1011
     ('auto next3 = [&](int i) { return ((CFG_FUSE_L3 == 2 || (CFG_FUSE_L3 == 1 && i == 0)) && i < q) ? e + "level3." + '
-     'std::to_string(i) : std::string(); };', 1),                                                   # :1038
+     'std::to_string(i) : std::string(); };', 1),                                                   # :1012
 ]
 
 
@@ -184,9 +188,27 @@ def test_dispatch_tripwire():
     for name, value in CONFIG.items():
         m = re.search(r"#ifndef %s\n#define %s (\S+)" % (name, name), cfg)
         assert m and m.group(1) == str(value), name
+    m = re.search(r"constexpr int L2SP = (\d+);", cfg)
+    assert m and int(m.group(1)) == L2SP
     for name, p in PIXELS_PER_LANE.items():
         m = re.search(r"#define %s\s+([^/\n]+)" % name, cfg)
         assert m and m.group(1).split(",")[8].strip() == p, name
+    # the switches that lost their A/B stay deleted ...
+    sources = [f for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".hip", ".inc", ".cpp", ".cu", ".txt"))]
+    assert len(sources) >= 10
+    for fname in sources:
+        text = _read(fname)
+        for name in DELETED:   # whole identifiers (`prev_n` is not `rev_n`); a name ending in "_" is a prefix
+            pattern = r"\b%s" % re.escape(name) + ("" if name.endswith("_") else r"\b")
+            assert not re.search(pattern, text), (fname, name)
+    # ... and a default nobody documents cannot ship: every overridable macro left is named in DESIGN.md's kernel section
+    with open(os.path.join(REPO, "DESIGN.md")) as fh:
+        design = fh.read()
+    kernels = design[design.index("\n## 4. Kernels"):design.index("\n## 5. ")]
+    macros = re.findall(r"#ifndef (\w+)\n#define \1\b", cfg + _read("conv_mfma.h"))
+    assert len(macros) >= 20 and len(set(macros)) == len(macros)
+    for name in macros:
+        assert "`%s`" % name in kernels, name
 
 
 # ---------------------------------------------------------------------------------------------- the cases

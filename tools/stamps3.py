@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Where one launch of a conv_mfma_kernel spends its time, from the per-chunk stamps of EVERY task of every wave
-(-DGS_DIAG build, GS_VARIANT=160..165 -> gpurun_out/stamps_*.txt; F_X_STAMP2 in csrc/conv_mfma.h).
+(-DGS_DIAG build, GS_VARIANT=160..165 -> $GS_STAMP_DIR/stamps_*.txt; F_X_STAMP2 in csrc/conv_mfma.h).
 
-    python tools/stamps3.py gpurun_out/stamps_l3esp.txt NCHUNK CPD [mfma_cycles_per_chunk] [clock_ghz]
+    python tools/stamps3.py $GS_STAMP_DIR/stamps_l3esp.txt NCHUNK CPD [mfma_cycles_per_chunk] [clock_ghz]
 
 A wave alternates between k-steps (matrix instructions of a chunk) and epilogues (after the last chunk of a dilation).  The two
 waves that share a SIMD are (block, wid) and (block, wid + 4).  For every SIMD the launch interval [first start, last end] is cut

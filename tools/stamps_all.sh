@@ -5,6 +5,7 @@ tag=${1:-r06}
 export GLOMSEG_EXPERIMENT=1 GLOMSEG_ALLOW_DIAG=1 GLOMSEG_LIB=variants_so/libglomseg_diag.so
 out=gpurun_out/stamps_$tag.txt
 : > $out
+export GS_STAMP_DIR=$(dirname $out)   # where the stamped launches of the diagnostic build write stamps_<tag>.txt
 # variant  file  NCHUNK CPD  matrix-pipe cycles of one chunk of one wave (k-steps x P x cycles per MFMA)
 while read v f nch cpd cyc; do
     GS_VARIANT=$v timeout -k 10 300 python tools/stamps_run.py > gpurun_out/stamps_run_$v.log 2>&1 || { echo "variant $v failed"; tail -5 gpurun_out/stamps_run_$v.log; exit 1; }

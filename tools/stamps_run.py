@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Runs four 32-tile forwards on the library under GLOMSEG_LIB (a -DGS_DIAG build) with GS_VARIANT set by the caller, so that the
-stamped launch of that variant (160..165, csrc/espnet_diag.inc) writes its gpurun_out/stamps_*.txt on the third call.
+stamped launch of that variant (160..165, csrc/espnet_diag.inc) writes its stamps_*.txt into $GS_STAMP_DIR (unset: the working directory) on the third call.
     GS_VARIANT=160 GLOMSEG_EXPERIMENT=1 GLOMSEG_ALLOW_DIAG=1 GLOMSEG_LIB=variants_so/libglomseg_diag.so python tools/stamps_run.py"""
 import os
 import sys
