@@ -15,7 +15,7 @@ if os.environ.get("GLOMSEG_LIB") and os.environ.get("GLOMSEG_EXPERIMENT") == "1"
 GS_OK = 0
 GS_IN_U8_BGR_NHWC = 0
 GS_IN_F32_NCHW = 1
-ABI_VERSION = 6
+ABI_VERSION = 7
 GS_BUILD_DIAG = 1
 MAX_CROPS_PER_CALL = 64
 

@@ -4,7 +4,7 @@
 // kernel argument, so a call allocates nothing, copies nothing and is stream-ordered like any other launch.
 //
 //   crops_prep_kernel    :107-116  (x - mean) / std at crop resolution -> cv2.resize INTER_LINEAR -> / 255 -> fp32 NCHW
-//   (forward)            :123,128  espnet_forward_ex: the mask comes out of the decoder tail, no logits
+//   (forward)            :123,128  espnet_forward_ex: the mask comes out of the decoder tail (ESPNet-C: of enc_head_kernel), no logits
 //   crops_back_kernel    :129,151-155  cv2.resize INTER_NEAREST back to every crop's size + per-class counts of THAT map
 //   crops_paste_kernel   eval_wsi_segmentation.py:311-312  np.max into the 1/ds slide map
 //
@@ -347,7 +347,9 @@ static gs_status check_common(gs_espnet *const *models, int n_models, const floa
     GS_REQUIRE(net_h >= 8 && net_w >= 8 && net_h % 8 == 0 && net_w % 8 == 0,
                "network size must be a positive multiple of 8 in both dimensions (got %dx%d)", net_h, net_w);
     for (int k = 0; k < n_models; ++k) {
-        GS_REQUIRE(models[k] && espnet_is_full_net(models[k]), "model %d is not a full ESPNet handle (the crop entries need the decoder)", k);
+        GS_REQUIRE(models[k], "model %d is null", k);
+        // (one ESPNet-C handle is served: its head kernel writes the network-resolution map where the decoder tail does)
+        GS_REQUIRE(n_models == 1 || espnet_is_full_net(models[k]), "ensemble member %d is an ESPNet-C handle: ensembles need full ESPNet members", k);
         GS_REQUIRE(espnet_classes(models[k]) == espnet_classes(models[0]), "model %d has %d classes, model 0 has %d", k,
                    espnet_classes(models[k]), espnet_classes(models[0]));
         for (int i = 0; i < 3; ++i)

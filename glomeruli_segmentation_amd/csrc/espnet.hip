@@ -14,6 +14,7 @@
 
 #include "conv_mfma.h"
 #include "dec_tail_args.h"
+#include "enc_head.h"
 #include "espnet_config.h"
 #include "espnet_kernels.h"
 #include "host_copy.h"
@@ -54,12 +55,13 @@ static gs_status launch_vec(const ConvArgs &ca, int num_cus, hipStream_t s)
 }
 enum KernelId {
     K_STEM, K_POOL, K_L2_C1S, K_L2_DOWN, K_L2_C1, K_L2_ESP, K_CAT_B2, K_L3_C1S, K_L3_DOWN, K_L3_C1, K_L3_ESP,
-    K_DEC1, K_DEC2, K_DEC3, K_DEC_CONV, K_DEC4, K_DEC_TAIL, K_COUNT
+    K_DEC1, K_DEC2, K_DEC3, K_DEC_CONV, K_DEC4, K_DEC_TAIL, K_ENC_HEAD, K_COUNT
 };
 static const char *kKernelNames[K_COUNT] = {
     "stem_kernel", "pool_kernel", "conv_l2_reduce_s2", "conv_l2_down_branches", "conv_l2_reduce_1x1",
     "conv_l2_esp_branches", "cat_b2_kernel", "conv_l3_reduce_s2", "conv_l3_down_branches", "conv_l3_reduce_1x1",
-    "conv_l3_esp_branches", "dec1_kernel", "dec2_kernel", "dec3_kernel", "conv_dec_cbr", "dec4_kernel", "dec_tail_kernel"};
+    "conv_l3_esp_branches", "dec1_kernel", "dec2_kernel", "dec3_kernel", "conv_dec_cbr", "dec4_kernel", "dec_tail_kernel",
+    "enc_head_kernel"};
 
 struct PackedConv {   // float offsets into the device weight blob
     long long c1 = -1, br = -1;
@@ -476,7 +478,7 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
         a.N = n;
         a.H = H;
         a.W = W;
-        if (hist && !m->encoder_only && (ens_mode == 0 || ens_mode >= 3)) {   // zeroed by the first kernel of the forward; the last one adds into it
+        if (hist && (ens_mode == 0 || ens_mode >= 3)) {   // zeroed by the first kernel of the forward; the last one adds into it
             a.hist_zero = hist;
             a.hist_count = n * m->classes;
         }
@@ -680,6 +682,9 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
 
     // ---- b3 + classifier (+ br + up_l3)  (Model.py:368-370)
     const int ncls = m->classes;   // real class count (CLS is the padded one): algorithmic FLOPs, output widths
+    // ESPNet-C: the 1/8-scale logits are an output of their own and the input of the head; a caller that wants the class map
+    // only gets them in the (otherwise unused) up_l3 buffer of the workspace, which is larger than [n][classes][H3][W3]
+    float *enc_logits = !m->encoder_only ? nullptr : logits ? logits : m->o2c.base;
     L.run(K_DEC1, px3 * (256 * ncls * 2) + px3 * (ncls * ncls * 4 * 2), [&] {
         Dec1Args a{};
         a.c0 = view(m->cc[0]);
@@ -688,7 +693,7 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
         a.br = m->encoder_only ? nullptr : wb + m->br;
         a.wup = m->encoder_only ? nullptr : wb + m->wup3;
         a.out = view(m->o2c);
-        a.enc_logits = m->encoder_only ? logits : nullptr;
+        a.enc_logits = enc_logits;
         a.N = n;
         a.classes = ncls;
         // (channel batch: 16 channels x (3 + CLS) scalar constants in flight fit the scalar registers for five classes only)
@@ -696,8 +701,22 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
         hipLaunchKernelGGL((dec1_kernel<CLS, CB>), dim3((unsigned)(((long long)n * H3 * W3 + 63) / 64)), dim3(256), 0, s, a);
         return GS_OK;
     });
-    if (m->encoder_only)
+    if (m->encoder_only) {
+        // ---- x8 bilinear upsampling + argmax + counts (VisualizeResults_iou.py:125-128,151-155,258-261), enc_head.h
+        if (mask)
+            L.run(K_ENC_HEAD, (double)H * W * (ncls * 6), [&] {
+                EncHeadArgs a{};
+                a.logits = enc_logits;
+                a.mask = mask;
+                a.hist = hist;
+                a.classes = ncls;
+                a.H3 = H3;
+                a.W3 = W3;
+                launch_enc_head(a, n, s);
+                return GS_OK;
+            });
         return L.st;
+    }
     set_stage("up_l3", m->o2c, ncls);
 
     // ---- level3_C + cat + BR (Model.py:372-373)
@@ -869,7 +888,7 @@ using namespace gs;
 extern "C" {
 
 const char *gs_last_error(void) { return g_err.c_str(); }
-int gs_abi_version(void) { return 6; }   // 2: lanes, block hook, detector, compositor LUT; 3: batched crop entries, detector host entry, build flags; 4: any class count 2..20 (hist is [n,classes]), batch planner, pinned-block query, overlays from the crop pipeline; 5: gs_device_fault_check, GS_ERR_DEVICE_FAULT; 6: gs_wsi_eval_windows
+int gs_abi_version(void) { return 7; }   // 2: lanes, block hook, detector, compositor LUT; 3: batched crop entries, detector host entry, build flags; 4: any class count 2..20 (hist is [n,classes]), batch planner, pinned-block query, overlays from the crop pipeline; 5: gs_device_fault_check, GS_ERR_DEVICE_FAULT; 6: gs_wsi_eval_windows; 7: ESPNet-C handles give class maps and counts (forward, segment_host, the crop entries with one model)
 gs_status gs_device_fault_check(void)
 {
     GS_HIP(hipDeviceSynchronize());
@@ -1267,12 +1286,9 @@ gs_status gs_espnet_forward_lane(gs_espnet *h, int lane, const void *in, int in_
     GS_REQUIRE(in_format == GS_IN_U8_BGR_NHWC || in_format == GS_IN_F32_NCHW, "unknown input format %d", in_format);
     GS_REQUIRE(in_format != GS_IN_U8_BGR_NHWC || (mean && std), "uint8 input needs mean and std");
     Model &m = h->lane(lane);
-    if (m.encoder_only) {
-        GS_REQUIRE(logits && !mask && !hist, "ESPNet-C handle: only the 1/8-scale logits output exists");
-    } else {
-        GS_REQUIRE(logits || mask, "nothing to compute: logits and mask are both NULL");
-        GS_REQUIRE(!hist || mask, "hist requires the mask output");
-    }
+    // (an ESPNet-C handle's logits are the 1/8-scale ones; its mask and counts come from the head kernel, enc_head.h)
+    GS_REQUIRE(logits || mask, "nothing to compute: logits and mask are both NULL");
+    GS_REQUIRE(!hist || mask, "hist requires the mask output");
     if (in_format == GS_IN_U8_BGR_NHWC)
         for (int i = 0; i < 3; ++i)
             GS_REQUIRE(std[i] != 0.0f, "std[%d] is zero", i);

@@ -148,16 +148,23 @@ class EspnetEngine:
                                                   out.data_ptr(), None, None, _stream_ptr(x.device)))
         return out
 
-    def segment(self, tiles_u8, mean, std, want_logits=False, want_hist=True, out_mask=None, out_hist=None, lane=None):
+    def segment(self, tiles_u8, mean, std, want_logits=False, want_hist=True, out_mask=None, out_hist=None, lane=None,
+                want_enc_logits=False):
         """uint8 BGR [N,H,W,3] on the GPU -> (mask uint8 [N,H,W], counts int64 [N,classes], logits|None).
         One pass of VisualizeResults_iou.py:107-128,151-155 for a batch.
+        ESPNet-C (encoder_only): the mask is the argmax of the encoder's logits upsampled x8 (:125-126,258-261), from the
+        library's head kernel; want_enc_logits=True also returns the 1/8-scale logits [N,classes,H/8,W/8] the mask of the SAME
+        pass was computed from (want_logits is refused for such an engine: it has no full-resolution logits).
         lane=None: on the current stream, in workspace 0.  lane=k: in workspace k on that lane's own stream (which first
         waits for the current stream, so inputs produced there are ready); the outputs belong to the lane's stream until
         wait_lanes() -- submit the next batch to another lane meanwhile."""
         if tiles_u8.dtype != torch.uint8 or tiles_u8.dim() != 4 or tiles_u8.shape[3] != 3 or not tiles_u8.is_cuda:
             raise ValueError("expected a uint8 [N,H,W,3] tensor on the GPU")
-        if self.encoder_only:
-            raise ValueError("segment() needs the full ESPNet (decoder)")
+        if want_enc_logits and not self.encoder_only:
+            raise ValueError("want_enc_logits: the 1/8-scale logits are an output of ESPNet-C engines only")
+        if want_logits and self.encoder_only:
+            raise ValueError("want_logits: an ESPNet-C engine has no full-resolution logits (want_enc_logits=True gives the 1/8-scale ones)")
+        want_logits = bool(want_logits or want_enc_logits)
         tiles_u8 = tiles_u8.contiguous()
         n, h, w, _ = tiles_u8.shape
         dev = tiles_u8.device
@@ -169,7 +176,8 @@ class EspnetEngine:
         hist = None
         if want_hist:
             hist = out_hist if out_hist is not None else torch.empty((n, self.classes), dtype=torch.int64, device=dev)
-        logits = torch.empty((n, self.classes, h, w), dtype=torch.float32, device=dev) if want_logits else None
+        lh, lw = (h // 8, w // 8) if self.encoder_only else (h, w)
+        logits = torch.empty((n, self.classes, lh, lw), dtype=torch.float32, device=dev) if want_logits else None
         with torch.cuda.device(dev):
             if lane is None:
                 if 0 in self._lane_streams:      # workspace 0 may still be in use on lane 0's own stream

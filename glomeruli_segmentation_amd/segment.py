@@ -91,9 +91,10 @@ def segment_batch(engine, images, mean, std, width, height, batch, want_net_maps
     masks (crop-size class maps), net_maps (network-resolution maps | None), counts (int64 [n, classes]: pixels per class of the
     crop-size maps) and overlays (the palette-coloured map blended over the crop, BGR | None) -- counts and overlays come out of
     the batched crop pipeline with the maps (gs_espnet_segment_crops_host: crops_back_kernel counts, crops_overlay_kernel
-    blends), the host only encodes.  ESPNet-C (modelType 2) has no such pipeline: its maps come from segment_images and the
-    two by-products from _byproducts (on the GPU as well)."""
-    if engine.encoder_only or not images:
+    blends), the host only encodes.  ESPNet-C (modelType 2) goes the same way: its maps come out of the library's head kernel where
+    the full network's come out of the decoder tail.  An engine without the batched entry (the CPU tests' stand-ins) gets its maps
+    from segment_images and the two by-products from _byproducts."""
+    if not hasattr(engine, "segment_crops") or not images:
         masks, net = segment_images(engine, images, mean, std, width, height, batch, want_net_maps=True)
         counts, overlays = _byproducts(engine, images, masks, want_overlay)
         return {"masks": masks, "net_maps": net if want_net_maps else None, "counts": counts, "overlays": overlays}
@@ -104,33 +105,13 @@ def segment_batch(engine, images, mean, std, width, height, batch, want_net_maps
 
 
 def _byproducts(engine, images, masks, want_overlay):
-    """counts (:151-155) and overlays (:139-146) of class maps that did not come out of the batched crop pipeline (ESPNet-C): on the
-    engine's GPU when it has one -- torch.bincount and gs_overlay_classmap, the arithmetic of crops_overlay_kernel -- else (the CPU tests'
-    stand-in engines) the same arithmetic in numpy"""
+    """counts (:151-155) and overlays (:139-146) of class maps that did not come out of the batched crop pipeline (an engine
+    without segment_crops: the CPU tests' stand-ins): the arithmetic of crops_back_kernel's counters and of
+    crops_overlay_kernel, in numpy"""
     classes = engine.classes
-    dev = getattr(engine, "device", None)
-    if dev is None or not hasattr(engine, "lib"):
-        counts = np.array([np.bincount(np.asarray(m).ravel(), minlength=classes)[:classes] for m in masks], dtype=np.int64).reshape(len(masks), classes)
-        overlays = [imageops.add_weighted(im, OVERLAY_WEIGHTS[0], imageops.colourise(m), OVERLAY_WEIGHTS[1])
-                    for im, m in zip(images, masks)] if want_overlay else None
-        return counts, overlays
-    import ctypes
-    import torch
-    from . import _lib
-    pal = torch.from_numpy(np.ascontiguousarray(imageops.PALETTE)).to(dev)
-    counts = np.zeros((len(masks), classes), dtype=np.int64)
-    overlays = [] if want_overlay else None
-    with torch.cuda.device(dev):
-        for i, (im, m) in enumerate(zip(images, masks)):
-            mg = torch.from_numpy(np.ascontiguousarray(m)).to(dev)
-            counts[i] = torch.bincount(mg.flatten().long(), minlength=classes)[:classes].cpu().numpy()
-            if want_overlay:
-                ig = torch.from_numpy(np.ascontiguousarray(im)).to(dev)
-                out = torch.empty_like(ig)
-                _lib.check(engine.lib.gs_overlay_classmap(ig.data_ptr(), mg.data_ptr(), int(m.shape[0]), int(m.shape[1]), pal.data_ptr(),
-                                                          int(pal.shape[0]), ctypes.c_float(OVERLAY_WEIGHTS[0]), ctypes.c_float(OVERLAY_WEIGHTS[1]),
-                                                          out.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-                overlays.append(out.cpu().numpy())
+    counts = np.array([np.bincount(np.asarray(m).ravel(), minlength=classes)[:classes] for m in masks], dtype=np.int64).reshape(len(masks), classes)
+    overlays = [imageops.add_weighted(im, OVERLAY_WEIGHTS[0], imageops.colourise(m), OVERLAY_WEIGHTS[1])
+                for im, m in zip(images, masks)] if want_overlay else None
     return counts, overlays
 
 
@@ -139,14 +120,12 @@ def segment_images(engine, images, mean, std, width, height, batch, want_net_map
     (with want_net_maps: (crop-size maps, network-resolution maps) -- the reference scores the latter, :202).
     A list of network-sized tiles goes down the fused uint8 pipeline (gs_espnet_segment_host); any other list goes through
     the batched crop pipeline (gs_espnet_segment_crops_host), which normalises and resizes on the GPU exactly in the
-    reference's order (:107-116) for a whole batch per launch.  With an encoder-only engine (modelType 2) every crop is
-    resampled on its own and the 1/8-scale logits are upsampled x8 bilinearly as the reference's `up` module does
-    (:259-261,125-126)."""
-    import torch
+    reference's order (:107-116) for a whole batch per launch.  An encoder-only engine (modelType 2) takes the same two
+    branches: the x8 bilinear upsampling of its 1/8-scale logits (the reference's `up` module, :259-261,125-126) and the
+    argmax are one kernel of the library."""
     out = [None] * len(images)
     net = [None] * len(images)
-    enc = engine.encoder_only
-    if not enc and images:
+    if images:
         if all(im.shape[:2] == (height, width) for im in images):
             # network-sized tiles: the fused uint8 path (normalisation through the stem's table), pinned pipeline
             masks, _ = engine.segment_host(np.stack(images), mean, std, batch=batch, want_hist=False)
@@ -159,22 +138,6 @@ def segment_images(engine, images, mean, std, width, height, batch, want_net_map
             out = r["masks"]
             if want_net_maps:
                 net = list(r["net_maps"])
-        return (out, net) if want_net_maps else out
-    from .engine import crop_preprocess, mask_resize_nearest
-    for s in range(0, len(images), batch):
-        idx = list(range(s, min(s + batch, len(images))))
-        x = torch.empty((len(idx), 3, height, width), dtype=torch.float32, device=engine.device)
-        for j, i in enumerate(idx):      # crop stage on the GPU: normalise + bilinear resize fused (:107-116)
-            crop_preprocess(torch.from_numpy(images[i]).to(engine.device), mean, std, height, width, out=x[j])
-        logits = engine.forward_logits(x)
-        logits = torch.nn.functional.interpolate(logits, scale_factor=8, mode="bilinear", align_corners=False)
-        cls = logits.max(1)[1].byte()       # :128
-        cls_host = cls.cpu().numpy() if want_net_maps else None
-        for j, i in enumerate(idx):
-            h, w = images[i].shape[:2]
-            out[i] = mask_resize_nearest(cls[j], h, w).cpu().numpy()    # :129
-            if want_net_maps:
-                net[i] = cls_host[j]
     return (out, net) if want_net_maps else out
 
 
@@ -444,7 +407,7 @@ def main(argv=None):
         # ESPNet-C (:267-272): the checkpoint holds the encoder's own keys; a full-network checkpoint is accepted too
         if any(k.startswith("encoder.") for k in sd):
             sd = {k[len("encoder."):]: v for k, v in sd.items() if k.startswith("encoder.")}
-        engine = EspnetEngine(sd, classes=args.classes, p=args.p, q=args.q, encoder_only=True)
+        engine = EspnetEngine(sd, classes=args.classes, p=args.p, q=args.q, encoder_only=True, lanes=2)
     else:
         engine = EspnetEngine(sd, classes=args.classes, p=args.p, q=args.q, lanes=2)
     from .shard import abort_rank, finish_ranks

@@ -38,7 +38,7 @@ typedef enum gs_status {
 } gs_status;
 
 const char *gs_last_error(void);
-/* ABI version, bumped on any signature change. */
+/* ABI version, bumped on any change of a signature or of what an entry accepts (7: ESPNet-C handles give masks and counts). */
 int gs_abi_version(void);
 /* How the library was compiled: GS_BUILD_DIAG = a -DGS_DIAG experiment build (timing variants that return wrong results by
  * construction can be switched on through the environment); the product library returns 0 and reads no environment. */
@@ -92,10 +92,16 @@ typedef enum gs_input_format {
 /* One pass of the hot path over a batch of n tiles resident in device memory.
  * Replaces VisualizeResults_iou.py:107-128 + :151-155 (normalise -> model(x) -> argmax -> counts).
  *   in        device, format per in_format; mean/std (host, 3 floats, BGR) used only for U8 input
- *   logits    device fp32 [n,classes,h,w] or NULL   (ESPNet-C: [n,classes,h/8,w/8])
+ *   logits    device fp32 [n,classes,h,w] or NULL   (ESPNet-C: [n,classes,h/8,w/8], the encoder's own output)
  *   mask      device uint8 [n,h,w] or NULL          (first maximum wins, torch semantics)
  *   hist      device uint64 [n,classes] per-class pixel counts or NULL (requires the mask pass)
- * At least one of logits/mask must be non-NULL. */
+ * At least one of logits/mask must be non-NULL.
+ * ESPNet-C handles (ABI 7): mask is the argmax of the 1/8-scale logits upsampled x8 bilinearly, as the reference's
+ * torch.nn.Upsample(scale_factor=8, mode='bilinear') + img_out[0].max(0)[1] (VisualizeResults_iou.py:125-128,258-261), computed
+ * with the counts by one head kernel that never writes full-resolution logits (csrc/enc_head.h holds the exact expression).
+ * logits and mask given together come from the same pass.  Everything below that takes a handle serves an ESPNet-C handle as
+ * it serves a full one (lanes, gs_espnet_segment_host, the crop entries with one model); only the ensembles refuse it as a
+ * member: gs_espnet_ensemble_forward, gs_espnet_ensemble_segment_crops, gs_espnet_segment_crops_host with n_models > 1. */
 gs_status gs_espnet_forward(gs_espnet *h, const void *in, int in_format, int n, int height, int width,
                             const float mean[3], const float std[3], float *logits, uint8_t *mask,
                             unsigned long long *hist, void *hip_stream);
@@ -139,7 +145,7 @@ gs_status gs_mask_resize_nearest(const uint8_t *mask, int h, int w, int out_h, i
  * merged box at its own size): normalise at crop resolution -> cv2.resize INTER_LINEAR to the network size -> /255 ->
  * forward -> argmax -> cv2.resize INTER_NEAREST back to the crop size -> per-class counts of THAT map (:151-155), for a
  * whole batch per launch: ONE descriptor-table kernel resamples every crop of the batch into the network's input, the mask
- * comes straight from the decoder tail (no logits), ONE kernel resizes all masks back and counts, ONE kernel pastes them
+ * comes straight from the decoder tail (an ESPNet-C handle: from its head kernel; no logits either way), ONE kernel resizes all masks back and counts, ONE kernel pastes them
  * into the 1/ds slide map (eval_wsi_segmentation.py:311-312, np.max: overlapping crops of one launch meet through a
  * compare-and-swap).  The arithmetic per pixel is that of gs_crop_preprocess / gs_mask_resize_nearest / gs_wsi_paste_max. */
 typedef struct gs_crop_desc {
