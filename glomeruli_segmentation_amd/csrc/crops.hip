@@ -18,6 +18,7 @@
 #include "crop_sample.h"
 #include "gs_internal.h"
 #include "host_copy.h"
+#include "host_pipe.h"
 
 namespace gs {
 
@@ -256,57 +257,29 @@ struct CropPipe {
         float *prob = nullptr;          // ensemble accumulator [n,classes,net_h,net_w]
         size_t prob_bytes = 0;
     } lane[4];
-    // host pipeline
-    struct Slot {
-        unsigned char *hin = nullptr, *din = nullptr, *hout = nullptr, *dout = nullptr, *hnet = nullptr, *dnet = nullptr;
-        unsigned char *hov = nullptr, *dov = nullptr;   // overlays (allocated on first use, sized like the packed input)
-        bool ov_direct = false;
-        unsigned long long *hh = nullptr, *dh = nullptr;
-        hipEvent_t up = nullptr, done = nullptr, down = nullptr;
-        int first = -1, count = 0;
-        bool out_direct = false;
+    // host pipeline (host_pipe.h): four slots
+    struct Slot : PipeSlot {
+        Staging<unsigned char> in, out, net;   // packed crops, packed crop-size maps, network-resolution maps
+        Staging<unsigned char> ov;             // overlays (allocated on first use, sized like the packed input)
+        Staging<unsigned long long> hist;
+        bool out_direct = false, ov_direct = false;
         std::vector<gs_crop_desc> descs;
-    } sl[4];
-    size_t cap_in = 0, cap_out = 0, cap_net = 0, cap_ov = 0;
-    int cap_batch = 0;
-    hipStream_t h2d = nullptr, compute[2] = {nullptr, nullptr};
+        size_t in_bytes = 0, out_bytes = 0;    // packed sizes of the batch (fill_crop_descs)
+        void free_staging() { in.free(), out.free(), net.free(), ov.free(), hist.free(); }
+    };
+    HostPipe<Slot, 4> host;
 };
-
-static void free_slots(CropPipe &p)
-{
-    for (auto &s : p.sl) {
-        if (s.hin) hipHostFree(s.hin);
-        if (s.hout) hipHostFree(s.hout);
-        if (s.hnet) hipHostFree(s.hnet);
-        if (s.hh) hipHostFree(s.hh);
-        if (s.din) hipFree(s.din);
-        if (s.dout) hipFree(s.dout);
-        if (s.dnet) hipFree(s.dnet);
-        if (s.dh) hipFree(s.dh);
-        if (s.hov) hipHostFree(s.hov);
-        if (s.dov) hipFree(s.dov);
-        if (s.up) hipEventDestroy(s.up);
-        if (s.done) hipEventDestroy(s.done);
-        if (s.down) hipEventDestroy(s.down);
-        s = CropPipe::Slot();
-    }
-    p.cap_in = p.cap_out = p.cap_net = p.cap_ov = 0;
-    p.cap_batch = 0;
-}
 
 void crop_pipe_destroy(CropPipe *p)
 {
     if (!p)
         return;
-    free_slots(*p);
+    p->host.destroy();
     for (auto &l : p->lane) {
         if (l.f32) hipFree(l.f32);
         if (l.net) hipFree(l.net);
         if (l.prob) hipFree(l.prob);
     }
-    if (p->h2d) hipStreamDestroy(p->h2d);
-    for (auto &c : p->compute)
-        if (c) hipStreamDestroy(c);
     delete p;
 }
 
@@ -569,203 +542,111 @@ gs_status gs_espnet_segment_crops_host(gs_espnet *const *models, int n_models, c
     const size_t need_in = plan.need_in, need_out = plan.need_out;
     batch = plan.max_count;
     GS_REQUIRE(batch >= 1 && batch <= MAXC, "internal: planned a batch of %d crops", batch);
-    constexpr int NSLOT = 4;
-    gs_status rc = GS_OK;
-    auto fail = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == GS_OK) {
-            set_error("%s failed: %s", what, hipGetErrorString(e));
-            rc = GS_ERR_HIP;
-        }
-        return e != hipSuccess;
-    };
-    // three streams at three priorities, as in gs_espnet_segment_host (espnet.hip): HIP keeps a pool of hardware queues per
-    // priority, so the upload stream and the two compute streams never share a queue whatever else the process has made
-    if (!p.h2d || !p.compute[0] || !p.compute[1]) {   // all three or none: a partial set would run later calls on the NULL stream
-        int lo = 0, hi = 0;
-        fail(hipDeviceGetStreamPriorityRange(&lo, &hi), "hipDeviceGetStreamPriorityRange");
-        hipStream_t *want[3] = {&p.h2d, &p.compute[0], &p.compute[1]};
-        const int prio[3] = {hi, (lo + hi) / 2, lo};
-        for (int k = 0; k < 3 && rc == GS_OK; ++k)
-            if (!*want[k])
-                fail(hipStreamCreateWithPriority(want[k], hipStreamNonBlocking, prio[k]), "hipStreamCreate");
-        if (rc != GS_OK) {
-            for (hipStream_t *w : want) {
-                if (*w) hipStreamDestroy(*w);
-                *w = nullptr;
-            }
-            return rc;
-        }
-    }
-    if (p.cap_in < need_in || p.cap_out < need_out || p.cap_net < npx * batch || p.cap_batch < batch) {
-        fail(hipDeviceSynchronize(), "hipDeviceSynchronize");
-        const size_t ci = std::max(p.cap_in, need_in), co = std::max(p.cap_out, need_out), cn = std::max(p.cap_net, npx * batch);
-        const int cb = std::max(p.cap_batch, batch);
-        free_slots(p);
-        for (int i = 0; i < NSLOT && rc == GS_OK; ++i) {
-            CropPipe::Slot &s = p.sl[i];
-            fail(hipHostMalloc(reinterpret_cast<void **>(&s.hin), ci, hipHostMallocDefault), "hipHostMalloc");
-            fail(hipHostMalloc(reinterpret_cast<void **>(&s.hout), co, hipHostMallocDefault), "hipHostMalloc");
-            fail(hipHostMalloc(reinterpret_cast<void **>(&s.hnet), cn, hipHostMallocDefault), "hipHostMalloc");
-            fail(hipHostMalloc(reinterpret_cast<void **>(&s.hh), sizeof(unsigned long long) * GS_MAX_CLASSES * cb, hipHostMallocDefault), "hipHostMalloc");
-            fail(hipMalloc(reinterpret_cast<void **>(&s.din), ci), "hipMalloc");
-            fail(hipMalloc(reinterpret_cast<void **>(&s.dout), co), "hipMalloc");
-            fail(hipMalloc(reinterpret_cast<void **>(&s.dnet), cn), "hipMalloc");
-            fail(hipMalloc(reinterpret_cast<void **>(&s.dh), sizeof(unsigned long long) * GS_MAX_CLASSES * cb), "hipMalloc");
-            fail(hipEventCreateWithFlags(&s.up, hipEventDisableTiming), "hipEventCreate");
-            fail(hipEventCreateWithFlags(&s.done, hipEventDisableTiming), "hipEventCreate");
-            fail(hipEventCreateWithFlags(&s.down, hipEventDisableTiming), "hipEventCreate");
-        }
-        if (rc != GS_OK) {
-            free_slots(p);
-            return rc;
-        }
-        p.cap_in = ci;
-        p.cap_out = co;
-        p.cap_net = cn;
-        p.cap_batch = cb;
-    }
-    if (overlay && p.cap_ov < p.cap_in) {   // overlay staging: as large as the packed input, made when first asked for
-        fail(hipDeviceSynchronize(), "hipDeviceSynchronize");
-        for (int i = 0; i < NSLOT && rc == GS_OK; ++i) {
-            CropPipe::Slot &s = p.sl[i];
-            if (s.hov) hipHostFree(s.hov);
-            if (s.dov) hipFree(s.dov);
-            s.hov = s.dov = nullptr;
-            fail(hipHostMalloc(reinterpret_cast<void **>(&s.hov), p.cap_in, hipHostMallocDefault), "hipHostMalloc");
-            fail(hipMalloc(reinterpret_cast<void **>(&s.dov), p.cap_in), "hipMalloc");
-        }
-        if (rc != GS_OK) {
-            free_slots(p);
-            return rc;
-        }
-        p.cap_ov = p.cap_in;
-    }
-    for (auto &s : p.sl)
-        s.first = -1;
+    using Slot = CropPipe::Slot;
+    HipLatch fail;
+    if (!p.host.ensure(2, true, fail, [&](Slot &s) {
+            s.in.grow(need_in, fail);
+            s.out.grow(need_out, fail);
+            s.net.grow(npx * batch, fail);
+            s.hist.grow(sizeof(unsigned long long) * GS_MAX_CLASSES * batch, fail);
+            if (overlay) s.ov.grow(s.in.bytes, fail);
+        }))
+        return fail.rc;
     const bool net_pinned = net_masks && host_is_pinned(net_masks), hist_pinned = hist && host_is_pinned(hist);
-    auto drain = [&](CropPipe::Slot &s) {
-        if (s.first < 0 || rc != GS_OK)
+    // One DMA for a batch of page-locked destinations laid out like the packed device buffer (every one at its 256-byte-aligned
+    // offset behind the batch's first: what engine.segment_crops_host allocates) -- 32 separate DMA commands per batch sat in
+    // the compute stream between two forwards -- and only when the whole range is ONE page-locked allocation: separately
+    // pinned buffers that happen to be neighbours in virtual memory are written one by one.  off / bytes: crop j's place.
+    auto download_direct = [&](uint8_t *const *dst, const unsigned char *dev, int cnt, hipStream_t compute, auto off, auto bytes) {
+        bool packed = true;
+        for (int j = 0; j < cnt; ++j)
+            packed = packed && dst[j] == dst[0] + off(j);
+        const size_t b = off(cnt - 1) + bytes(cnt - 1);
+        packed = packed && host_block_is_pinned(dst[0], b);
+        if (packed) {
+            fail(hipMemcpy2DAsync(dst[0], b, dev, b, b, 1, hipMemcpyDeviceToHost, compute), "D2H copy");
             return;
-        if (fail(hipEventSynchronize(s.down), "hipEventSynchronize")) return;
-        if (masks && !s.out_direct)
-            parallel_jobs(s.count, 4, [&](int j) {
-                std::memcpy(masks[s.first + j], s.hout + s.descs[j].out_off, (size_t)s.descs[j].h * s.descs[j].w);
-            });
-        if (overlay && !s.ov_direct)
-            parallel_jobs(s.count, 4, [&](int j) {
-                std::memcpy(overlay->out_bgr[s.first + j], s.hov + s.descs[j].in_off, (size_t)s.descs[j].h * s.descs[j].w * 3);
-            });
-        if (net_masks && !net_pinned)
-            parallel_memcpy(net_masks + (size_t)s.first * npx, s.hnet, npx * s.count);
-        if (hist && !hist_pinned)
-            std::memcpy(hist + (size_t)s.first * ncl, s.hh, sizeof(unsigned long long) * ncl * s.count);
-        s.first = -1;
+        }
+        for (int j = 0; j < cnt && fail.ok(); ++j)
+            fail(hipMemcpy2DAsync(dst[j], bytes(j), dev + off(j), bytes(j), bytes(j), 1, hipMemcpyDeviceToHost, compute), "D2H copy");
     };
-    int slot = 0, bi = 0;
-    for (; bi + 1 < (int)starts.size() && rc == GS_OK; slot = (slot + 1) % NSLOT, ++bi) {
-        const int first = starts[bi];
-        CropPipe::Slot &s = p.sl[slot];
-        hipStream_t compute = p.compute[bi & 1];
-        drain(s);   // the slot's previous batch must have left its buffers
-        if (rc != GS_OK) break;
-        const int cnt = starts[bi + 1] - first;
-        s.descs.assign(cnt, gs_crop_desc{});
-        size_t oi = 0, oo = 0;
-        fill_crop_descs(heights, widths, x1, y1, first, cnt, s.descs.data(), &oi, &oo);
-        bool in_direct = true;
-        s.out_direct = masks != nullptr;
-        s.ov_direct = overlay != nullptr;
-        for (int j = 0; j < cnt; ++j) {
-            in_direct = in_direct && host_is_pinned(crops[first + j]);
-            if (masks)
-                s.out_direct = s.out_direct && host_is_pinned(masks[first + j]);
-            if (overlay)
-                s.ov_direct = s.ov_direct && host_is_pinned(overlay->out_bgr[first + j]);
-        }
-        // uploads: page-locked crops are DMA'd in place, pageable ones are packed into the slot's pinned buffer by a few
-        // threads (one core copies ~10 GB/s) and leave as one copy
-        if (in_direct) {
-            for (int j = 0; j < cnt && rc == GS_OK; ++j)
-                fail(hipMemcpyAsync(s.din + s.descs[j].in_off, crops[first + j], (size_t)s.descs[j].h * s.descs[j].w * 3, hipMemcpyHostToDevice,
-                                    p.h2d), "H2D copy");
-        } else {
-            parallel_jobs(cnt, bi == 0 ? 8 : 4, [&](int j) {   // (the first batch's staging is exposed: more threads)
-                std::memcpy(s.hin + s.descs[j].in_off, crops[first + j], (size_t)s.descs[j].h * s.descs[j].w * 3);
-            });
-            fail(hipMemcpyAsync(s.din, s.hin, oi, hipMemcpyHostToDevice, p.h2d), "H2D copy");
-        }
-        if (rc != GS_OK) break;
-        fail(hipEventRecord(s.up, p.h2d), "hipEventRecord");
-        fail(hipStreamWaitEvent(compute, s.up, 0), "hipStreamWaitEvent");
-        if (nl == 1 && bi > 0)   // one workspace: this batch after the previous one (on the other stream)
-            fail(hipStreamWaitEvent(compute, p.sl[(slot + NSLOT - 1) % NSLOT].done, 0), "hipStreamWaitEvent");
-        gs_status st2 = run_batch(models, n_models, bi % nl, s.din, s.descs.data(), cnt, means, stds, net_h, net_w, s.dnet,
-                                  (masks || overlay) ? s.dout : nullptr, hist ? s.dh : nullptr, paste, compute, overlay, overlay ? s.dov : nullptr);
-        if (st2 != GS_OK) { rc = st2; break; }
-        fail(hipEventRecord(s.done, compute), "hipEventRecord");
-        // downloads through hipMemcpy2DAsync: the SDMA engine, not a blit kernel that would take CUs from the next forward
-        // (gs_espnet_segment_host)
-        if (masks) {
-            if (s.out_direct) {
-                // page-locked destinations laid out like the packed device buffer (every map at its 256-byte-aligned offset
-                // behind the batch's first one: what engine.segment_crops_host allocates) leave as ONE copy; 32 separate DMA
-                // commands per batch sat in the compute stream between two forwards
-                bool packed = true;
-                for (int j = 0; j < cnt; ++j)
-                    packed = packed && masks[first + j] == masks[first] + s.descs[j].out_off;
-                const size_t b = (size_t)s.descs[cnt - 1].out_off + (size_t)s.descs[cnt - 1].h * s.descs[cnt - 1].w;
-                // ... and only when the whole range is ONE page-locked allocation: separately pinned buffers that happen to be
-                // neighbours in virtual memory are written map by map
-                packed = packed && host_block_is_pinned(masks[first], b);
-                if (packed) {
-                    fail(hipMemcpy2DAsync(masks[first], b, s.dout, b, b, 1, hipMemcpyDeviceToHost, compute), "D2H copy");
-                } else {
-                    for (int j = 0; j < cnt && rc == GS_OK; ++j) {
-                        const size_t b = (size_t)s.descs[j].h * s.descs[j].w;
-                        fail(hipMemcpy2DAsync(masks[first + j], b, s.dout + s.descs[j].out_off, b, b, 1, hipMemcpyDeviceToHost, compute), "D2H copy");
-                    }
-                }
-            } else {
-                fail(hipMemcpy2DAsync(s.hout, oo, s.dout, oo, oo, 1, hipMemcpyDeviceToHost, compute), "D2H copy");
+    const gs_status rc = p.host.run(
+        (int)starts.size() - 1, nl == 1, fail,
+        [&](int bi, Slot &s, hipStream_t h2d) {
+            const int first = s.first = starts[bi], cnt = s.count = starts[bi + 1] - first;
+            s.descs.assign(cnt, gs_crop_desc{});
+            fill_crop_descs(heights, widths, x1, y1, first, cnt, s.descs.data(), &s.in_bytes, &s.out_bytes);
+            bool in_direct = true;
+            s.out_direct = masks != nullptr;
+            s.ov_direct = overlay != nullptr;
+            for (int j = 0; j < cnt; ++j) {
+                in_direct = in_direct && host_is_pinned(crops[first + j]);
+                if (masks)
+                    s.out_direct = s.out_direct && host_is_pinned(masks[first + j]);
+                if (overlay)
+                    s.ov_direct = s.ov_direct && host_is_pinned(overlay->out_bgr[first + j]);
             }
-        }
-        if (overlay) {
-            if (s.ov_direct) {   // (as the maps: one DMA for a batch laid out like the packed buffer inside ONE pinned allocation)
-                bool packed = true;
-                for (int j = 0; j < cnt; ++j)
-                    packed = packed && overlay->out_bgr[first + j] == overlay->out_bgr[first] + s.descs[j].in_off;
-                const size_t b = (size_t)s.descs[cnt - 1].in_off + (size_t)s.descs[cnt - 1].h * s.descs[cnt - 1].w * 3;
-                packed = packed && host_block_is_pinned(overlay->out_bgr[first], b);
-                if (packed) {
-                    fail(hipMemcpy2DAsync(overlay->out_bgr[first], b, s.dov, b, b, 1, hipMemcpyDeviceToHost, compute), "D2H copy");
-                } else {
-                    for (int j = 0; j < cnt && rc == GS_OK; ++j) {
-                        const size_t bj = (size_t)s.descs[j].h * s.descs[j].w * 3;
-                        fail(hipMemcpy2DAsync(overlay->out_bgr[first + j], bj, s.dov + s.descs[j].in_off, bj, bj, 1, hipMemcpyDeviceToHost, compute), "D2H copy");
-                    }
-                }
+            // uploads: page-locked crops are DMA'd in place, pageable ones are packed into the slot's pinned buffer by a few
+            // threads (one core copies ~10 GB/s) and leave as one copy
+            if (in_direct) {
+                for (int j = 0; j < cnt && fail.ok(); ++j)
+                    fail(hipMemcpyAsync(s.in.d + s.descs[j].in_off, crops[first + j], (size_t)s.descs[j].h * s.descs[j].w * 3,
+                                        hipMemcpyHostToDevice, h2d), "H2D copy");
             } else {
-                fail(hipMemcpy2DAsync(s.hov, oi, s.dov, oi, oi, 1, hipMemcpyDeviceToHost, compute), "D2H copy");
+                parallel_jobs(cnt, bi == 0 ? 8 : 4, [&](int j) {   // (the first batch's staging is exposed: more threads)
+                    std::memcpy(s.in.h + s.descs[j].in_off, crops[first + j], (size_t)s.descs[j].h * s.descs[j].w * 3);
+                });
+                fail(hipMemcpyAsync(s.in.d, s.in.h, s.in_bytes, hipMemcpyHostToDevice, h2d), "H2D copy");
             }
-        }
-        if (net_masks)
-            fail(hipMemcpy2DAsync(net_pinned ? net_masks + (size_t)first * npx : s.hnet, npx, s.dnet, npx, npx, cnt, hipMemcpyDeviceToHost, compute),
-                 "D2H copy");
-        if (hist) {
-            const size_t b = sizeof(unsigned long long) * ncl * cnt;
-            fail(hipMemcpy2DAsync(hist_pinned ? hist + (size_t)first * ncl : s.hh, b, s.dh, b, b, 1, hipMemcpyDeviceToHost, compute), "D2H copy");
-        }
-        fail(hipEventRecord(s.down, compute), "hipEventRecord");
-        s.first = first;
-        s.count = cnt;
-    }
-    for (int k = 0; k < NSLOT; ++k)
-        drain(p.sl[(slot + k) % NSLOT]);   // oldest first
-    if (rc != GS_OK) {
-        hipDeviceSynchronize();
-        return rc;
-    }
-    return gs_device_fault_check();
+        },
+        [&](int bi, Slot &s, hipStream_t compute) {
+            return run_batch(models, n_models, bi % nl, s.in.d, s.descs.data(), s.count, means, stds, net_h, net_w, s.net.d,
+                             (masks || overlay) ? s.out.d : nullptr, hist ? s.hist.d : nullptr, paste, compute, overlay,
+                             overlay ? s.ov.d : nullptr);
+        },
+        [&](int, Slot &s, hipStream_t compute) {
+            const int first = s.first, cnt = s.count;
+            auto map_off = [&](int j) { return (size_t)s.descs[j].out_off; };
+            auto map_bytes = [&](int j) { return (size_t)s.descs[j].h * s.descs[j].w; };
+            auto bgr_off = [&](int j) { return (size_t)s.descs[j].in_off; };
+            auto bgr_bytes = [&](int j) { return (size_t)s.descs[j].h * s.descs[j].w * 3; };
+            const size_t oi = s.in_bytes, oo = s.out_bytes;
+            if (masks) {
+                if (s.out_direct)
+                    download_direct(masks + first, s.out.d, cnt, compute, map_off, map_bytes);
+                else
+                    fail(hipMemcpy2DAsync(s.out.h, oo, s.out.d, oo, oo, 1, hipMemcpyDeviceToHost, compute), "D2H copy");
+            }
+            if (overlay) {
+                if (s.ov_direct)
+                    download_direct(overlay->out_bgr + first, s.ov.d, cnt, compute, bgr_off, bgr_bytes);
+                else
+                    fail(hipMemcpy2DAsync(s.ov.h, oi, s.ov.d, oi, oi, 1, hipMemcpyDeviceToHost, compute), "D2H copy");
+            }
+            if (net_masks)
+                fail(hipMemcpy2DAsync(net_pinned ? net_masks + (size_t)first * npx : s.net.h, npx, s.net.d, npx, npx, cnt,
+                                      hipMemcpyDeviceToHost, compute), "D2H copy");
+            if (hist) {
+                const size_t b = sizeof(unsigned long long) * ncl * cnt;
+                fail(hipMemcpy2DAsync(hist_pinned ? hist + (size_t)first * ncl : s.hist.h, b, s.hist.d, b, b, 1, hipMemcpyDeviceToHost,
+                                      compute), "D2H copy");
+            }
+        },
+        [&](Slot &s) {
+            if (masks && !s.out_direct)
+                parallel_jobs(s.count, 4, [&](int j) {
+                    std::memcpy(masks[s.first + j], s.out.h + s.descs[j].out_off, (size_t)s.descs[j].h * s.descs[j].w);
+                });
+            if (overlay && !s.ov_direct)
+                parallel_jobs(s.count, 4, [&](int j) {
+                    std::memcpy(overlay->out_bgr[s.first + j], s.ov.h + s.descs[j].in_off, (size_t)s.descs[j].h * s.descs[j].w * 3);
+                });
+            if (net_masks && !net_pinned)
+                parallel_memcpy(net_masks + (size_t)s.first * npx, s.net.h, npx * s.count);
+            if (hist && !hist_pinned)
+                std::memcpy(hist + (size_t)s.first * ncl, s.hist.h, sizeof(unsigned long long) * ncl * s.count);
+        });
+    return rc != GS_OK ? rc : gs_device_fault_check();
 }
 
 }  // extern "C"

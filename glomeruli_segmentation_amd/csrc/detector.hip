@@ -19,6 +19,7 @@
 
 #include "gs_internal.h"
 #include "host_copy.h"
+#include "host_pipe.h"
 
 namespace gs {
 
@@ -583,32 +584,14 @@ struct Detector {
     float rpn_iou = 0.7f, det_iou = 0.6f, det_score = 0.0f;
     void *ws = nullptr;
     size_t ws_bytes = 0;
-    // host pipeline (gs_detector_detect_host): three slots of pinned + device staging, kept across calls
-    struct Slot {
-        unsigned char *hin = nullptr, *din = nullptr;
-        float *hres = nullptr, *dres = nullptr;   // [boxes n*D*4 | scores n*D | classes n*D | num n]
-        hipEvent_t up = nullptr, down = nullptr;
-        int first = -1, count = 0;
-    } sl[3];
-    size_t pipe_in_bytes = 0;
-    int pipe_batch = 0;
-    hipStream_t pipe_h2d = nullptr, pipe_compute = nullptr;
+    // host pipeline (host_pipe.h): three slots of pinned + device staging, kept across calls
+    struct Slot : PipeSlot {
+        Staging<unsigned char> in;
+        Staging<float> res;   // [boxes b*D*4 | scores b*D | classes b*D | num b], b = the batch the pair was made for
+        void free_staging() { in.free(), res.free(); }
+    };
+    HostPipe<Slot, 3> host;
 };
-
-static void free_det_pipeline(Detector &d)
-{
-    for (auto &s : d.sl) {
-        if (s.hin) hipHostFree(s.hin);
-        if (s.hres) hipHostFree(s.hres);
-        if (s.din) hipFree(s.din);
-        if (s.dres) hipFree(s.dres);
-        if (s.up) hipEventDestroy(s.up);
-        if (s.down) hipEventDestroy(s.down);
-        s = Detector::Slot();
-    }
-    d.pipe_in_bytes = 0;
-    d.pipe_batch = 0;
-}
 
 static inline unsigned nblk(long long items) { return (unsigned)((items + 255) / 256); }
 
@@ -695,9 +678,7 @@ void gs_detector_destroy(gs_detector *h)
     if (!h)
         return;
     hipDeviceSynchronize();
-    free_det_pipeline(h->d);
-    if (h->d.pipe_h2d) hipStreamDestroy(h->d.pipe_h2d);
-    if (h->d.pipe_compute) hipStreamDestroy(h->d.pipe_compute);
+    h->d.host.destroy();
     if (h->d.ws) hipFree(h->d.ws);
     if (h->d.dblob) hipFree(h->d.dblob);
     delete h;
@@ -833,97 +814,48 @@ gs_status gs_detector_detect_host(gs_detector *h, const uint8_t *const *windows,
         GS_REQUIRE(windows[i], "window %d is a null pointer", i);
     if (batch > n) batch = n;
     Detector &d = h->d;
-    constexpr int NSLOT = 3, D = DET_MAX_DET;
+    constexpr int D = DET_MAX_DET;
+    constexpr size_t res_b = (D * 6 + 1) * sizeof(float);   // result bytes per window
+    using Slot = Detector::Slot;
     const size_t in_b = (size_t)height * width * 3;
-    const size_t res_f = (size_t)batch * (D * 6 + 1);   // floats per slot
-    gs_status rc = GS_OK;
-    auto fail = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == GS_OK) {
-            set_error("%s failed: %s", what, hipGetErrorString(e));
-            rc = GS_ERR_HIP;
-        }
-        return e != hipSuccess;
-    };
-    if (!d.pipe_h2d || !d.pipe_compute) {   // both or neither: a partial pair would run later calls on the NULL stream
-        int lo = 0, hi = 0;
-        fail(hipDeviceGetStreamPriorityRange(&lo, &hi), "hipDeviceGetStreamPriorityRange");
-        if (rc == GS_OK && !d.pipe_h2d)
-            fail(hipStreamCreateWithPriority(&d.pipe_h2d, hipStreamNonBlocking, hi), "hipStreamCreate");
-        if (rc == GS_OK && !d.pipe_compute)
-            fail(hipStreamCreateWithPriority(&d.pipe_compute, hipStreamNonBlocking, lo), "hipStreamCreate");
-        if (rc != GS_OK) {
-            if (d.pipe_h2d) hipStreamDestroy(d.pipe_h2d);
-            if (d.pipe_compute) hipStreamDestroy(d.pipe_compute);
-            d.pipe_h2d = d.pipe_compute = nullptr;
-            return rc;
-        }
-    }
-    if (d.pipe_in_bytes < in_b * batch || d.pipe_batch < batch) {
-        fail(hipDeviceSynchronize(), "hipDeviceSynchronize");
-        free_det_pipeline(d);
-        for (auto &s : d.sl) {
-            fail(hipHostMalloc(reinterpret_cast<void **>(&s.hin), in_b * batch, hipHostMallocDefault), "hipHostMalloc");
-            fail(hipHostMalloc(reinterpret_cast<void **>(&s.hres), res_f * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
-            fail(hipMalloc(reinterpret_cast<void **>(&s.din), in_b * batch), "hipMalloc");
-            fail(hipMalloc(reinterpret_cast<void **>(&s.dres), res_f * sizeof(float)), "hipMalloc");
-            fail(hipEventCreateWithFlags(&s.up, hipEventDisableTiming), "hipEventCreate");
-            fail(hipEventCreateWithFlags(&s.down, hipEventDisableTiming), "hipEventCreate");
-        }
-        if (rc != GS_OK) {
-            free_det_pipeline(d);
-            return rc;
-        }
-        d.pipe_in_bytes = in_b * batch;
-        d.pipe_batch = batch;
-    }
-    for (auto &s : d.sl)
-        s.first = -1;
-    const int pb = d.pipe_batch;   // the slot layout follows the batch the buffers were made for
-    auto drain = [&](Detector::Slot &s) {
-        if (s.first < 0 || rc != GS_OK)
-            return;
-        if (fail(hipEventSynchronize(s.down), "hipEventSynchronize")) return;
-        const float *r = s.hres;
-        std::memcpy(boxes + (size_t)s.first * D * 4, r, sizeof(float) * s.count * D * 4);
-        std::memcpy(scores + (size_t)s.first * D, r + (size_t)pb * D * 4, sizeof(float) * s.count * D);
-        std::memcpy(classes + (size_t)s.first * D, r + (size_t)pb * D * 5, sizeof(float) * s.count * D);
-        std::memcpy(num + s.first, r + (size_t)pb * D * 6, sizeof(float) * s.count);
-        s.first = -1;
-    };
-    int slot = 0;
-    for (int first = 0; first < n && rc == GS_OK; first += batch, slot = (slot + 1) % NSLOT) {
-        Detector::Slot &s = d.sl[slot];
-        drain(s);
-        if (rc != GS_OK) break;
-        const int cnt = n - first < batch ? n - first : batch;
-        bool direct = true;
-        for (int j = 0; j < cnt; ++j)
-            direct = direct && host_is_pinned(windows[first + j]);
-        if (direct) {
-            for (int j = 0; j < cnt && rc == GS_OK; ++j)
-                fail(hipMemcpyAsync(s.din + (size_t)j * in_b, windows[first + j], in_b, hipMemcpyHostToDevice, d.pipe_h2d), "H2D copy");
-        } else {
-            parallel_jobs(cnt, 4, [&](int j) { std::memcpy(s.hin + (size_t)j * in_b, windows[first + j], in_b); });
-            fail(hipMemcpyAsync(s.din, s.hin, in_b * cnt, hipMemcpyHostToDevice, d.pipe_h2d), "H2D copy");
-        }
-        if (rc != GS_OK) break;
-        fail(hipEventRecord(s.up, d.pipe_h2d), "hipEventRecord");
-        fail(hipStreamWaitEvent(d.pipe_compute, s.up, 0), "hipStreamWaitEvent");
-        float *r = s.dres;
-        gs_status st2 = gs_detector_forward(h, s.din, cnt, height, width, r, r + (size_t)pb * D * 4, r + (size_t)pb * D * 5,
-                                            r + (size_t)pb * D * 6, nullptr, nullptr, nullptr, nullptr, d.pipe_compute);
-        if (st2 != GS_OK) { rc = st2; break; }
-        const size_t rb = (size_t)pb * (D * 6 + 1) * sizeof(float);
-        fail(hipMemcpy2DAsync(s.hres, rb, s.dres, rb, rb, 1, hipMemcpyDeviceToHost, d.pipe_compute), "D2H copy");
-        fail(hipEventRecord(s.down, d.pipe_compute), "hipEventRecord");
-        s.first = first;
-        s.count = cnt;
-    }
-    for (int k = 0; k < NSLOT; ++k)
-        drain(d.sl[(slot + k) % NSLOT]);
-    if (rc != GS_OK)
-        hipDeviceSynchronize();
-    return rc;
+    HipLatch fail;
+    if (!d.host.ensure(1, false, fail, [&](Slot &s) {
+            s.in.grow(in_b * batch, fail);
+            s.res.grow(res_b * batch, fail);
+        }))
+        return fail.rc;
+    const size_t pb = d.host.sl[0].res.bytes / res_b;   // the slot layout follows the batch the buffers were made for
+    return d.host.run(
+        (n + batch - 1) / batch, false, fail,
+        [&](int bi, Slot &s, hipStream_t h2d) {
+            const int first = s.first = bi * batch, cnt = s.count = n - first < batch ? n - first : batch;
+            bool direct = true;
+            for (int j = 0; j < cnt; ++j)
+                direct = direct && host_is_pinned(windows[first + j]);
+            if (direct) {
+                for (int j = 0; j < cnt && fail.ok(); ++j)
+                    fail(hipMemcpyAsync(s.in.d + (size_t)j * in_b, windows[first + j], in_b, hipMemcpyHostToDevice, h2d), "H2D copy");
+            } else {
+                parallel_jobs(cnt, 4, [&](int j) { std::memcpy(s.in.h + (size_t)j * in_b, windows[first + j], in_b); });
+                fail(hipMemcpyAsync(s.in.d, s.in.h, in_b * cnt, hipMemcpyHostToDevice, h2d), "H2D copy");
+            }
+        },
+        [&](int, Slot &s, hipStream_t compute) {
+            float *r = s.res.d;
+            return gs_detector_forward(h, s.in.d, s.count, height, width, r, r + pb * D * 4, r + pb * D * 5, r + pb * D * 6, nullptr, nullptr,
+                                       nullptr, nullptr, compute);
+        },
+        [&](int, Slot &s, hipStream_t compute) {
+            const size_t rb = pb * res_b;
+            fail(hipMemcpy2DAsync(s.res.h, rb, s.res.d, rb, rb, 1, hipMemcpyDeviceToHost, compute), "D2H copy");
+        },
+        [&](Slot &s) {
+            const float *r = s.res.h;
+            std::memcpy(boxes + (size_t)s.first * D * 4, r, sizeof(float) * s.count * D * 4);
+            std::memcpy(scores + (size_t)s.first * D, r + pb * D * 4, sizeof(float) * s.count * D);
+            std::memcpy(classes + (size_t)s.first * D, r + pb * D * 5, sizeof(float) * s.count * D);
+            std::memcpy(num + s.first, r + pb * D * 6, sizeof(float) * s.count);
+        });
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 #include "espnet_config.h"
 #include "espnet_kernels.h"
 #include "host_copy.h"
+#include "host_pipe.h"
 
 namespace gs {
 
@@ -99,17 +100,6 @@ struct Model {
     std::map<std::string, std::pair<Act, int>> stages;   // name -> (activation, channels) of the last forward
     int last_n = 0;
     bool b2_lazy = false;    // planes 64..127 of the stage "b2" are not materialised by the last forward (read_stage fills them)
-
-    // host pipeline (gs_espnet_segment_host): two slots of pinned + device staging, kept across calls
-    struct Slot {
-        uint8_t *hin = nullptr, *hout = nullptr, *din = nullptr, *dout = nullptr;
-        unsigned long long *hh = nullptr, *dh = nullptr;
-        hipEvent_t up = nullptr, done = nullptr, down = nullptr;
-        int first = -1, count = 0;
-    } sl[4];   // four slots, two per stream: the host runs up to four batches ahead of the GPU
-    hipStream_t pipe_compute = nullptr, pipe_h2d = nullptr;   // the first of the pipeline's two compute streams (even batches) and its upload stream; see gs_espnet_segment_host
-    size_t pipe_in_bytes = 0, pipe_out_bytes = 0;
-    int pipe_batch = 0;
 
     // profiling
     bool profile = false;
@@ -862,23 +852,12 @@ static gs_status forward_any(Model *m, const void *in, int in_format, int n, int
     return GS_ERR_UNSUPPORTED;
 }
 
-static void free_pipeline(Model &m)
-{
-    for (auto &s : m.sl) {
-        if (s.hin) hipHostFree(s.hin);
-        if (s.hout) hipHostFree(s.hout);
-        if (s.hh) hipHostFree(s.hh);
-        if (s.din) hipFree(s.din);
-        if (s.dout) hipFree(s.dout);
-        if (s.dh) hipFree(s.dh);
-        if (s.up) hipEventDestroy(s.up);
-        if (s.done) hipEventDestroy(s.done);
-        if (s.down) hipEventDestroy(s.down);
-        s = Model::Slot();
-    }
-    m.pipe_in_bytes = m.pipe_out_bytes = 0;
-    m.pipe_batch = 0;
-}
+// staging of gs_espnet_segment_host (host_pipe.h): four slots, two per compute stream, kept across calls
+struct TileSlot : PipeSlot {
+    Staging<uint8_t> in, out;
+    Staging<unsigned long long> hist;
+    void free_staging() { in.free(), out.free(), hist.free(); }
+};
 
 }  // namespace gs
 
@@ -917,7 +896,7 @@ int gs_build_flags(void)
 struct gs_espnet {
     Model m;
     std::vector<std::unique_ptr<Model>> lanes;   // lane k >= 1 is lanes[k - 1]
-    hipStream_t pipe_compute2 = nullptr;         // gs_espnet_segment_host: the second of its two streams (odd batches)
+    HostPipe<TileSlot, 4> tile_pipe;             // gs_espnet_segment_host: staging state
     gs::CropPipe *crop_pipe = nullptr;           // gs_espnet_segment_crops*: staging state (csrc/crops.hip)
     Model &lane(int k) { return k == 0 ? m : *lanes[k - 1]; }
 };
@@ -1199,11 +1178,8 @@ void gs_espnet_destroy(gs_espnet *h)
         hipEventDestroy(ev.a);
         hipEventDestroy(ev.b);
     }
-    free_pipeline(h->m);
+    h->tile_pipe.destroy();
     crop_pipe_destroy(h->crop_pipe);
-    if (h->m.pipe_compute) hipStreamDestroy(h->m.pipe_compute);
-    if (h->m.pipe_h2d) hipStreamDestroy(h->m.pipe_h2d);
-    if (h->pipe_compute2) hipStreamDestroy(h->pipe_compute2);
     for (auto &l : h->lanes) {
         for (auto &ev : l->events) {
             hipEventDestroy(ev.a);
@@ -1248,7 +1224,7 @@ gs_status gs_espnet_set_lanes(gs_espnet *h, int n_lanes)
     }
     while ((int)h->lanes.size() < n_lanes - 1) {
         std::unique_ptr<Model> l(new Model(h->m));   // same weights (shared device blob), same configuration ...
-        l->ws = nullptr;                             // ... and nothing else of the original: own workspace, no pipeline, no profile
+        l->ws = nullptr;                             // ... and nothing else of the original: own workspace, no profile
         l->ws_bytes = 0;
         l->ws_n = l->ws_h = l->ws_w = 0;
         l->prob = nullptr;
@@ -1256,11 +1232,6 @@ gs_status gs_espnet_set_lanes(gs_espnet *h, int n_lanes)
         l->stages.clear();
         l->events.clear();
         l->profile = false;
-        for (auto &s : l->sl)
-            s = Model::Slot();
-        l->pipe_compute = l->pipe_h2d = nullptr;
-        l->pipe_in_bytes = l->pipe_out_bytes = 0;
-        l->pipe_batch = 0;
         h->lanes.push_back(std::move(l));
     }
     return GS_OK;
@@ -1464,144 +1435,66 @@ gs_status gs_espnet_segment_host(gs_espnet *h, const uint8_t *tiles, int n_tiles
     if (batch > n_tiles) batch = n_tiles;
     const size_t in_b = (size_t)height * width * 3, out_b = (size_t)height * width;
     const size_t ncl = (size_t)h->m.classes;   // hist is [n_tiles][classes]
-    constexpr int NSLOT = 4;
     const int nl = h->lanes.empty() ? 1 : 2;   // batches alternate between (at most) two lanes, each on its own compute stream
-    // caller buffers that are already page-locked (hipHostMalloc / hipHostRegister) are DMA'd in place;
+    // caller buffers that are already page-locked are DMA'd in place;
     // pageable ones are staged through the pinned slot buffers with a host memcpy
     const bool in_pinned = host_is_pinned(tiles), out_pinned = host_is_pinned(masks) && (!hist || host_is_pinned(hist));
-    Model &m = h->m;
-    using Slot = Model::Slot;
-    Slot *sl = m.sl;
-    gs_status rc = GS_OK;
-    auto fail = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == GS_OK) {
-            set_error("%s failed: %s", what, hipGetErrorString(e));
-            rc = GS_ERR_HIP;
-        }
-        return e != hipSuccess;
-    };
-    // Three streams.  Uploads run ahead on their own stream, which never waits for anything on the GPU.  Batch b's forward
-    // AND its download (SDMA, see below) are on compute stream b % 2, in order, behind one wait for the batch's
-    // upload; with two lanes the two compute streams have no dependency on each other, with one lane (a single workspace)
-    // each forward also waits for the previous batch's.
-    // (Round 2 first had a download stream as well, chained to the forward by an event.  HIP multiplexes streams onto a few
-    // hardware queues and a queue runs its packets in order whatever stream they came from: the download's wait-for-the-
-    // forward packet sat in front of later uploads, and in the rocprofv3 timeline every batch's first kernel -- and the
-    // upload two batches ahead -- started only when the previous batch's download had ended: 0.4 ms lost per batch.  With
-    // upload, forward and download of a batch all on one stream the two streams fell into step and copied at the same
-    // time.  No packet that waits for a kernel may sit on a stream that others might queue behind.)
-    // The three streams get three different priorities, because HIP keeps a separate pool of hardware queues per priority:
-    // whatever other streams the process has made (torch's, the engine's lane streams), these three never share a queue
-    // with each other.  (With equal priorities and two torch streams made first, the same pipeline ran at 9.2 k instead of
-    // 10.4 k patches/s.)  The upload stream is the high one; the two compute streams differ only nominally.
-    int prio_lo = 0, prio_hi = 0;
-    fail(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi), "hipDeviceGetStreamPriorityRange");   // (least, greatest): numerically lo >= hi
-    const int prio_mid = (prio_lo + prio_hi) / 2;
-    if (!m.pipe_compute)
-        fail(hipStreamCreateWithPriority(&m.pipe_compute, hipStreamNonBlocking, prio_mid), "hipStreamCreate");
-    if (!h->pipe_compute2)
-        fail(hipStreamCreateWithPriority(&h->pipe_compute2, hipStreamNonBlocking, prio_lo), "hipStreamCreate");
-    if (!m.pipe_h2d)
-        fail(hipStreamCreateWithPriority(&m.pipe_h2d, hipStreamNonBlocking, prio_hi), "hipStreamCreate");
-    if (m.pipe_in_bytes < in_b * batch || m.pipe_out_bytes < out_b * batch || m.pipe_batch < batch) {
-        free_pipeline(m);
-        for (int i = 0; i < NSLOT; ++i) {
-            Slot &s = sl[i];
-            fail(hipHostMalloc(reinterpret_cast<void **>(&s.hin), in_b * batch, hipHostMallocDefault), "hipHostMalloc");
-            fail(hipHostMalloc(reinterpret_cast<void **>(&s.hout), out_b * batch, hipHostMallocDefault), "hipHostMalloc");
-            fail(hipHostMalloc(reinterpret_cast<void **>(&s.hh), sizeof(unsigned long long) * GS_MAX_CLASSES * batch, hipHostMallocDefault), "hipHostMalloc");
-            fail(hipMalloc(reinterpret_cast<void **>(&s.din), in_b * batch), "hipMalloc");
-            fail(hipMalloc(reinterpret_cast<void **>(&s.dout), out_b * batch), "hipMalloc");
-            fail(hipMalloc(reinterpret_cast<void **>(&s.dh), sizeof(unsigned long long) * GS_MAX_CLASSES * batch), "hipMalloc");
-            fail(hipEventCreateWithFlags(&s.up, hipEventDisableTiming), "hipEventCreate");
-            fail(hipEventCreateWithFlags(&s.done, hipEventDisableTiming), "hipEventCreate");
-            fail(hipEventCreateWithFlags(&s.down, hipEventDisableTiming), "hipEventCreate");
-        }
-        m.pipe_in_bytes = in_b * batch;
-        m.pipe_out_bytes = out_b * batch;
-        m.pipe_batch = batch;
-    }
-    for (int i = 0; i < NSLOT; ++i)
-        sl[i].first = -1;
-    auto drain = [&](Slot &s) {   // wait for the slot's masks and hand them to the caller
-        if (s.first < 0 || rc != GS_OK)
-            return;
-        if (fail(hipEventSynchronize(s.down), "hipEventSynchronize")) return;
-        if (!out_pinned) {
-            parallel_memcpy(masks + (size_t)s.first * out_b, s.hout, out_b * s.count);
-            if (hist) std::memcpy(hist + (size_t)s.first * ncl, s.hh, sizeof(unsigned long long) * ncl * s.count);
-        }
-        s.first = -1;
-    };
-    int slot = 0, bi = 0;
+    auto &pipe = h->tile_pipe;
+    HipLatch fail;
+    if (!pipe.ensure(2, true, fail, [&](TileSlot &s) {
+            s.in.grow(in_b * batch, fail);
+            s.out.grow(out_b * batch, fail);
+            s.hist.grow(sizeof(unsigned long long) * GS_MAX_CLASSES * batch, fail);
+        }))
+        return fail.rc;
 #ifdef GS_DIAG
     // host-side timeline of the loop (GS_PIPE_TRACE=1): where does the enqueueing thread wait?
     const bool ptrace = std::getenv("GS_PIPE_TRACE") != nullptr;
     const auto pt0 = std::chrono::steady_clock::now();
-    auto stamp = [&](const char *what) {
+    auto stamp = [&](int bi, const char *what) {
         if (ptrace && bi < 12)
             std::fprintf(stderr, "pipe %2d %-10s %9.1f us\n", bi, what,
                          std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - pt0).count());
     };
     const int pskip = std::getenv("GS_PIPE_SKIP") ? std::atoi(std::getenv("GS_PIPE_SKIP")) : 0;   // 1: no uploads, 2: no downloads (timing only)
 #else
-    auto stamp = [](const char *) {};
+    auto stamp = [](int, const char *) {};
     constexpr int pskip = 0;
 #endif
-    for (int first = 0; first < n_tiles && rc == GS_OK; first += batch, slot = (slot + 1) % NSLOT, ++bi) {
-        Slot &s = sl[slot];
-        const int lane = bi % nl;
-        hipStream_t compute = (bi & 1) == 0 ? m.pipe_compute : h->pipe_compute2;
-        stamp("top");
-        drain(s);   // the slot's previous batch must have left its pinned buffers
-        stamp("drained");
-        if (rc != GS_OK) break;
-        const int cnt = n_tiles - first < batch ? n_tiles - first : batch;
-        const uint8_t *src = tiles + (size_t)first * in_b;
-        if (!in_pinned) {
-            parallel_memcpy(s.hin, src, in_b * cnt);
-            src = s.hin;
-        }
-        // (the slot's device buffers: its previous batch was drained above, i.e. computed and downloaded)
-        if (!(pskip & 1) || bi < NSLOT)
-            if (fail(hipMemcpyAsync(s.din, src, in_b * cnt, hipMemcpyHostToDevice, m.pipe_h2d), "H2D copy")) break;
-        stamp("h2d");
-        fail(hipEventRecord(s.up, m.pipe_h2d), "hipEventRecord");
-        fail(hipStreamWaitEvent(compute, s.up, 0), "hipStreamWaitEvent");
-        if (nl == 1 && bi > 0)   // one workspace: this forward after the previous batch's (recorded on the other stream)
-            fail(hipStreamWaitEvent(compute, sl[(slot + NSLOT - 1) % NSLOT].done, 0), "hipStreamWaitEvent");
-        stamp("waitev");
-        gs_status st2 = gs_espnet_forward_lane(h, lane, s.din, GS_IN_U8_BGR_NHWC, cnt, height, width, mean, std, nullptr,
-                                               s.dout, s.dh, compute);
-        if (st2 != GS_OK) { rc = st2; break; }
-        stamp("forward");
-        fail(hipEventRecord(s.done, compute), "hipEventRecord");
-        stamp("waitdone");
-        // Results -> pinned host memory through hipMemcpy2DAsync: on this stack a plain hipMemcpyAsync(DeviceToHost) runs as a
-        // blit KERNEL (__amd_rocclr_copyBuffer) and the rectangular copy goes to the SDMA engine (rocprofv3: a memory-copy
-        // record instead of a kernel, the same 53 GB/s).  A copy kernel of any size costs the pipeline its whole 0.33 ms:
-        // the level-2 / level-3 launches need every CU's full register file (one workgroup per CU), so every CU that holds a
-        // copy wave sends a launch into a second round -- measured 3.29 ms per batch with a 48-workgroup copy kernel, 2.96
-        // without the download, 2.93 without any copy.
-        uint8_t *hdst = out_pinned ? masks + (size_t)first * out_b : s.hout;
-        unsigned long long *hhdst = (out_pinned && hist) ? hist + (size_t)first * ncl : s.hh;
-        if (!(pskip & 2))
-            fail(hipMemcpy2DAsync(hdst, out_b, s.dout, out_b, out_b, cnt, hipMemcpyDeviceToHost, compute), "D2H copy");
-        if (hist || !out_pinned)
-            fail(hipMemcpy2DAsync(hhdst, sizeof(unsigned long long) * ncl * cnt, s.dh, sizeof(unsigned long long) * ncl * cnt,
-                                  sizeof(unsigned long long) * ncl * cnt, 1, hipMemcpyDeviceToHost, compute), "D2H copy");
-        fail(hipEventRecord(s.down, compute), "hipEventRecord");
-        stamp("d2h");
-        s.first = first;
-        s.count = cnt;
-    }
-    for (int k = 0; k < NSLOT; ++k)
-        drain(sl[(slot + k) % NSLOT]);   // oldest first
-    if (rc != GS_OK) {
-        hipDeviceSynchronize();
-        return rc;
-    }
-    return gs_device_fault_check();   // (every batch has been drained: a few microseconds)
+    const gs_status rc = pipe.run(
+        (n_tiles + batch - 1) / batch, nl == 1, fail,
+        [&](int bi, TileSlot &s, hipStream_t h2d) {
+            s.first = bi * batch;
+            s.count = n_tiles - s.first < batch ? n_tiles - s.first : batch;
+            const uint8_t *src = tiles + (size_t)s.first * in_b;
+            if (!in_pinned) {
+                parallel_memcpy(s.in.h, src, in_b * s.count);
+                src = s.in.h;
+            }
+            if (!(pskip & 1) || bi < pipe.NSLOT)
+                fail(hipMemcpyAsync(s.in.d, src, in_b * s.count, hipMemcpyHostToDevice, h2d), "H2D copy");
+        },
+        [&](int bi, TileSlot &s, hipStream_t compute) {
+            return gs_espnet_forward_lane(h, bi % nl, s.in.d, GS_IN_U8_BGR_NHWC, s.count, height, width, mean, std, nullptr, s.out.d,
+                                          s.hist.d, compute);
+        },
+        [&](int, TileSlot &s, hipStream_t compute) {
+            uint8_t *hdst = out_pinned ? masks + (size_t)s.first * out_b : s.out.h;
+            unsigned long long *hhdst = (out_pinned && hist) ? hist + (size_t)s.first * ncl : s.hist.h;
+            const size_t hb = sizeof(unsigned long long) * ncl * s.count;
+            if (!(pskip & 2))
+                fail(hipMemcpy2DAsync(hdst, out_b, s.out.d, out_b, out_b, s.count, hipMemcpyDeviceToHost, compute), "D2H copy");
+            if (hist || !out_pinned)
+                fail(hipMemcpy2DAsync(hhdst, hb, s.hist.d, hb, hb, 1, hipMemcpyDeviceToHost, compute), "D2H copy");
+        },
+        [&](TileSlot &s) {
+            if (out_pinned)
+                return;
+            parallel_memcpy(masks + (size_t)s.first * out_b, s.out.h, out_b * s.count);
+            if (hist) std::memcpy(hist + (size_t)s.first * ncl, s.hist.h, sizeof(unsigned long long) * ncl * s.count);
+        },
+        stamp);
+    return rc != GS_OK ? rc : gs_device_fault_check();   // (every batch has been drained: a few microseconds)
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// Host-side staging helpers shared by the host pipelines (gs_espnet_segment_host, gs_espnet_segment_crops_host,
-// gs_detector_detect_host): the page-locked test; the threaded copies are host_jobs.h.
+// What the host entries ask about caller memory: the page-locked tests.  The pipeline they all run on is host_pipe.h, the
+// threaded copies are host_jobs.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
