@@ -15,8 +15,9 @@ if os.environ.get("GLOMSEG_LIB") and os.environ.get("GLOMSEG_EXPERIMENT") == "1"
 GS_OK = 0
 GS_IN_U8_BGR_NHWC = 0
 GS_IN_F32_NCHW = 1
-ABI_VERSION = 7
+ABI_VERSION = 8
 GS_BUILD_DIAG = 1
+GS_FORM_NONE = -1
 MAX_CROPS_PER_CALL = 64
 
 STATUS_NAMES = {0: "GS_OK", 1: "GS_ERR_INVALID", 2: "GS_ERR_HIP", 3: "GS_ERR_NOMEM", 4: "GS_ERR_UNSUPPORTED",
@@ -95,6 +96,8 @@ PROTOTYPES = {
     "gs_espnet_ensemble_forward": (_I, [ctypes.POINTER(_P), _I, _P, _I, _I, _I, _FP, _FP, _P, _P, _P]),
     "gs_espnet_read_stage": (_I, [_P, ctypes.c_char_p, _I, _P, ctypes.c_size_t, ctypes.POINTER(_I * 3)]),
     "gs_espnet_block_forward": (_I, [_P, _I, _I, _I, _P, _I, _I, _P]),
+    "gs_espnet_plan_forward": (_I, [_I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I), _I, ctypes.POINTER(_I)]),
+    "gs_espnet_form_info": (_I, [_I, _I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I)]),
     "gs_espnet_profile_enable": (_I, [_P, _I]),
     "gs_espnet_profile_read": (_I, [_P, ctypes.POINTER(KernelTime), _I, ctypes.POINTER(_I)]),
     "gs_crop_preprocess": (_I, [_P, _I, _I, _FP, _FP, _I, _I, _P, _P]),

@@ -16,6 +16,7 @@
 #include "dec_tail_args.h"
 #include "enc_head.h"
 #include "espnet_config.h"
+#include "forward_plan.h"
 #include "espnet_kernels.h"
 #include "host_copy.h"
 #include "host_pipe.h"
@@ -44,16 +45,6 @@ static bool no_vec() { return getenv_flag("GS_NO_VEC"); }
 static constexpr bool no_vec() { return false; }
 #endif
 
-// Every unit-stride conv launch exists in two pixel mappings; the vector one (F_VEC) needs the output width to be a
-// multiple of P (the 9th configuration parameter).
-template <int FLAGS, int... C>
-static gs_status launch_vec(const ConvArgs &ca, int num_cus, hipStream_t s)
-{
-    constexpr int cfg[] = {C...};
-    if (ca.W % cfg[8] == 0 && !no_vec())
-        return launch_conv_mfma<C..., FLAGS | F_VEC>(ca, num_cus, s);
-    return launch_conv_mfma<C..., FLAGS>(ca, num_cus, s);
-}
 enum KernelId {
     K_STEM, K_POOL, K_L2_C1S, K_L2_DOWN, K_L2_C1, K_L2_ESP, K_CAT_B2, K_L3_C1S, K_L3_DOWN, K_L3_C1, K_L3_ESP,
     K_DEC1, K_DEC2, K_DEC3, K_DEC_CONV, K_DEC4, K_DEC_TAIL, K_ENC_HEAD, K_COUNT
@@ -297,13 +288,13 @@ static gs_status layout_workspace(Model *m, int n, int H, int W)
         m->cc[i] = make_act(128, 128, H3, W3, 0, 0, 0, 0);
     m->o2c = make_act(cls, cls, H2, W2, 0, 0, 0, 0);
     // (twelve classes and more: combine_l2_l3.1's 3x3 runs on the matrix cores and reads its input with a zero halo; t3 is its output)
-    const bool dec3_mfma = cls >= 12;
+    const bool dec3_mfma = dec3_on_mfma(cls);
     m->tt = dec3_mfma ? make_act(2 * cls, 2 * cls, H2, W2, 1, 1, 32, 1) : make_act(2 * cls, 2 * cls, H2, W2, 0, 0, 0, 0);
     m->t3 = dec3_mfma ? make_act(cls, cls, H2, W2, 0, 0, 0, 0) : make_act(1, 1, 8, 8, 0, 0, 0, 0);
     m->ff = make_act(cls, cls, H1, W1, 0, 0, 0, 0);
     // Lazy b2 (p > 0): output1_0 is stored RAW, once, straight into planes 64..127 of output1_cat -- bb[0] becomes a view of
     // them -- and the consumers of output1_cat apply b2 to those planes on load (espnet_config.h, "Lazy b2").
-    const bool lazy_b2 = m->p > 0;
+    const bool lazy_b2 = b2_is_lazy(m->p);
     if (lazy_b2)
         m->bb[0] = Act();   // no storage of its own
     Act *all[] = {&m->a0c, &m->inp1, &m->inp2, &m->r2[0], &m->r2[1], &m->bb[0], &m->bb[1], &m->bb[2], &m->a1, &m->r3[0], &m->r3[1],
@@ -434,6 +425,168 @@ static inline unsigned blocks_for(long long items) { return (unsigned)((items + 
 #define GS_DIAG_STAMPED(var, tag, ca, ...)
 #endif
 
+// ------------------------------------------------------------------------------------------
+// The per-class dispatch: every conv_mfma_kernel instantiation of the forward is spelled here, once -- one `case` per form of
+// forward_plan.h's table.  forward_impl and the single-block hook (gs_espnet_block_forward) launch through these and decide
+// nothing themselves; the caller has put the second / third output of a fused form into `ca` (with_dual / with_fused).
+static gs_status not_planned(const char *launch_class)
+{
+    set_error("internal: the forward plan has no form for launch class %s", launch_class);
+    return GS_ERR_INVALID;
+}
+
+// The two pixel mappings of a unit-stride conv launch; `vec` (F_VEC) is the plan's decision.  (The level-2 small-batch forms
+// are only ever planned with it: their scalar twins are instantiated and never launched.)
+template <int FLAGS, int... C>
+static gs_status launch_vec(const ConvArgs &ca, int num_cus, hipStream_t s, bool vec)
+{
+    return vec ? launch_conv_mfma<C..., FLAGS | F_VEC>(ca, num_cus, s) : launch_conv_mfma<C..., FLAGS>(ca, num_cus, s);
+}
+
+// the launches that have one form: the level-2 stride-2 reduce and the 1x1 reduces that no epilogue computed
+static gs_status launch_l2_reduce(const Model *m, const ConvArgs &ca, hipStream_t s) { return launch_conv_mfma<CFG_L2_C1S, F_S2PAIR | POL_L2_C1S | S2FLIP_L2>(ca, m->num_cus, s); }
+static gs_status launch_l2_c1(const Model *m, const ConvArgs &ca, hipStream_t s) { return launch_conv_mfma<CFG_L2_C1, POL_L2_C1>(ca, m->num_cus, s); }   // 1x1: the run mapping measured no slower
+static gs_status launch_l3_c1(const Model *m, const ConvArgs &ca, hipStream_t s) { return launch_conv_mfma<CFG_L3_C1, POL_L3_C1>(ca, m->num_cus, s); }
+
+// the raw output only, with or without ESP blocks behind it: b2 is applied by the consumers (p > 0: the level-3 stride-2
+// reduce and dec2 on load; p == 0: cat_b2_kernel)
+static gs_status launch_l2_down(const Model *m, form::l2_down f, const ConvArgs &ca, hipStream_t s)
+{
+    switch (f) {
+    case form::l2_down::P2S_VEC: return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2, CFG_L2_BR_P2S>(ca, m->num_cus, s, true);
+    case form::l2_down::P4S_VEC_SKIP:
+        GS_DIAG_STAMPED(162, "l2down", ca, F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2 | F_VEC, CFG_L2_BR_P4)
+        return launch_conv_mfma<CFG_L2_BR_P4S, F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2 | F_VEC | F_SKIP_PAD>(ca, m->num_cus, s);
+    case form::l2_down::P4_VEC:
+        GS_DIAG_STAMPED(162, "l2down", ca, F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2 | F_VEC, CFG_L2_BR_P4)
+        return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2, CFG_L2_BR_P4>(ca, m->num_cus, s, true);
+    case form::l2_down::P4: return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2, CFG_L2_BR_P4>(ca, m->num_cus, s, false);
+    case form::l2_down::UNFUSED_P4_VEC: return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT), CFG_L2_BR_P4>(ca, m->num_cus, s, true);
+    case form::l2_down::UNFUSED_P4: return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT), CFG_L2_BR_P4>(ca, m->num_cus, s, false);
+    case form::l2_down::none: break;
+    }
+    return not_planned("l2_down");
+}
+
+static gs_status launch_l2_esp_fused(const Model *m, form::l2_esp_fused f, const ConvArgs &ca, hipStream_t s)
+{
+    switch (f) {
+    case form::l2_esp_fused::P2S_VEC: return launch_vec<F_BNACT | F_RES | POL_L2_ESP | FUSE_L2, CFG_L2_BR_P2S>(ca, m->num_cus, s, true);
+    case form::l2_esp_fused::P4_VEC:
+        GS_DIAG_STAMPED(161, "l2esp", ca, F_BNACT | F_RES | POL_L2_ESP | FUSE_L2 | F_VEC, CFG_L2_BR_P4)
+        return launch_vec<F_BNACT | F_RES | POL_L2_ESP | FUSE_L2, CFG_L2_BR_P4>(ca, m->num_cus, s, true);
+    case form::l2_esp_fused::P4: return launch_vec<F_BNACT | F_RES | POL_L2_ESP | FUSE_L2, CFG_L2_BR_P4>(ca, m->num_cus, s, false);
+    case form::l2_esp_fused::UNFUSED_P4_VEC: return launch_vec<F_BNACT | F_RES | POL_L2_ESP, CFG_L2_BR_P4>(ca, m->num_cus, s, true);
+    case form::l2_esp_fused::UNFUSED_P4: return launch_vec<F_BNACT | F_RES | POL_L2_ESP, CFG_L2_BR_P4>(ca, m->num_cus, s, false);
+    case form::l2_esp_fused::none: break;
+    }
+    return not_planned("l2_esp_fused");
+}
+
+static gs_status launch_l2_esp_last(const Model *m, form::l2_esp_last f, const ConvArgs &ca, hipStream_t s)
+{
+    switch (f) {
+    case form::l2_esp_last::P2S_VEC: return launch_vec<F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST, CFG_L2_BR_P2S>(ca, m->num_cus, s, true);
+    case form::l2_esp_last::P4_VEC:
+        GS_DIAG_STAMPED(163, "l2last", ca, F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST | F_VEC, CFG_L2_BR_P4)
+        return launch_vec<F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST, CFG_L2_BR_P4>(ca, m->num_cus, s, true);
+    case form::l2_esp_last::P4: return launch_vec<F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST, CFG_L2_BR_P4>(ca, m->num_cus, s, false);
+    case form::l2_esp_last::none: break;
+    }
+    return not_planned("l2_esp_last");
+}
+
+// (the F_BNLOAD forms: planes 64..127 of output1_cat hold output1_0 RAW, b2 is applied to the B operands on load)
+static gs_status launch_l3_reduce(const Model *m, form::l3_reduce f, const ConvArgs &ca, hipStream_t s)
+{
+    switch (f) {
+    case form::l3_reduce::BNL_P1: return launch_conv_mfma<CFG_L3_C1S_BNL_P1, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD>(ca, m->num_cus, s);
+    case form::l3_reduce::BNL:
+        GS_DIAG_STAMPED(165, "l3c1s", ca, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD, CFG_L3_C1S_BNL)
+        return launch_conv_mfma<CFG_L3_C1S_BNL, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD>(ca, m->num_cus, s);
+    case form::l3_reduce::C1S: return launch_conv_mfma<CFG_L3_C1S, F_S2PAIR | POL_L3_C1S | S2FLIP_L3>(ca, m->num_cus, s);
+    case form::l3_reduce::none: break;
+    }
+    return not_planned("l3_reduce");
+}
+
+static gs_status launch_l3_down(const Model *m, form::l3_down f, const ConvArgs &ca, hipStream_t s)
+{
+    switch (f) {
+    case form::l3_down::P1R: return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | POL_L3_DOWN | FUSE_L3 | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(ca, m->num_cus, s);
+    case form::l3_down::P2R_VEC:
+        GS_DIAG_STAMPED(164, "l3down", ca, F_BNACT | POL_L3_DOWN | FUSE_L3 | F_VEC | SKIP_L3, CFG_L3_BR_P2R)
+        return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | POL_L3_DOWN | FUSE_L3 | F_VEC | SKIP_L3>(ca, m->num_cus, s);
+    case form::l3_down::BR_VEC: return launch_conv_mfma<CFG_L3_BR, F_BNACT | POL_L3_DOWN | FUSE_L3 | F_VEC>(ca, m->num_cus, s);
+    case form::l3_down::P2F: return launch_conv_mfma<CFG_L3_BR_P2F, F_BNACT | POL_L3_DOWN | FUSE_L3>(ca, m->num_cus, s);
+    case form::l3_down::UNFUSED_BR_VEC: return launch_vec<F_BNACT | POL_L3_DOWN, CFG_L3_BR>(ca, m->num_cus, s, true);
+    case form::l3_down::UNFUSED_BR: return launch_vec<F_BNACT | POL_L3_DOWN, CFG_L3_BR>(ca, m->num_cus, s, false);
+    case form::l3_down::none: break;
+    }
+    return not_planned("l3_down");
+}
+
+// `block`: the ESP block's index (a stamp variant of -DGS_DIAG builds takes block 1)
+static gs_status launch_l3_esp_fused(const Model *m, form::l3_esp_fused f, const ConvArgs &ca, int block, hipStream_t s)
+{
+    switch (f) {
+    case form::l3_esp_fused::P1R: return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | F_RES | POL_L3_ESP | FUSE_L3 | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(ca, m->num_cus, s);
+    case form::l3_esp_fused::P2R_VEC:
+        if (block == 1) {
+            GS_DIAG_STAMPED(160, "l3esp", ca, F_BNACT | F_RES | F_VEC | POL_L3_ESP | FUSE_L3 | SKIP_L3, CFG_L3_BR_P2R)
+        }
+        return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | F_RES | F_VEC | POL_L3_ESP | FUSE_L3 | SKIP_L3>(ca, m->num_cus, s);
+    case form::l3_esp_fused::P2F: return launch_conv_mfma<CFG_L3_BR_P2F, F_BNACT | F_RES | FUSE_L3>(ca, m->num_cus, s);
+    case form::l3_esp_fused::none: break;
+    }
+    return not_planned("l3_esp_fused");
+}
+
+static gs_status launch_l3_esp_last(const Model *m, form::l3_esp_last f, const ConvArgs &ca, hipStream_t s)
+{
+    switch (f) {
+    case form::l3_esp_last::P1R: return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | F_RES | POL_L3_ESP | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(ca, m->num_cus, s);
+    case form::l3_esp_last::P2R_VEC: return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | F_RES | F_VEC | POL_L3_ESP | SKIP_L3>(ca, m->num_cus, s);   // tap rows in the halo skipped
+    case form::l3_esp_last::BR_VEC: return launch_conv_mfma<CFG_L3_BR, F_BNACT | F_RES | F_VEC | POL_L3_ESP>(ca, m->num_cus, s);
+    case form::l3_esp_last::P2: return launch_conv_mfma<CFG_L3_BR_P2, F_BNACT | F_RES>(ca, m->num_cus, s);
+    case form::l3_esp_last::none: break;
+    }
+    return not_planned("l3_esp_last");
+}
+
+// The decoder's 3x3 convolutions as plain conv_mfma launches (MFMA rows = the padded output channels, BN + PReLU in the
+// epilogue).  The shape is a property of the instantiation: the plan names it from the same CLS = Model::cp (dec_mt).
+// (Deeper operand rings and four pixels per lane were measured on the conv launch: no gain -- at twenty classes it is at 90 % of
+// what its padded matrix work allows, 20 of 32 rows.)
+template <int CLS>
+static gs_status launch_dec3(const Model *m, form::dec3 f, const ConvArgs &ca, hipStream_t s)
+{
+    switch (f) {
+    case form::dec3::MT16:
+    case form::dec3::MT32: return launch_vec<F_BNACT, dec_mt(CLS), 8, 2 * CLS, 9, 1, 1, CLS, CLS, dec_pixels(CLS), 3>(ca, m->num_cus, s, false);
+    case form::dec3::MT16_VEC:
+    case form::dec3::MT32_VEC: return launch_vec<F_BNACT, dec_mt(CLS), 8, 2 * CLS, 9, 1, 1, CLS, CLS, dec_pixels(CLS), 3>(ca, m->num_cus, s, true);
+    case form::dec3::KERNEL:
+    case form::dec3::none: break;
+    }
+    return not_planned("dec3");
+}
+
+template <int CLS>
+static gs_status launch_dec_conv(const Model *m, form::dec_conv f, const ConvArgs &ca, hipStream_t s)
+{
+    constexpr int CINP = (19 + CLS + 3) / 4 * 4;
+    switch (f) {
+    case form::dec_conv::MT16:
+    case form::dec_conv::MT32: return launch_vec<F_BNACT | POL_DEC_CONV, dec_mt(CLS), 8, CINP, 9, 1, 1, CLS, CLS, dec_pixels(CLS), 3>(ca, m->num_cus, s, false);
+    case form::dec_conv::MT16_VEC:
+    case form::dec_conv::MT32_VEC: return launch_vec<F_BNACT | POL_DEC_CONV, dec_mt(CLS), 8, CINP, 9, 1, 1, CLS, CLS, dec_pixels(CLS), 3>(ca, m->num_cus, s, true);
+    case form::dec_conv::TAIL:
+    case form::dec_conv::none: break;
+    }
+    return not_planned("dec_conv");
+}
+
 template <int CLS>
 static gs_status forward_impl(Model *m, const void *in, int in_format, int n, int H, int W, const float *mean,
                               const float *stdv, float *logits, uint8_t *mask, unsigned long long *hist, hipStream_t s,
@@ -441,6 +594,7 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
 {
     const float *wb = m->dblob;
     Launcher L{m, s, GS_OK, n};
+    const ForwardPlan plan = plan_forward(n, H, W, m->p, m->q, CLS, m->num_cus, no_vec());   // every choice of a kernel form
     const int H1 = H / 2, W1 = W / 2, H2 = H / 4, W2 = W / 4, H3 = H / 8, W3 = W / 8;
     const double px1 = (double)H1 * W1, px2 = (double)H2 * W2, px3 = (double)H3 * W3;
     m->stages.clear();
@@ -489,8 +643,7 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
     // ---- level 2 (Model.py:351-357): DownSamplerB(19,64) then p ESP blocks
     L.run(K_L2_C1S, px2 * (19 * 9 * 12 * 2), [&] {
         GS_DIAG_TRY(diag_reduce_s2(m, 2, conv_args(m->a0, wb + m->l2_0.c1, m->r2[0], nullptr, n), s, dst_));
-        ConvArgs ca = conv_args(m->a0, wb + m->l2_0.c1, m->r2[0], nullptr, n);
-        return launch_conv_mfma<CFG_L2_C1S, F_S2PAIR | POL_L2_C1S | S2FLIP_L2>(ca, m->num_cus, s);
+        return launch_l2_reduce(m, conv_args(m->a0, wb + m->l2_0.c1, m->r2[0], nullptr, n), s);
     });
     // b2 = BR(131) over cat([output1, output1_0, inp2]) (Model.py:359) never runs as a kernel: the last ESP block stores
     // only its b2-normalised form (planes 0..63 of output1_cat), the pool kernel writes planes 128..130 normalised, and
@@ -517,26 +670,12 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
         a.nout3 = nout3;
         return a;
     };
-    // small batches: 32-pixel level-2 tasks while there are at most CFG_SMALL2_WAVES of them per CU (see small3 below)
-    const bool small2 = CFG_SMALL2_WAVES > 0 && (long long)n * H2 * cdiv(W2, 64) * 2 <= (long long)m->num_cus * CFG_SMALL2_WAVES && W2 % 2 == 0 && !no_vec();
-    const bool lazy_b2 = m->p > 0;
+    const bool lazy_b2 = plan.lazy_b2;
     m->b2_lazy = lazy_b2;
     int rd2 = 0;   // index of the reduced map the next level-2 branch kernel reads
     L.run(K_L2_DOWN, px2 * (12 * 9 * 64 * 2) + (m->l2_0.fused_next ? px2 * (64 * 12 * 2) : 0), [&] {
-        ConvArgs ca = conv_args(m->r2[rd2], wb + m->l2_0.br, m->bb[0], nullptr, n);
-        // the raw output only, with or without ESP blocks behind it: b2 is applied by the consumers (p > 0: the level-3 stride-2
-        // reduce and dec2 on load; p == 0: cat_b2_kernel)
-        if (m->l2_0.fused_next) {
-            if (small2)
-                return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2, CFG_L2_BR_P2S>(with_fused(ca, m->r2[rd2 ^ 1], 12), m->num_cus, s);
-            GS_DIAG_STAMPED(162, "l2down", with_fused(ca, m->r2[rd2 ^ 1], 12), F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2 | F_VEC, CFG_L2_BR_P4)
-#if CFG_L2_DOWN_SKIP
-            if (ca.W % L2SP == 0 && !no_vec())   // tap-row chunks, tap rows in the zero halo skipped (espnet_config.h)
-                return launch_conv_mfma<CFG_L2_BR_P4S, F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2 | F_VEC | F_SKIP_PAD>(with_fused(ca, m->r2[rd2 ^ 1], 12), m->num_cus, s);
-#endif
-            return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2, CFG_L2_BR_P4>(with_fused(ca, m->r2[rd2 ^ 1], 12), m->num_cus, s);
-        }
-        return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT), CFG_L2_BR_P4>(ca, m->num_cus, s);
+        const ConvArgs ca = conv_args(m->r2[rd2], wb + m->l2_0.br, m->bb[0], nullptr, n);
+        return launch_l2_down(m, plan.l2_down, m->l2_0.fused_next ? with_fused(ca, m->r2[rd2 ^ 1], 12) : ca, s);
     });
     bool have_r2 = m->l2_0.fused_next;   // the reduced map of the next block already exists
     rd2 ^= have_r2 ? 1 : 0;
@@ -548,24 +687,13 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
         const bool fuse_next = m->l2[i].fused_next;
         if (!have_r2)
             L.run(K_L2_C1, px2 * (64 * 12 * 2), [&] {
-                ConvArgs ca = conv_args(m->bb[cur2], wb + m->l2[i].c1, m->r2[rd2], nullptr, n);
-                return launch_conv_mfma<CFG_L2_C1, POL_L2_C1>(ca, m->num_cus, s);   // 1x1: the run mapping measured no slower
+                return launch_l2_c1(m, conv_args(m->bb[cur2], wb + m->l2[i].c1, m->r2[rd2], nullptr, n), s);
             });
         L.run(K_L2_ESP, px2 * (12 * 9 * 64 * 2) + (fuse_next ? px2 * (64 * 12 * 2) : 0), [&] {
-            ConvArgs ca = conv_args(m->r2[rd2], wb + m->l2[i].br, m->bb[nxt], &m->bb[cur2], n);
-            if (last) {
-                if (small2)
-                    return launch_vec<F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST, CFG_L2_BR_P2S>(with_dual(ca, 0), m->num_cus, s);
-                GS_DIAG_STAMPED(163, "l2last", with_dual(ca, 0), F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST | F_VEC, CFG_L2_BR_P4)
-                return launch_vec<F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST, CFG_L2_BR_P4>(with_dual(ca, 0), m->num_cus, s);
-            }
-            if (fuse_next) {
-                if (small2)
-                    return launch_vec<F_BNACT | F_RES | POL_L2_ESP | FUSE_L2, CFG_L2_BR_P2S>(with_fused(ca, m->r2[rd2 ^ 1], 12), m->num_cus, s);
-                GS_DIAG_STAMPED(161, "l2esp", with_fused(ca, m->r2[rd2 ^ 1], 12), F_BNACT | F_RES | POL_L2_ESP | FUSE_L2 | F_VEC, CFG_L2_BR_P4)
-                return launch_vec<F_BNACT | F_RES | POL_L2_ESP | FUSE_L2, CFG_L2_BR_P4>(with_fused(ca, m->r2[rd2 ^ 1], 12), m->num_cus, s);
-            }
-            return launch_vec<F_BNACT | F_RES | POL_L2_ESP, CFG_L2_BR_P4>(ca, m->num_cus, s);
+            const ConvArgs ca = conv_args(m->r2[rd2], wb + m->l2[i].br, m->bb[nxt], &m->bb[cur2], n);
+            if (last)
+                return launch_l2_esp_last(m, plan.l2_esp_last, with_dual(ca, 0), s);
+            return launch_l2_esp_fused(m, plan.l2_esp_fused, fuse_next ? with_fused(ca, m->r2[rd2 ^ 1], 12) : ca, s);
         });
         have_r2 = fuse_next;
         rd2 ^= have_r2 ? 1 : 0;
@@ -573,7 +701,7 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
         if (!last)
             set_stage("level2." + std::to_string(i), m->bb[cur2], 64);
     }
-    if (!lazy_b2) {
+    if (plan.cat_b2 == form::cat_b2::KERNEL) {
         L.run(K_CAT_B2, 0, [&] {
             hipLaunchKernelGGL(cat_b2_kernel, dim3(blocks_for((long long)n * 131 * H2 * W2)), dim3(256), 0, s, view(m->bb[cur2]),
                                view(m->bb[0]), view(m->inp2), wb + m->b2, view(m->a1), n);
@@ -583,42 +711,19 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
     set_stage("b2", m->a1, 131);
 
     // ---- level 3 (Model.py:361-366)
-    // Small batches: a half-row task per SIMD does not fill the chip below 8 tiles (64 rows x 2 strips x n tasks for 1024
-    // SIMDs); with 32-pixel strips (one pixel per lane, the same accumulation chain per pixel: same bits) there are twice as
-    // many, each half as long.  Used up to one such task per wave slot (CFG_SMALL3_WAVES per CU: 8 tiles).
-    const bool small3 = (long long)n * H3 * cdiv(W3, 64) * 2 <= (long long)m->num_cus * CFG_SMALL3_WAVES && !no_vec();
     int rd3 = 0;
     L.run(K_L3_C1S, px3 * (131 * 9 * 25 * 2), [&] {
         GS_DIAG_TRY(diag_reduce_s2(m, 3, conv_args(m->a1, wb + m->l3_0.c1, m->r3[0], nullptr, n), s, dst_));
+        ConvArgs ca = conv_args(m->a1, wb + m->l3_0.c1, m->r3[0], nullptr, n);
         if (lazy_b2) {   // planes 64..127 of output1_cat hold output1_0 RAW: b2 is applied to the B operands on load
-            ConvArgs ca = conv_args(m->a1, wb + m->l3_0.c1, m->r3[0], nullptr, n);
             ca.bnl_s0 = 64 / 2;      // k-groups of two channels
             ca.bnl_s1 = 128 / 2;
-            // whole-row tasks (128 pixels) are one per wave at batch 32; below a quarter of that the row is cut into 32-pixel
-            // tasks (batch 1: 64 -> 256 tasks, 0.180 -> see profiles/r04_latency.json)
-            if ((long long)n * H3 * cdiv(W3, 128) * 4 <= (long long)m->num_cus * 8)
-                return launch_conv_mfma<CFG_L3_C1S_BNL_P1, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD>(ca, m->num_cus, s);
-            GS_DIAG_STAMPED(165, "l3c1s", ca, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD, CFG_L3_C1S_BNL)
-            return launch_conv_mfma<CFG_L3_C1S_BNL, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD>(ca, m->num_cus, s);
         }
-        return launch_conv_mfma<CFG_L3_C1S, F_S2PAIR | POL_L3_C1S | S2FLIP_L3>(conv_args(m->a1, wb + m->l3_0.c1, m->r3[0], nullptr, n), m->num_cus, s);
+        return launch_l3_reduce(m, plan.l3_reduce, ca, s);
     });
     L.run(K_L3_DOWN, px3 * (25 * 9 * 128 * 2) + (m->l3_0.fused_next ? px3 * (128 * 25 * 2) : 0), [&] {
-        ConvArgs ca = conv_args(m->r3[rd3], wb + m->l3_0.br, m->cc[0], nullptr, n);
-        if (m->l3_0.fused_next) {   // no residual here: the four-pixel vector mapping still fits with the second accumulator set
-            if (small3)
-                return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | POL_L3_DOWN | FUSE_L3 | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
-#if CFG_L3_DOWN_P2
-            if (ca.W % 2 == 0 && !no_vec()) {
-                GS_DIAG_STAMPED(164, "l3down", with_fused(ca, m->r3[rd3 ^ 1], 25), F_BNACT | POL_L3_DOWN | FUSE_L3 | F_VEC | SKIP_L3, CFG_L3_BR_P2R)
-                return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | POL_L3_DOWN | FUSE_L3 | F_VEC | SKIP_L3>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
-            }
-#endif
-            if (ca.W % 4 == 0 && !no_vec())
-                return launch_conv_mfma<CFG_L3_BR, F_BNACT | POL_L3_DOWN | FUSE_L3 | F_VEC>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
-            return launch_conv_mfma<CFG_L3_BR_P2F, F_BNACT | POL_L3_DOWN | FUSE_L3>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
-        }
-        return launch_vec<F_BNACT | POL_L3_DOWN, CFG_L3_BR>(ca, m->num_cus, s);
+        const ConvArgs ca = conv_args(m->r3[rd3], wb + m->l3_0.br, m->cc[0], nullptr, n);
+        return launch_l3_down(m, plan.l3_down, m->l3_0.fused_next ? with_fused(ca, m->r3[rd3 ^ 1], 25) : ca, s);
     });
     bool have_r3 = m->l3_0.fused_next;
     set_stage("level3_reduce", m->r3[rd3], 25);      // (debug: valid until the second ESP block overwrites the map)
@@ -630,39 +735,14 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
         const bool fuse_next = m->l3[i].fused_next;
         if (!have_r3)
             L.run(K_L3_C1, px3 * (128 * 25 * 2), [&] {
-                ConvArgs ca = conv_args(m->cc[cur3], wb + m->l3[i].c1, m->r3[rd3], nullptr, n);
-                return launch_conv_mfma<CFG_L3_C1, POL_L3_C1>(ca, m->num_cus, s);
+                return launch_l3_c1(m, conv_args(m->cc[cur3], wb + m->l3[i].c1, m->r3[rd3], nullptr, n), s);
             });
         L.run(K_L3_ESP, px3 * (25 * 9 * 128 * 2) + (fuse_next ? px3 * (128 * 25 * 2) : 0), [&] {
-            ConvArgs ca = conv_args(m->r3[rd3], wb + m->l3[i].br, m->cc[nxt], &m->cc[cur3], n);
+            const ConvArgs ca = conv_args(m->r3[rd3], wb + m->l3[i].br, m->cc[nxt], &m->cc[cur3], n);
             GS_DIAG_TRY(diag_l3_esp(m, ca, i, s, dst_));
-            if (fuse_next) {
-                if (small3)   // (one pixel per lane: a whole slot's residual fits in registers, requested a dilation ahead)
-                    return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | F_RES | POL_L3_ESP | FUSE_L3 | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
-                // Two consecutive pixels per lane, a 13-step operand ring (CFG_L3_RING), a whole slot's residual in
-                // registers.  A task is then half a row, so the 256 waves of an XCD have TWO images in flight instead of four
-                // and the reduced maps the taps re-read stay in that XCD's 4 MiB L2: beyond-L2 fetch of a launch
-                // 542 -> 296 MB, 0.1898 -> 0.1834 ms (profiles/README.md).
-                if (ca.W % 2 == 0 && !no_vec()) {
-                    if (i == 1) {
-                        GS_DIAG_STAMPED(160, "l3esp", with_fused(ca, m->r3[rd3 ^ 1], 25), F_BNACT | F_RES | F_VEC | POL_L3_ESP | FUSE_L3 | SKIP_L3, CFG_L3_BR_P2R)
-                    }
-                    return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | F_RES | F_VEC | POL_L3_ESP | FUSE_L3 | SKIP_L3>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
-                }
-                return launch_conv_mfma<CFG_L3_BR_P2F, F_BNACT | F_RES | FUSE_L3>(with_fused(ca, m->r3[rd3 ^ 1], 25), m->num_cus, s);
-            }
-            if (small3)
-                return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | F_RES | POL_L3_ESP | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(ca, m->num_cus, s);
-#if CFG_L3_LAST_P2
-            // the last (unfused) block in the half-row task shape of the fused ones, tap rows in the halo skipped
-            if (ca.W % 2 == 0 && !no_vec())
-                return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | F_RES | F_VEC | POL_L3_ESP | SKIP_L3>(ca, m->num_cus, s);
-#endif
-            // four consecutive pixels per lane and 16-byte accesses when the width allows it (0.170 ms per
-            // launch at batch 32), else the two-run mapping with its deeper ring (0.175 ms)
-            if (ca.W % 4 == 0 && !no_vec())
-                return launch_conv_mfma<CFG_L3_BR, F_BNACT | F_RES | F_VEC | POL_L3_ESP>(ca, m->num_cus, s);
-            return launch_conv_mfma<CFG_L3_BR_P2, F_BNACT | F_RES>(ca, m->num_cus, s);
+            if (fuse_next)
+                return launch_l3_esp_fused(m, plan.l3_esp_fused, with_fused(ca, m->r3[rd3 ^ 1], 25), i, s);
+            return launch_l3_esp_last(m, plan.l3_esp_last, ca, s);
         });
         have_r3 = fuse_next;
         rd3 ^= have_r3 ? 1 : 0;
@@ -729,15 +809,11 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
     if (ncls == CLS)   // (with padding planes in between the two halves are not one contiguous stage)
         set_stage("combine_t", m->tt, 2 * CLS);
     // ---- CBR(2c,c,3) + up_l2 (Model.py:373)
-    if constexpr (CLS >= 12) {
+    if constexpr (dec3_on_mfma(CLS)) {
         // many classes: the 3x3 over 2 * CLS planes is 7 200 FMAs per pixel at twenty classes -- on the matrix cores (a plain
         // conv_mfma launch, BN + PReLU in its epilogue), the deconvolution + BR as a second, small kernel
         L.run(K_DEC3, px2 * (2 * ncls * 9 * ncls * 2), [&] {
-            const ConvArgs ca = conv_args(m->tt, wb + m->wcc_mfma, m->t3, nullptr, n);
-            if constexpr (CLS <= 16)
-                return launch_vec<F_BNACT, 16, 8, 2 * CLS, 9, 1, 1, CLS, CLS, 8, 3>(ca, m->num_cus, s);
-            else
-                return launch_vec<F_BNACT, 32, 8, 2 * CLS, 9, 1, 1, CLS, CLS, 4, 3>(ca, m->num_cus, s);
+            return launch_dec3<CLS>(m, plan.dec3, conv_args(m->tt, wb + m->wcc_mfma, m->t3, nullptr, n), s);
         });
         L.run(K_DEC3, px2 * (ncls * ncls * 4 * 2), [&] {
             Dec3Args a{};
@@ -767,7 +843,7 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
     }
     set_stage("up_l2", m->ee, ncls);
     // ---- conv CBR(19+c,c,3) + classifier deconv + argmax + counts (Model.py:375-377, VisualizeResults_iou.py:128,151-155)
-    if constexpr (CLS == 5) {
+    if constexpr (dec_tail_fused(CLS)) {
         L.run(K_DEC_TAIL, px1 * ((19 + CLS) * 9 * CLS * 2) + px1 * (CLS * CLS * 4 * 2), [&] {
             DecTailArgs a{};
             a.in = m->a0c.base;
@@ -802,14 +878,7 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
         // buffer as a plain conv_mfma launch (MFMA rows = the padded output channels, BN + PReLU in its epilogue), then the
         // classifier deconvolution + argmax + counts (+ the ensemble's softmax accumulation) as a second kernel.
         L.run(K_DEC_CONV, px1 * ((19 + ncls) * 9 * ncls * 2), [&] {
-            const ConvArgs ca = conv_args(m->a0c, wb + m->wconv, m->ff, nullptr, n);
-            constexpr int CINP = (19 + CLS + 3) / 4 * 4;
-            // (deeper operand rings and four pixels per lane were measured on these launches: no gain -- at twenty classes the launch is
-            // at 90 % of what its padded matrix work allows, 20 of 32 rows)
-            if constexpr (CLS <= 16)
-                return launch_vec<F_BNACT | POL_DEC_CONV, 16, 8, CINP, 9, 1, 1, CLS, CLS, 8, 3>(ca, m->num_cus, s);
-            else
-                return launch_vec<F_BNACT | POL_DEC_CONV, 32, 8, CINP, 9, 1, 1, CLS, CLS, 4, 3>(ca, m->num_cus, s);
+            return launch_dec_conv<CLS>(m, plan.dec_conv, conv_args(m->a0c, wb + m->wconv, m->ff, nullptr, n), s);
         });
         set_stage("conv", m->ff, ncls);
         L.run(K_DEC4, px1 * (ncls * ncls * 4 * 2), [&] {
@@ -867,7 +936,7 @@ using namespace gs;
 extern "C" {
 
 const char *gs_last_error(void) { return g_err.c_str(); }
-int gs_abi_version(void) { return 7; }   // 2: lanes, block hook, detector, compositor LUT; 3: batched crop entries, detector host entry, build flags; 4: any class count 2..20 (hist is [n,classes]), batch planner, pinned-block query, overlays from the crop pipeline; 5: gs_device_fault_check, GS_ERR_DEVICE_FAULT; 6: gs_wsi_eval_windows; 7: ESPNet-C handles give class maps and counts (forward, segment_host, the crop entries with one model)
+int gs_abi_version(void) { return 8; }   // 2: lanes, block hook, detector, compositor LUT; 3: batched crop entries, detector host entry, build flags; 4: any class count 2..20 (hist is [n,classes]), batch planner, pinned-block query, overlays from the crop pipeline; 5: gs_device_fault_check, GS_ERR_DEVICE_FAULT; 6: gs_wsi_eval_windows; 7: ESPNet-C handles give class maps and counts (forward, segment_host, the crop entries with one model); 8: gs_espnet_plan_forward, gs_espnet_form_info
 gs_status gs_device_fault_check(void)
 {
     GS_HIP(hipDeviceSynchronize());
@@ -967,7 +1036,7 @@ gs_status gs_espnet_create(const float *blob, const gs_layer_desc *table, int n_
     std::unique_ptr<gs_espnet> h(new gs_espnet());
     Model &m = h->m;
     m.classes = classes;
-    m.cp = classes == 5 ? 5 : (classes + 3) / 4 * 4;
+    m.cp = padded_classes(classes);
     m.p = p;
     m.q = q;
     m.encoder_only = encoder_only != 0;
@@ -1006,8 +1075,8 @@ gs_status gs_espnet_create(const float *blob, const gs_layer_desc *table, int n_
     std::vector<float> b2f(3 * 131);
     if (!fold_bn(t, e + "b2.bn", e + "b2.act", 131, b2f.data())) return GS_ERR_INVALID;
     m.b2 = bb.push(b2f.data(), 393);
-    auto next2 = [&](int i) { return (CFG_FUSE_L2 && i < p) ? e + "level2." + std::to_string(i) : std::string(); };
-    auto next3 = [&](int i) { return ((CFG_FUSE_L3 == 2 || (CFG_FUSE_L3 == 1 && i == 0)) && i < q) ? e + "level3." + std::to_string(i) : std::string(); };
+    auto next2 = [&](int i) { return l2_c1_fused(i, p) ? e + "level2." + std::to_string(i) : std::string(); };
+    auto next3 = [&](int i) { return l3_c1_fused(i, q) ? e + "level3." + std::to_string(i) : std::string(); };
     // (lazy b2: the down-sampler has no second store, so its image carries no second BN section)
     if (!pack_block(t, bb, e + "level2_0", true, 2, m.l2_0, nullptr, 0, 0, next2(0))) return GS_ERR_INVALID;
     m.l2.resize(p);
@@ -1091,7 +1160,7 @@ gs_status gs_espnet_create(const float *blob, const gs_layer_desc *table, int n_
                 }
             m.wcc = bb.push(v.data(), v.size());
         }
-        if (cp >= 12) {   // the same convolution as a conv_mfma image: [tap][2 * cp planes][cp rows], then its folded BN + PReLU
+        if (dec3_on_mfma(cp)) {   // the same convolution as a conv_mfma image: [tap][2 * cp planes][cp rows], then its folded BN + PReLU
             m.wcc_mfma = bb.reserve(conv_wfloats(2 * cp, 9, 1, cp, cp, true));
             float *dst = bb.data.data() + m.wcc_mfma;
             for (int tap = 0; tap < 9; ++tap)
@@ -1125,7 +1194,7 @@ gs_status gs_espnet_create(const float *blob, const gs_layer_desc *table, int n_
         auto cat_ch = [&](int pl) { return pl < cp ? (pl < c ? pl : -1) : (pl - cp < 19 ? c + pl - cp : -1); };
         if (!fold_bn(t, "conv.bn", "conv.act", c, tmp.data())) return GS_ERR_INVALID;
         const std::vector<float> bn_conv = pad_bn(tmp.data(), c, 3, cp, ident);
-        if (cp != 5) {   // (five classes: dec_tail reads m.wtail, packed below)
+        if (!dec_tail_fused(cp)) {   // (five classes: dec_tail reads m.wtail, packed below)
             // the generic tail's conv_mfma image [tap][CINP planes][cp rows] + BN: CINP = 19 + cp rounded up to the k-step
             const int cinp = (19 + cp + 3) / 4 * 4;
             m.wconv = bb.reserve(conv_wfloats(cinp, 9, 1, cp, cp, true));
@@ -1144,7 +1213,7 @@ gs_status gs_espnet_create(const float *blob, const gs_layer_desc *table, int n_
             const std::vector<float> v = pad_deconv(w);
             m.wclassifier = bb.push(v.data(), v.size());
         }
-        if (cp == 5) {
+        if (dec_tail_fused(cp)) {
             // dec_tail image: A operands [ty][plane group][lane] (lane = k-group * 16 + MFMA row, row = tx*c + o),
             // then BN scale / shift / alpha of conv, then classifier.weight
             const float *wc = t.get("conv.conv.weight", {c, 19 + c, 3, 3});
@@ -1324,23 +1393,20 @@ gs_status gs_espnet_block_forward(gs_espnet *h, int kind, int level, int index, 
         GS_HIP(hipMemcpy(tmp, in, nin * sizeof(float), hipMemcpyHostToDevice));
         hipLaunchKernelGGL(pad_kernel, dim3(blocks_for((long long)nin)), dim3(256), 0, s, view(src), 0, cin, tmp);
         const PackedConv &pc = kind == 1 ? (level == 2 ? m.l2_0 : m.l3_0) : (level == 2 ? m.l2[index] : m.l3[index]);
+        // the block's reduce, then its branches in the unfused whole-row form its output width allows (forward_plan.h)
+        const ConvArgs rca = conv_args(src, wb + pc.c1, red, nullptr, 1);
+        const ConvArgs bca = conv_args(red, wb + pc.br, dst, kind == 1 ? nullptr : &src, 1);
         gs_status r;
         if (level == 2) {
-            r = kind == 1 ? launch_conv_mfma<CFG_L2_C1S, F_S2PAIR | POL_L2_C1S | S2FLIP_L2>(conv_args(src, wb + pc.c1, red, nullptr, 1), m.num_cus, s)
-                          : launch_conv_mfma<CFG_L2_C1, POL_L2_C1>(conv_args(src, wb + pc.c1, red, nullptr, 1), m.num_cus, s);
+            r = kind == 1 ? launch_l2_reduce(&m, rca, s) : launch_l2_c1(&m, rca, s);
             if (r != GS_OK) return r;
-            r = kind == 1 ? launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT), CFG_L2_BR_P4>(conv_args(red, wb + pc.br, dst, nullptr, 1), m.num_cus, s)
-                          : launch_vec<F_BNACT | F_RES | POL_L2_ESP, CFG_L2_BR_P4>(conv_args(red, wb + pc.br, dst, &src, 1), m.num_cus, s);
+            r = kind == 1 ? launch_l2_down(&m, unfused_l2_down(dst.W, no_vec()), bca, s)
+                          : launch_l2_esp_fused(&m, unfused_l2_esp(dst.W, no_vec()), bca, s);
         } else {
-            r = kind == 1 ? launch_conv_mfma<CFG_L3_C1S, F_S2PAIR | POL_L3_C1S | S2FLIP_L3>(conv_args(src, wb + pc.c1, red, nullptr, 1), m.num_cus, s)
-                          : launch_conv_mfma<CFG_L3_C1, POL_L3_C1>(conv_args(src, wb + pc.c1, red, nullptr, 1), m.num_cus, s);
+            r = kind == 1 ? launch_l3_reduce(&m, form::l3_reduce::C1S, rca, s) : launch_l3_c1(&m, rca, s);
             if (r != GS_OK) return r;
-            if (kind == 1)
-                r = launch_vec<F_BNACT | POL_L3_DOWN, CFG_L3_BR>(conv_args(red, wb + pc.br, dst, nullptr, 1), m.num_cus, s);
-            else if (dst.W % 4 == 0)
-                r = launch_conv_mfma<CFG_L3_BR, F_BNACT | F_RES | F_VEC | POL_L3_ESP>(conv_args(red, wb + pc.br, dst, &src, 1), m.num_cus, s);
-            else
-                r = launch_conv_mfma<CFG_L3_BR_P2, F_BNACT | F_RES>(conv_args(red, wb + pc.br, dst, &src, 1), m.num_cus, s);
+            r = kind == 1 ? launch_l3_down(&m, unfused_l3_down(dst.W, no_vec()), bca, s)
+                          : launch_l3_esp_last(&m, whole_row_l3_esp(dst.W, no_vec()), bca, s);
         }
         if (r != GS_OK) return r;
         hipLaunchKernelGGL(unpad_kernel, dim3(blocks_for((long long)nout)), dim3(256), 0, s, view(dst), 0, cout, tmp);
@@ -1352,6 +1418,35 @@ gs_status gs_espnet_block_forward(gs_espnet *h, int kind, int level, int index, 
     hipFree(tmp);
     m.stages.clear();   // the workspace no longer holds a forward's stages
     return rc;
+}
+
+gs_status gs_espnet_plan_forward(int n, int height, int width, int p, int q, int classes, int num_cus, int *out_forms, int cap,
+                                 int *n_out)
+{
+    GS_REQUIRE(n_out, "gs_espnet_plan_forward: null argument");
+    gs_status st = check_shape(n, height, width);
+    if (st != GS_OK) return st;
+    GS_REQUIRE(p >= 0 && q >= 0 && num_cus > 0, "gs_espnet_plan_forward: p and q must be non-negative, num_cus positive");
+    if (classes < 2 || classes > 20) {
+        set_error("gs_espnet_plan_forward: classes must be 2..20 (got %d)", classes);
+        return GS_ERR_UNSUPPORTED;
+    }
+    *n_out = kLaunchClassCount;
+    if (!out_forms)
+        return GS_OK;
+    GS_REQUIRE(cap >= kLaunchClassCount, "gs_espnet_plan_forward: %d entries needed, room for %d", kLaunchClassCount, cap);
+    plan_forward(n, height, width, p, q, padded_classes(classes), num_cus, no_vec()).codes(out_forms);
+    return GS_OK;
+}
+
+gs_status gs_espnet_form_info(int launch_class, int form, const char **name, int *pixels_per_lane)
+{
+    GS_REQUIRE(launch_class >= 0 && launch_class < kLaunchClassCount, "no launch class %d", launch_class);
+    const LaunchClassInfo &c = kLaunchClasses[launch_class];
+    GS_REQUIRE(form >= GS_FORM_NONE && form < c.n_forms, "launch class %s has no form %d", c.name, form);
+    if (name) *name = form == GS_FORM_NONE ? c.name : c.forms[form].name;   // (no form: the class itself)
+    if (pixels_per_lane) *pixels_per_lane = form == GS_FORM_NONE ? 0 : c.forms[form].pixels_per_lane;
+    return GS_OK;
 }
 
 gs_status gs_espnet_profile_enable(gs_espnet *h, int on)

@@ -4,6 +4,7 @@ the C ABI takes and exposes the hot-path calls on torch HIP tensors.
 torch is used for device memory and streams only; all arithmetic happens in libglomseg.so.
 """
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -291,6 +292,32 @@ class EspnetEngine:
             _lib.check(self.lib.gs_espnet_profile_read(self.handle, arr, 32, ctypes.byref(n)))
         return [{"name": arr[i].name.decode(), "total_ms": arr[i].total_ms, "launches": arr[i].launches,
                  "flops_per_tile": arr[i].flops_per_tile} for i in range(n.value)]
+
+
+@functools.lru_cache(maxsize=None)
+def forward_forms():
+    """The library's table of kernel forms: [(launch class name, [(form name, pixels per lane), ...]), ...] in the order of
+    the form codes (gs_espnet_form_info), read once.  Host-only: needs no GPU."""
+    lib = _lib.load()
+    table = []
+    name, ppl = ctypes.c_char_p(), ctypes.c_int()
+    while lib.gs_espnet_form_info(len(table), _lib.GS_FORM_NONE, ctypes.byref(name), ctypes.byref(ppl)) == _lib.GS_OK:
+        k, cls, forms = len(table), name.value.decode(), []
+        while lib.gs_espnet_form_info(k, len(forms), ctypes.byref(name), ctypes.byref(ppl)) == _lib.GS_OK:
+            forms.append((name.value.decode(), ppl.value))
+        table.append((cls, tuple(forms)))
+    return tuple(table)
+
+
+def plan_forward(n, height, width, p, q, classes, num_cus):
+    """{launch class name: form name}: what a forward of n tiles of height x width launches for ESPNet(classes, p, q) on a
+    device with num_cus compute units (gs_espnet_plan_forward, the planner the forward itself calls); a class that model does
+    not launch is left out.  Host-only: needs no GPU."""
+    lib = _lib.load()
+    table = forward_forms()
+    codes, count = (ctypes.c_int * len(table))(), ctypes.c_int()
+    _lib.check(lib.gs_espnet_plan_forward(n, height, width, p, q, classes, num_cus, codes, len(table), ctypes.byref(count)))
+    return {cls: forms[codes[k]][0] for k, (cls, forms) in enumerate(table) if codes[k] != _lib.GS_FORM_NONE}
 
 
 def crop_preprocess(crop_u8, mean, std, out_h, out_w, out=None):

@@ -38,7 +38,8 @@ typedef enum gs_status {
 } gs_status;
 
 const char *gs_last_error(void);
-/* ABI version, bumped on any change of a signature or of what an entry accepts (7: ESPNet-C handles give masks and counts). */
+/* ABI version, bumped on any change of a signature or of what an entry accepts (8: the forward-plan entries;
+ * 7: ESPNet-C handles give masks and counts). */
 int gs_abi_version(void);
 /* How the library was compiled: GS_BUILD_DIAG = a -DGS_DIAG experiment build (timing variants that return wrong results by
  * construction can be switched on through the environment); the product library returns 0 and reads no environment. */
@@ -316,6 +317,23 @@ gs_status gs_espnet_read_stage(gs_espnet *h, const char *stage, int image, float
  * h, w: input size (any size >= 1 for kind 0; even for kind 1).  Runs the plain (unfused) kernels of the block. */
 gs_status gs_espnet_block_forward(gs_espnet *h, int kind, int level, int index, const float *in, int height, int width,
                                   float *out);
+
+/* Test hook: the kernel-form plan of a forward, as a host-only function (no handle, no device work; csrc/forward_plan.h).
+ * A forward runs more than one kernel form per layer: per LAUNCH CLASS (the level-2 down-sampler's branches, the last level-3
+ * ESP block, the decoder's 3x3, ...) it picks a FORM from the batch size, the tile size, the depths, the class count and the
+ * device's CU count.  gs_espnet_plan_forward reports what a forward of n tiles of height x width would launch for
+ * ESPNet(classes, p, q) on a device with num_cus compute units: out_forms gets one form code per launch class (*n_out of them;
+ * cap counts ints; with out_forms == NULL only the count is reported), GS_FORM_NONE for a class that model does not launch.
+ * It is the function the forward itself calls, and it refuses what the forward refuses: n <= 0, sizes that are no positive
+ * multiples of 8, classes outside 2..GS_MAX_CLASSES.  (An ESPNet-C handle stops before the decoder classes.)
+ * gs_espnet_form_info enumerates the table behind the codes: of form f of launch class k its name and the pixels per lane of
+ * its vector pixel mapping -- such a form is only planned when the class's output width is a multiple of that figure; 0 for a
+ * form without one -- and with form == GS_FORM_NONE the name of the class itself; GS_ERR_INVALID past the last class or form.
+ * The strings are static.  ABI 8. */
+#define GS_FORM_NONE (-1)
+gs_status gs_espnet_plan_forward(int n, int height, int width, int p, int q, int classes, int num_cus, int *out_forms, int cap,
+                                 int *n_out);
+gs_status gs_espnet_form_info(int launch_class, int form, const char **name, int *pixels_per_lane);
 
 /* Per-kernel timing with HIP events recorded on the launch stream.  While enabled every kernel of
  * gs_espnet_forward is bracketed by an event pair; gs_espnet_profile_read synchronises and

@@ -1,18 +1,22 @@
 """Every kernel form forward_impl (csrc/espnet.hip) can pick, checked against a float64 reference.
 
-forward_impl does not run one kernel per layer: per launch it picks a conv_mfma_kernel instantiation from the batch size,
-the tile size and the device's CU count.  forms() restates that choice.  test_dispatch_tripwire holds the restatement to
-the source text, test_cases_cover_every_form makes the GPU cases reach every form forms() can return, and each GPU case
-checks three tiles of its batch -- every stage the engine still holds after the forward, the logits, the mask and the
-counts -- against oracle/espnet_torch_port.py run in float64.
+forward_impl does not run one kernel per layer: per launch class it runs the form that plan_forward (csrc/forward_plan.h)
+picks from the batch size, the tile size and the device's CU count.  The tests ask the library for that plan
+(engine.plan_forward: gs_espnet_plan_forward, the function the forward itself calls): CASES holds known answers for it,
+written by hand; test_cases_cover_every_form makes the GPU cases reach every form a sweep of the planner returns;
+test_vector_forms_fit_the_width holds the one planner mistake that would become an out-of-bounds access on a card; and each
+GPU case checks three tiles of its batch -- every stage the engine still holds after the forward, the logits, the mask and
+the counts -- against oracle/espnet_torch_port.py run in float64.
 
 One bound per stage: max|got - ref64| <= tau * max(1, max|ref64|).  test_bounds_discriminate shows on the CPU that the
 fp32 C oracle passes them on every case's shape, and that they reject a 1e-4 change of one element in a stage's last
 column, a zeroed d16 tap row and a dropped K-tail channel.
 """
+import ctypes
 import os
 import re
 from collections import namedtuple
+from functools import lru_cache
 
 import numpy as np
 import pytest
@@ -23,8 +27,9 @@ from test_gpu_parity import DEC_STAGE_TOL, ENC_STAGE_TOL, LOGIT_TOL
 CSRC = os.path.join(REPO, "glomeruli_segmentation_amd", "csrc")
 RANDOM_MEAN_STD = ((120.0, 130.0, 110.0), (60.0, 55.0, 70.0))
 
-# ---------------------------------------------------------------------------------------------- the dispatch, restated
-# the shipped defaults of espnet_config.h the dispatch reads (test_dispatch_tripwire pins each one)
+# ---------------------------------------------------------------------------------------------- the plan
+# the shipped defaults of espnet_config.h the planner reads (test_dispatch_tripwire pins each one): CASES and
+# UNREACHABLE_AT_DEFAULTS are answers for these values
 CONFIG = {"CFG_SMALL2_WAVES": 4, "CFG_SMALL3_WAVES": 8, "CFG_L3_DOWN_P2": 1, "CFG_L3_LAST_P2": 1,
           "CFG_L2_DOWN_SKIP": 1, "CFG_FUSE_L2": 1, "CFG_FUSE_L3": 2}
 L2SP = 4    # `constexpr int L2SP` there: pixels per lane of the level-2 branch kernels
@@ -32,70 +37,40 @@ L2SP = 4    # `constexpr int L2SP` there: pixels per lane of the level-2 branch 
 DELETED = ("F_EPI_PIPE", "CFG_EPI_SPLIT", "CFG_EPI_PRIO", "CFG_EPI_PRELOAD", "CFG_REFILL_MID", "CFG_L3_W16",
            "CFG_L3_FUSE_P4", "CFG_AGL_", "CFG_SKIP_PAD_L2", "CFG_RES_RING_DIV", "CFG_RES_TOP", "CFG_L2_MINW", "CFG_LAZY_B2",
            "CFG_L2_C1S_REV", "rev_n", "F_XMERGE", "wconv_xm")
-# pixels per lane of the configurations whose vector mapping the width decides (the 9th template argument)
-PIXELS_PER_LANE = {"CFG_L2_BR_P4": "L2SP", "CFG_L2_BR_P4S": "L2SP", "CFG_L2_BR_P2S": "2", "CFG_L3_BR": "4",
-                   "CFG_L3_BR_P2R": "2"}
+# the forms the library enumerates and no shape reaches with the shipped defaults, each with the switch that keeps it away
+# (found by the sweep of reachable_forms; test_every_enumerated_form_is_accounted_for)
+UNREACHABLE_AT_DEFAULTS = {
+    ("l2_down", "CFG_L2_BR_P4+F_VEC"): "CFG_L2_DOWN_SKIP = 1 takes every width that is a multiple of four first",
+    ("l2_esp_fused", "unfused CFG_L2_BR_P4+F_VEC"): "CFG_FUSE_L2 = 1: every block but the last computes the next 1x1 (the block hook runs it)",
+    ("l2_esp_fused", "unfused CFG_L2_BR_P4"): "CFG_FUSE_L2 = 1 (the block hook runs it)",
+    ("l3_down", "CFG_L3_BR+F_VEC"): "CFG_L3_DOWN_P2 = 1 takes every even width first",
+    ("l3_esp_last", "CFG_L3_BR+F_VEC"): "CFG_L3_LAST_P2 = 1 takes every even width first (the block hook runs it)",
+    ("dec_conv", "MFMA MT32"): "no switch: tile widths are multiples of 8, so W/2 is always a multiple of the four pixels per lane "
+                               "(GS_NO_VEC of a -DGS_DIAG build runs it)",
+}
 
 
-def cdiv(a, b):
-    return -(-a // b)
+def plan(n, H, W, p, q, classes, num_cus):
+    """launch class -> the form a forward runs for it, from the library's planner"""
+    from glomeruli_segmentation_amd.engine import plan_forward
+    return plan_forward(n, H, W, p, q, classes, num_cus)
+
+
+@lru_cache(maxsize=None)
+def form_table():
+    """{launch class: {form name: pixels per lane}} as the library enumerates it"""
+    from glomeruli_segmentation_amd.engine import forward_forms
+    return {cls: dict(forms) for cls, forms in forward_forms()}
 
 
 def padded_classes(classes):
-    return 5 if classes == 5 else cdiv(classes, 4) * 4                                  # Model::cp, espnet.hip:972
+    """Model::cp, for engine_stages: the class planes the decoder's stages are stored with"""
+    return 5 if classes == 5 else -(-classes // 4) * 4
 
 
-def forms(n, H, W, p, q, classes, num_cus):
-    """launch class -> the form forward_impl runs for it (espnet.hip:529-805).  "+F_VEC" is the vector pixel mapping;
-    launch_vec (espnet.hip:48-54) takes it when the output width is a multiple of the form's pixels per lane."""
-    small2_waves, small3_waves, l2sp = CONFIG["CFG_SMALL2_WAVES"], CONFIG["CFG_SMALL3_WAVES"], L2SP
-    H2, W2, H3, W3, W1 = H // 4, W // 4, H // 8, W // 8, W // 2
-
-    def vec(ok):
-        return "+F_VEC" if ok else ""
-    f = {}
-    small2 = n * H2 * cdiv(W2, 64) * 2 <= num_cus * small2_waves and W2 % 2 == 0        # :529
-    if p > 0:   # lazy b2 (:530); the down-sampler and every ESP block but the last compute the next 1x1 reduce
-        if small2:
-            f["l2_down"] = "CFG_L2_BR_P2S+F_VEC"                                        # :538-539
-        elif W2 % l2sp == 0:
-            f["l2_down"] = "CFG_L2_BR_P4S+F_VEC+F_SKIP_PAD"                             # :541-543
-        else:
-            f["l2_down"] = "CFG_L2_BR_P4"                                               # :545
-        esp = "CFG_L2_BR_P2S+F_VEC" if small2 else "CFG_L2_BR_P4" + vec(W2 % l2sp == 0)  # :564-574
-        if p > 1:
-            f["l2_esp_fused"] = esp
-        f["l2_esp_last"] = esp
-        f["l3_reduce"] = ("CFG_L3_C1S_BNL_P1" if n * H3 * cdiv(W3, 128) * 4 <= num_cus * 8     # :607-610
-                          else "CFG_L3_C1S_BNL")
-    else:       # p = 0: nothing to fuse into; b2 runs as a kernel of its own (:584-589)
-        f["l2_down"] = "unfused CFG_L2_BR_P4" + vec(W2 % l2sp == 0)                     # :547
-        f["cat_b2"] = "cat_b2_kernel"
-        f["l3_reduce"] = "CFG_L3_C1S"                                                   # :612
-    small3 = n * H3 * cdiv(W3, 64) * 2 <= num_cus * small3_waves                        # :597
-    if q > 0:
-        fused = "CFG_L3_BR_P1R" if small3 else "CFG_L3_BR_P2R+F_VEC" if W3 % 2 == 0 else "CFG_L3_BR_P2F"
-        f["l3_down"] = fused                                                            # :617-627
-        if q > 1:
-            f["l3_esp_fused"] = fused                                                   # :647-660
-        f["l3_esp_last"] = ("CFG_L3_BR_P1R" if small3 else "CFG_L3_BR_P2R+F_VEC" if W3 % 2 == 0   # :662-673
-                            else "CFG_L3_BR_P2")
-    else:
-        f["l3_down"] = "unfused CFG_L3_BR" + vec(W3 % 4 == 0)                           # :629
-    cp = padded_classes(classes)
-    if cp < 12:
-        f["dec3"] = "dec3_kernel"                                                       # :744-757
-    elif cp <= 16:
-        f["dec3"] = "MFMA MT16" + vec(W2 % 8 == 0)                                      # :728-729
-    else:
-        f["dec3"] = "MFMA MT32" + vec(W2 % 4 == 0)                                      # :730-731
-    if cp == 5:
-        f["dec_conv"] = "dec_tail_kernel"                                               # :761-790
-    elif cp <= 16:
-        f["dec_conv"] = "MFMA MT16" + vec(W1 % 8 == 0)                                  # :800-801
-    else:
-        f["dec_conv"] = "MFMA MT32" + vec(W1 % 4 == 0)                                  # :802-803
-    return f
+def output_width(launch_class, W):
+    """the width of the activation a launch class writes: level 2 and dec3 at 1/4, level 3 at 1/8, the decoder conv at 1/2"""
+    return W // 2 if launch_class == "dec_conv" else W // 8 if launch_class.startswith("l3_") else W // 4
 
 
 def edges(H, W):
@@ -109,90 +84,20 @@ def edges(H, W):
     return out
 
 
-# every conv_mfma launch site of forward_impl in source order: its configuration, plus F_VEC / F_SKIP_PAD where its flags
-# name them ("launch_vec": the vector mapping is chosen from the width, espnet.hip:48-54)
-LAUNCH_SITES = [
-    "CFG_L2_C1S",                                                                                   # :501
-    "launch_vec CFG_L2_BR_P2S", "CFG_L2_BR_P4S+F_VEC+F_SKIP_PAD", "launch_vec CFG_L2_BR_P4",        # :539-545
-    "launch_vec CFG_L2_BR_P4",                                                                      # :547
-    "CFG_L2_C1",                                                                                    # :560
-    "launch_vec CFG_L2_BR_P2S", "launch_vec CFG_L2_BR_P4",                                          # :566-568
-    "launch_vec CFG_L2_BR_P2S", "launch_vec CFG_L2_BR_P4", "launch_vec CFG_L2_BR_P4",               # :572-576
-    "CFG_L3_C1S_BNL_P1", "CFG_L3_C1S_BNL", "CFG_L3_C1S",                                            # :608-612
-    "CFG_L3_BR_P1R", "CFG_L3_BR_P2R+F_VEC", "CFG_L3_BR+F_VEC", "CFG_L3_BR_P2F",                     # :618-627
-    "launch_vec CFG_L3_BR",                                                                         # :629
-    "CFG_L3_C1",                                                                                    # :642
-    "CFG_L3_BR_P1R", "CFG_L3_BR_P2R+F_VEC", "CFG_L3_BR_P2F",                                        # :649-660
-    "CFG_L3_BR_P1R", "CFG_L3_BR_P2R+F_VEC", "CFG_L3_BR+F_VEC", "CFG_L3_BR_P2",                      # :663-673
-    "launch_vec 16, 8, 2 * CLS, 9, 1, 1, CLS, CLS, 8, 3", "launch_vec 32, 8, 2 * CLS, 9, 1, 1, CLS, CLS, 4, 3",  # :729-731
-    "launch_vec 16, 8, CINP, 9, 1, 1, CLS, CLS, 8, 3", "launch_vec 32, 8, CINP, 9, 1, 1, CLS, CLS, 4, 3",        # :801-803
-]
-
-# the predicates forms() restates, as espnet.hip spells them (whitespace aside), and how often each occurs there
-PREDICATES = [
-    ("static constexpr bool no_vec() { return false; }", 1),                                        # :42
-    ("if (ca.W % cfg[8] == 0 && !no_vec())", 1),                                                    # :51
-    ("a.H = out.H; a.W = out.W;", 1),                                                               # :420-421
-    ("const bool small2 = CFG_SMALL2_WAVES > 0 && (long long)n * H2 * cdiv(W2, 64) * 2 <= "
-     "(long long)m->num_cus * CFG_SMALL2_WAVES && W2 % 2 == 0 && !no_vec();", 1),                   # :529
-    ("const bool lazy_b2 = m->p > 0;", 2),                                                          # :314, :530
-    ("if (m->l2_0.fused_next) {", 1),                                                               # :537
-    ("if (!lazy_b2) { L.run(K_CAT_B2, 0, [&] {", 1),                                                # :584-585
-    ("if (ca.W % L2SP == 0 && !no_vec())", 1),                                                      # :542
-    ("const bool small3 = (long long)n * H3 * cdiv(W3, 64) * 2 <= (long long)m->num_cus * CFG_SMALL3_WAVES "
-     "&& !no_vec();", 1),                                                                           # :597
-    ("if ((long long)n * H3 * cdiv(W3, 128) * 4 <= (long long)m->num_cus * 8)", 1),                 # :607
-    ("if (ca.W % 2 == 0 && !no_vec())", 3),                                                         # :620, :654, :666
-    ("if (ca.W % 4 == 0 && !no_vec())", 2),                                                         # :625, :671
-    ("if constexpr (CLS >= 12)", 1),                                                                # :723
-    ("if constexpr (CLS <= 16)", 2),                                                                # :728, :800
-    ("if constexpr (CLS == 5)", 1),                                                                 # :761
-    ("m.cp = classes == 5 ? 5 : (classes + 3) / 4 * 4;", 1),                                        # :972
-    ('auto next2 = [&](int i) { return (CFG_FUSE_L2 && i < p) ? e + "level2." + std::to_string(i) : std::string(); };',
-     1),                                                                                            # :1011
-    ('auto next3 = [&](int i) { return ((CFG_FUSE_L3 == 2 || (CFG_FUSE_L3 == 1 && i == 0)) && i < q) ? e + "level3." + '
-     'std::to_string(i) : std::string(); };', 1),                                                   # :1012
-]
-
-
-def _flat(text):
-    return " ".join(text.split())
-
-
 def _read(name):
     with open(os.path.join(CSRC, name)) as fh:
         return fh.read()
 
 
-def launch_sites(body):
-    out = []
-    for m in re.finditer(r"launch_(conv_mfma|vec)<(.*?)>\(", _flat(body)):
-        if m.group(1) == "vec":
-            out.append("launch_vec " + m.group(2).split(", ", 1)[1])
-        else:
-            cfg, flags = m.group(2).split(", ", 1)
-            out.append(cfg + "".join("+" + f for f in ("F_VEC", "F_SKIP_PAD") if re.search(r"\b%s\b" % f, flags)))
-    return out
-
-
 def test_dispatch_tripwire():
-    """forms() restates the dispatch as the source reads today.  A changed predicate, launch site or default fails here,
-    so that the restatement and the GPU cases are updated with it instead of silently losing coverage."""
-    src = _read("espnet.hip")
-    flat = _flat(src)
-    for text, count in PREDICATES:
-        assert flat.count(_flat(text)) == count, text
-    body = src[src.index("static gs_status forward_impl("):src.index("static gs_status forward_any(")]
-    assert launch_sites(body) == LAUNCH_SITES
+    """CASES and UNREACHABLE_AT_DEFAULTS are answers for the shipped defaults: a changed default fails here, so that they are
+    revisited with it.  Deleted switches stay deleted, and every switch left is documented."""
     cfg = _read("espnet_config.h")
     for name, value in CONFIG.items():
         m = re.search(r"#ifndef %s\n#define %s (\S+)" % (name, name), cfg)
         assert m and m.group(1) == str(value), name
     m = re.search(r"constexpr int L2SP = (\d+);", cfg)
     assert m and int(m.group(1)) == L2SP
-    for name, p in PIXELS_PER_LANE.items():
-        m = re.search(r"#define %s\s+([^/\n]+)" % name, cfg)
-        assert m and m.group(1).split(",")[8].strip() == p, name
     # the switches that lost their A/B stay deleted ...
     sources = [f for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".hip", ".inc", ".cpp", ".cu", ".txt"))]
     assert len(sources) >= 10
@@ -253,21 +158,34 @@ CASES = [
 def batch_for(case, num_cus):
     """the smallest batch whose launches take the case's target forms on a device with num_cus CUs"""
     for n in range(1, 8 * num_cus + 1):
-        f = forms(n, case.H, case.W, case.p, case.q, case.classes, num_cus)
+        f = plan(n, case.H, case.W, case.p, case.q, case.classes, num_cus)
         if all(f.get(k) == v for k, v in case.targets.items()):
             return n
     raise AssertionError("case %s: no batch reaches %s on %d CUs" % (case.name, case.targets, num_cus))
 
 
-def reachable_forms(num_cus):
-    """every (launch class, form) forms() returns at legal tile sizes (multiples of 8), depths and class counts"""
-    out = set()
+SWEEP_DEPTHS = ((0, 0), (0, 1), (0, 2), (1, 0), (1, 1), (2, 2), (2, 8), (3, 0))
+SWEEP_CLASSES = (2, 5, 7, 12, 16, 20)
+
+
+@lru_cache(maxsize=None)
+def sweep(num_cus):
+    """[(W, plan)] at legal tile sizes (multiples of 8), depths and class counts"""
+    out = []
     for n in (1, 2, 4, 9, 16, 21, 32):
         for H in (8, 136, 264, 512):
             for W in range(8, 1048, 8):
-                for p, q in ((0, 0), (0, 1), (0, 2), (1, 0), (1, 1), (2, 2), (2, 8), (3, 0)):
-                    for classes in (2, 5, 7, 12, 16, 20):
-                        out.update(forms(n, H, W, p, q, classes, num_cus).items())
+                for p, q in SWEEP_DEPTHS:
+                    for classes in SWEEP_CLASSES:
+                        out.append((W, plan(n, H, W, p, q, classes, num_cus)))
+    return out
+
+
+def reachable_forms(num_cus):
+    """every (launch class, form) the planner returns over the sweep"""
+    out = set()
+    for _, f in sweep(num_cus):
+        out.update(f.items())
     return out
 
 
@@ -280,9 +198,72 @@ def test_case_batches_at_256_cus():
 def test_cases_cover_every_form():
     hit = set()
     for c in CASES:
-        hit.update(forms(batch_for(c, 256), c.H, c.W, c.p, c.q, c.classes, 256).items())
+        hit.update(plan(batch_for(c, 256), c.H, c.W, c.p, c.q, c.classes, 256).items())
     every = reachable_forms(256)
     assert hit == every, ("not covered: %s" % sorted(every - hit), "not reachable: %s" % sorted(hit - every))
+
+
+def test_vector_forms_fit_the_width():
+    """A form with a vector pixel mapping (pixels per lane P > 0 in the library's table) is planned only when its launch
+    class's output width is a multiple of P: lanes of such a kernel store P pixels at once, so anything else writes past a
+    row.  Over the sweep, and over every width 8..1040 at one tile and at 32."""
+    table = form_table()
+    plans = list(sweep(256))
+    for n in (1, 32):
+        for W in range(8, 1048, 8):
+            for p, q in ((0, 0), (2, 8)):
+                for classes in (5, 16, 20):
+                    plans.append((W, plan(n, 512, W, p, q, classes, 256)))
+    vector = 0
+    for W, f in plans:
+        for cls, form in f.items():
+            P = table[cls][form]
+            assert P >= 0
+            if P:
+                vector += 1
+                assert output_width(cls, W) % P == 0, (cls, form, W, P)
+    assert vector > len(plans)      # (the check is not vacuous: most plans hold several vector forms)
+    # every form named "+F_VEC" reports its P, and no other form reports one
+    for cls, forms in table.items():
+        for form, P in forms.items():
+            assert (P > 0) == ("+F_VEC" in form), (cls, form, P)
+
+
+def test_every_enumerated_form_is_accounted_for():
+    """every (launch class, form) of the library's table is reached by the sweep or pinned, with the switch that gates it, in
+    UNREACHABLE_AT_DEFAULTS -- and nothing pinned there is reachable"""
+    enumerated = {(cls, form) for cls, forms in form_table().items() for form in forms}
+    assert {cls for cls, _ in enumerated} == {"l2_down", "l2_esp_fused", "l2_esp_last", "cat_b2", "l3_reduce", "l3_down",
+                                              "l3_esp_fused", "l3_esp_last", "dec3", "dec_conv"}
+    reached = reachable_forms(256)
+    assert reached <= enumerated, sorted(reached - enumerated)
+    assert enumerated - reached == set(UNREACHABLE_AT_DEFAULTS), sorted((enumerated - reached) ^ set(UNREACHABLE_AT_DEFAULTS))
+
+
+def test_plan_refuses_bad_arguments():
+    """the entry applies the forward's own rules: a positive batch, sizes that are positive multiples of 8, 2..20 classes"""
+    from glomeruli_segmentation_amd import _lib
+    lib = _lib.load()
+    count = ctypes.c_int()
+
+    def status(n=1, H=512, W=1024, p=2, q=8, classes=5, num_cus=256):
+        return lib.gs_espnet_plan_forward(n, H, W, p, q, classes, num_cus, None, 0, ctypes.byref(count))
+    assert status() == _lib.GS_OK and count.value == len(form_table()) == 10
+    for bad in ({"n": 0}, {"n": -1}, {"H": 0}, {"W": 0}, {"H": 4}, {"H": 508}, {"W": 1028}, {"W": 1001}, {"H": -8},
+                {"classes": 1}, {"classes": 21}, {"classes": 0}, {"p": -1}, {"q": -1}, {"num_cus": 0}):
+        assert status(**bad) != _lib.GS_OK, bad
+        assert lib.gs_last_error()
+    for ok in ({"classes": 2}, {"classes": 20}, {"H": 8, "W": 8}, {"p": 0, "q": 0}):
+        assert status(**ok) == _lib.GS_OK, ok
+    codes = (ctypes.c_int * 10)()
+    assert lib.gs_espnet_plan_forward(1, 512, 1024, 2, 8, 5, 256, codes, 9, ctypes.byref(count)) != _lib.GS_OK      # too little room
+    assert lib.gs_espnet_plan_forward(1, 512, 1024, 2, 8, 5, 256, codes, 10, ctypes.byref(count)) == _lib.GS_OK
+    # the enumeration ends with GS_ERR_INVALID
+    name, P = ctypes.c_char_p(), ctypes.c_int()
+    for k, f in ((10, 0), (10, -1), (-1, 0), (0, -2), (3, 1)):                            # (cat_b2, class 3, has one form)
+        assert lib.gs_espnet_form_info(k, f, ctypes.byref(name), ctypes.byref(P)) == 1, (k, f)
+    assert lib.gs_espnet_form_info(3, 0, ctypes.byref(name), ctypes.byref(P)) == _lib.GS_OK and name.value == b"cat_b2_kernel"
+    assert lib.gs_espnet_form_info(3, -1, ctypes.byref(name), ctypes.byref(P)) == _lib.GS_OK and name.value == b"cat_b2"
 
 
 def case_weights(case):
@@ -400,7 +381,7 @@ def test_kernel_form_against_float64(case):
     assert torch.cuda.is_available(), "the gpu-marked tests need a HIP device"
     num_cus = torch.cuda.get_device_properties(0).multi_processor_count
     n = batch_for(case, num_cus)
-    hit = forms(n, case.H, case.W, case.p, case.q, case.classes, num_cus)
+    hit = plan(n, case.H, case.W, case.p, case.q, case.classes, num_cus)
     assert all(hit[k] == v for k, v in case.targets.items()) and case.edges <= edges(case.H, case.W)
     sd, mean, std = case_weights(case)
     tiles = np.stack([case_tile(case, k) for k in range(n)])
