@@ -14,12 +14,163 @@
 namespace gs {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned nhwc_u4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------
-// conv2d NHWC: GEMM-M = output pixels (32 per wave), GEMM-N = output channels (32 per wave, on the
-// lanes, so NHWC stores are 128-byte rows), GEMM-K = (ky,kx,cin) two at a time.
-// (ConvNhwcArgs: gs_internal.h)
+// conv2d NHWC on the fp32 matrix cores (ConvNhwcArgs: gs_internal.h).  GEMM-M = output pixels, GEMM-N = output channels
+// (on the lanes, so NHWC stores are 128-byte rows), GEMM-K = (ky, kx, cin).  Four kernels: a generic one (one 32 x 32
+// MFMA tile per wave, any shape) and three that share a 64-pixel x 64-channel wave tile -- its prologue, operand loads
+// and epilogue are the helpers below -- and differ in how they walk K.
 
+// Whole tensors sit behind buffer descriptors: a lane with nothing to read uses this byte offset, which is beyond any
+// descriptor (and stays beyond it with a chunk stride added), and gets 0.
+constexpr int NHWC_OOB = 0x7ffffff0;
+
+// One 16-byte buffer load as four floats.
+static __device__ __forceinline__ void nhwc_load4(__amdgpu_buffer_rsrc_t rsrc, int off, float *f)
+{
+    const nhwc_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
+    // through named scalars: with this toolchain a bit_cast straight from v[i] reads element 0
+    const unsigned e0 = v[0], e1 = v[1], e2 = v[2], e3 = v[3];
+    f[0] = __builtin_bit_cast(float, e0), f[1] = __builtin_bit_cast(float, e1);
+    f[2] = __builtin_bit_cast(float, e2), f[3] = __builtin_bit_cast(float, e3);
+}
+static __device__ __forceinline__ float nhwc_load1(__amdgpu_buffer_rsrc_t rsrc, int off)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0));
+}
+
+// What a wave of the 64 x 64 kernels knows before it walks K: a workgroup is four waves along the pixel axis, lane
+// 32 * kq + r holds A row r (pixel pix0 + 32 t + r of pixel tile t) and B column r (channel co0 + 32 u + r of channel
+// tile u) of k-group kq.
+struct NhwcTile {
+    int r, kq;
+    long long npix, pix0;
+    int co0;
+    __amdgpu_buffer_rsrc_t rin, rw;   // the whole input / weight tensor
+    int ox[2], oy[2];                 // output position of the lane's pixel, per pixel tile
+    long long ibase[2];               // image * h
+    bool pv[2];                       // pixel inside the output
+    bool cv[2];                       // channel inside cout, per channel tile
+
+    // false: the wave has no pixels
+    __device__ __forceinline__ bool init(const ConvNhwcArgs &a)
+    {
+        const int lane = threadIdx.x & 63;
+        const int wid = threadIdx.x >> 6;
+        r = lane & 31, kq = lane >> 5;
+        npix = (long long)a.n * a.ho * a.wo;
+        pix0 = ((long long)blockIdx.x * 4 + wid) * 64;
+        co0 = blockIdx.y * 64;
+        if (pix0 >= npix)
+            return false;
+        const unsigned in_bytes = (unsigned)min((long long)a.n * a.h * a.w_ * a.cin * 4, (long long)0x7fffffff);
+        const unsigned w_bytes = (unsigned)((long long)a.kh * a.kw * a.cin * a.cout * 4);
+        rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.in), 0, in_bytes, 0x00020000);
+        rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.w), 0, w_bytes, 0x00020000);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const long long pix = pix0 + t * 32 + r;
+            pv[t] = pix < npix;
+            const long long pc = pv[t] ? pix : 0;
+            ox[t] = (int)(pc % a.wo);
+            oy[t] = (int)((pc / a.wo) % a.ho);
+            ibase[t] = (pc / ((long long)a.wo * a.ho)) * a.h;
+        }
+        cv[0] = co0 + r < a.cout;
+        cv[1] = co0 + 32 + r < a.cout;
+        return true;
+    }
+};
+
+// Bias, ReLU and the guarded NHWC store of NT pixel tiles x NU channel tiles of 32 x 32 accumulators.
+// D: column = lane & 31 (channel), row = (reg & 3) + 8 * (reg >> 2) + 4 * kq (pixel)
+template <int NT, int NU>
+static __device__ __forceinline__ void nhwc_epilogue(const ConvNhwcArgs &a, const NhwcTile &T, const f32x16 (&acc)[NT][NU])
+{
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+        const int co = T.co0 + 32 * u + T.r;
+        if (co >= a.cout)
+            continue;
+        const float b = a.bias ? a.bias[co] : 0.0f;
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const long long p = T.pix0 + t * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * T.kq;
+                if (p < T.npix) {
+                    float v = acc[t][u][reg] + b;
+                    if (a.relu)
+                        v = fmaxf(v, 0.0f);
+                    a.out[p * a.cout + co] = v;
+                }
+            }
+    }
+}
+
+// Weights of one 8-channel chunk.  WP4: pre-packed [k / 4][cout][4] (k = (tap, input channel) flattened;
+// conv2d_nhwc_pack4), so that the four k-steps of a lane's channel come with ONE 16-byte load instead of four dword loads
+// from four weight rows (10 -> 4 vector-memory instructions per 16 MFMAs); otherwise TensorFlow's [kh,kw,cin,cout] as the
+// public gs_conv2d_nhwc takes it.  Handles that own their weights (gs_detector) pack them once.
+// Byte offset of the lane's first weight of the chunk that starts at k0 (a multiple of 8; k-group kq takes k0 + 4 kq ..),
+// and the bytes between consecutive chunks: the offset is linear in the chunk in both layouts.
+template <bool WP4>
+static __device__ __forceinline__ int nhwc_w_off(const ConvNhwcArgs &a, const NhwcTile &T, int k0)
+{
+    return WP4 ? ((k0 / 4 + T.kq) * a.cout + T.co0 + T.r) * 16 : ((k0 + 4 * T.kq) * a.cout + T.co0 + T.r) * 4;
+}
+template <bool WP4>
+static __device__ __forceinline__ int nhwc_w_step(const ConvNhwcArgs &a)
+{
+    return WP4 ? 2 * a.cout * 16 : 8 * a.cout * 4;
+}
+// b[channel tile][k-step] from offset `off` (beyond the last chunk it leaves the descriptor: the loads return zeros)
+template <bool WP4>
+static __device__ __forceinline__ void nhwc_fetch_w(const ConvNhwcArgs &a, const NhwcTile &T, int off, float (&b)[2][4])
+{
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        if (WP4) {
+            nhwc_load4(T.rw, T.cv[u] ? off + 32 * u * 16 : NHWC_OOB, b[u]);
+            continue;
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            b[u][s] = nhwc_load1(T.rw, T.cv[u] ? off + (s * a.cout + 32 * u) * 4 : NHWC_OOB);
+    }
+}
+
+// Tap iterator of the kernels that walk K tap by tap.  Everything that depends on the tap -- the two input positions,
+// their validity, the byte offset of the lane's first activation -- is computed once per tap; inside a tap a fetch only
+// adds constant strides (no divisions, no 64-bit address arithmetic per chunk: with those in every fetch the VALU work
+// beside 16 MFMAs held the tiled kernel at 46 % of the matrix peak).
+struct NhwcTapIter {
+    int ky = 0, kx = 0, tap = 0;
+    int aoff[2];   // per pixel tile: byte offset of channel 4 kq at the tap's input position, NHWC_OOB outside the image
+
+    __device__ __forceinline__ void set_tap(const ConvNhwcArgs &a, const NhwcTile &T)
+    {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int iy = T.oy[t] * a.stride - a.pad + ky, ix = T.ox[t] * a.stride - a.pad + kx;
+            const bool ok = T.pv[t] && iy >= 0 && iy < a.h && ix >= 0 && ix < a.w_;
+            aoff[t] = ok ? (int)((((T.ibase[t] + iy) * a.w_ + ix) * a.cin + 4 * T.kq) * 4) : NHWC_OOB;
+        }
+    }
+    __device__ __forceinline__ void next_tap(const ConvNhwcArgs &a, const NhwcTile &T)
+    {
+        ++tap;
+        if (++kx == a.kw) {
+            kx = 0;
+            ++ky;
+        }
+        set_tap(a, T);
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
+// Generic form: 32 pixels x 32 channels per wave, K = (ky, kx, cin) two channels at a time, plain loads.
 __global__ void __launch_bounds__(256) conv2d_nhwc_kernel(const ConvNhwcArgs a)
 {
     const int lane = threadIdx.x & 63;
@@ -51,7 +202,7 @@ __global__ void __launch_bounds__(256) conv2d_nhwc_kernel(const ConvNhwcArgs a)
             }
         }
     }
-    // D: column = lane & 31 (channel), row = (reg & 3) + 8 * (reg >> 2) + 4 * kq (pixel)
+    // one tile of nhwc_epilogue, written out: through the helper this kernel's code moves (31 -> 42 VGPRs)
     if (co < a.cout) {
         const float b = a.bias ? a.bias[co] : 0.0f;
 #pragma unroll
@@ -69,115 +220,39 @@ __global__ void __launch_bounds__(256) conv2d_nhwc_kernel(const ConvNhwcArgs a)
 
 // ---------------------------------------------------------------------------------------------
 // conv2d NHWC, tiled form for cin % 8 == 0 (every backbone layer but the first).
-// A wave owns 64 output pixels x 64 output channels (2 x 2 MFMA tiles, 64 accumulator registers); a workgroup is
-// four such waves along the pixel axis.  K walks (tap, 8-channel chunk): per chunk a lane fetches FOUR consecutive
-// input channels of each of its two pixels with one 16-byte load (k-group kq takes channels c+4kq..c+4kq+3, so
-// element s of the load is the lane's operand of k-step s) and the four weight rows it needs for both channel
-// tiles as coalesced dword loads (the weight tensor is a few hundred KB and stays in L2).  16 MFMAs per chunk per
-// wave run on the operands of the previous fetch while the next chunk's 10 loads are in flight.
-typedef unsigned nhwc_u4 __attribute__((ext_vector_type(4)));
-
+// A wave owns 64 output pixels x 64 output channels (2 x 2 MFMA tiles, 64 accumulator registers).  K walks (tap,
+// 8-channel chunk), chunk fastest: per chunk a lane fetches FOUR consecutive input channels of each of its two pixels
+// with one 16-byte load (k-group kq takes channels c+4kq..c+4kq+3, so element s of the load is the lane's operand of
+// k-step s) and the four weight rows it needs for both channel tiles (the weight tensor is a few hundred KB and stays
+// in L2).  16 MFMAs per chunk per wave run on the operands of the previous fetch while the next chunk's loads are in flight.
 struct NhwcChunk {
     float a[2][4];   // [pixel tile][k-step]
     float b[2][4];   // [channel tile][k-step]
 };
 
-// WP4: the weights are pre-packed [k / 4][cout][4] (k = (tap, input channel) flattened; conv2d_nhwc_pack4), so that the
-// four k-steps of a lane's channel come with ONE 16-byte load instead of four dword loads from four weight rows
-// (10 -> 4 vector-memory instructions per 16 MFMAs).  The public gs_conv2d_nhwc takes TensorFlow's [kh,kw,cin,cout] as is;
-// handles that own their weights (gs_detector) pack them once.
 template <bool WP4>
 __global__ void __launch_bounds__(256) conv2d_nhwc_tiled_kernel(const ConvNhwcArgs a)
 {
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    const int r = lane & 31, kq = lane >> 5;
-    const long long npix = (long long)a.n * a.ho * a.wo;
-    const long long pix0 = ((long long)blockIdx.x * 4 + wid) * 64;
-    const int co0 = blockIdx.y * 64;
-    if (pix0 >= npix)
+    NhwcTile T;
+    if (!T.init(a))
         return;
-    constexpr int OOB = 0x7ffffff0;
-    // whole tensors behind buffer descriptors: a lane with nothing to read uses an out-of-range offset and gets 0
-    const unsigned in_bytes = (unsigned)min((long long)a.n * a.h * a.w_ * a.cin * 4, (long long)0x7fffffff);
-    const unsigned w_bytes = (unsigned)((long long)a.kh * a.kw * a.cin * a.cout * 4);
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.in), 0, in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.w), 0, w_bytes, 0x00020000);
-    int oy[2], ox[2];
-    long long ibase[2];
-    bool pv[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const long long pix = pix0 + t * 32 + r;
-        pv[t] = pix < npix;
-        const long long pc = pv[t] ? pix : 0;
-        ox[t] = (int)(pc % a.wo);
-        oy[t] = (int)((pc / a.wo) % a.ho);
-        ibase[t] = (pc / ((long long)a.wo * a.ho)) * a.h;
-    }
-    const bool cv[2] = {co0 + r < a.cout, co0 + 32 + r < a.cout};
     const int nchunk = a.cin / 8;
     const int total = a.kh * a.kw * nchunk;
 
-    // Fetch iterator over (tap, 8-channel chunk), chunk fastest.  Everything that depends on the tap -- the two input
-    // positions, their validity, the byte offsets of the lane's first activation and weight -- is computed once per tap;
-    // inside a tap a fetch only adds the chunk's constant strides (no divisions, no 64-bit address arithmetic per chunk:
-    // with those in every fetch the VALU work beside 16 MFMAs held the kernel at 46 % of the matrix peak).
-    int f_cch = 0, f_ky = 0, f_kx = 0, f_tap = 0;
-    int f_aoff[2], f_woff;
-    auto set_tap = [&]() {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int iy = oy[t] * a.stride - a.pad + f_ky, ix = ox[t] * a.stride - a.pad + f_kx;
-            const bool ok = pv[t] && iy >= 0 && iy < a.h && ix >= 0 && ix < a.w_;
-            f_aoff[t] = ok ? (int)((((ibase[t] + iy) * a.w_ + ix) * a.cin + 4 * kq) * 4) : OOB;
-        }
-        f_woff = WP4 ? (((f_tap * a.cin) / 4 + kq) * a.cout + co0 + r) * 16 : ((f_tap * a.cin + 4 * kq) * a.cout + co0 + r) * 4;
-    };
-    set_tap();
-    const int wstep = WP4 ? 2 * a.cout * 16 : 8 * a.cout * 4;   // bytes between the weights of consecutive chunks
+    NhwcTapIter f;
+    int f_cch = 0, f_woff;
+    f.set_tap(a, T);
+    f_woff = nhwc_w_off<WP4>(a, T, f.tap * a.cin);
+    const int wstep = nhwc_w_step<WP4>(a);
     auto fetch = [&](NhwcChunk &q) {
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            // (an invalid position keeps its out-of-range offset: OOB + chunk stride is still beyond the descriptor)
-#if defined(GS_DIAG) && defined(DET_X_SAMECHUNK)
-            const nhwc_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rin, f_aoff[t] == OOB ? OOB : f_aoff[t], 0, 0);   // timing only
-#elif defined(GS_DIAG) && defined(DET_X_NOALOAD)
-            const nhwc_u4 v = {(unsigned)f_aoff[t], (unsigned)f_cch, 1u, 2u};   // timing only
-#else
-            const nhwc_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rin, f_aoff[t] == OOB ? OOB : f_aoff[t] + f_cch * 32, 0, 0);
-#endif
-            const unsigned e0 = v[0], e1 = v[1], e2 = v[2], e3 = v[3];   // (bit_cast straight from v[i] reads element 0)
-            q.a[t][0] = __builtin_bit_cast(float, e0);
-            q.a[t][1] = __builtin_bit_cast(float, e1);
-            q.a[t][2] = __builtin_bit_cast(float, e2);
-            q.a[t][3] = __builtin_bit_cast(float, e3);
-        }
-        const int wrow = f_woff + f_cch * wstep;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            if (WP4) {
-                const nhwc_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rw, cv[u] ? wrow + 32 * u * 16 : OOB, 0, 0);
-                const unsigned e0 = v[0], e1 = v[1], e2 = v[2], e3 = v[3];
-                q.b[u][0] = __builtin_bit_cast(float, e0);
-                q.b[u][1] = __builtin_bit_cast(float, e1);
-                q.b[u][2] = __builtin_bit_cast(float, e2);
-                q.b[u][3] = __builtin_bit_cast(float, e3);
-                continue;
-            }
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                q.b[u][s] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                          rw, cv[u] ? wrow + (s * a.cout + 32 * u) * 4 : OOB, 0, 0));
-        }
+        for (int t = 0; t < 2; ++t)
+            nhwc_load4(T.rin, f.aoff[t] == NHWC_OOB ? NHWC_OOB : f.aoff[t] + f_cch * 32, q.a[t]);
+        nhwc_fetch_w<WP4>(a, T, f_woff + f_cch * wstep, q.b);
         if (++f_cch == nchunk) {   // (uniform) next tap
             f_cch = 0;
-            ++f_tap;
-            if (++f_kx == a.kw) {
-                f_kx = 0;
-                ++f_ky;
-            }
-            set_tap();
+            f.next_tap(a, T);
+            f_woff = nhwc_w_off<WP4>(a, T, f.tap * a.cin);
         }
     };
 
@@ -202,37 +277,18 @@ __global__ void __launch_bounds__(256) conv2d_nhwc_tiled_kernel(const ConvNhwcAr
                     acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.a[t][s], cur.b[u][s], acc[t][u], 0, 0, 0);
         cur = nxt;
     }
-    // D: column = lane & 31 (channel), row = (reg & 3) + 8 * (reg >> 2) + 4 * kq (pixel)
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int co = co0 + 32 * u + r;
-        if (co >= a.cout)
-            continue;
-        const float b = a.bias ? a.bias[co] : 0.0f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const long long p = pix0 + t * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kq;
-                if (p < npix) {
-                    float v = acc[t][u][reg] + b;
-                    if (a.relu)
-                        v = fmaxf(v, 0.0f);
-                    a.out[p * a.cout + co] = v;
-                }
-            }
-    }
+    nhwc_epilogue(a, T, acc);
 }
 
 // ---------------------------------------------------------------------------------------------
-// conv2d NHWC with packed weights for cin % 32 == 0 (the detector's 64 / 128 / 256-channel layers): the tiled kernel with
-// its activation fetch widened to a whole 128-byte line per pixel.  In NHWC a lane's pixel is cin * 4 bytes from its
-// neighbour's, so the 16-byte operand load of an 8-channel chunk uses an eighth of every line it pulls into L1, and by
-// the time the same wave wants the next 16 bytes of that line -- a whole 16-MFMA chunk later, with every other wave of
-// the CU doing the same -- the line has left the 32 KB L1: measured 86 TFLOP/s against 115 with the activation loads
-// removed.  Here a lane fetches the 64 bytes it will need from the line (its k-group's four channels of FOUR consecutive
-// chunks) with four back-to-back 16-byte loads, the partner k-group's lanes take the other 64, and the 64 MFMAs of the
-// block run on registers.  Activations double-buffered per 32-channel block, weights per 8-channel chunk.
+// conv2d NHWC for cin % 32 == 0 (the detector's 64 / 128 / 256-channel layers): the tiled kernel with its activation
+// fetch widened to a whole 128-byte line per pixel.  In NHWC a lane's pixel is cin * 4 bytes from its neighbour's, so
+// the 16-byte operand load of an 8-channel chunk uses an eighth of every line it pulls into L1, and by the time the same
+// wave wants the next 16 bytes of that line -- a whole 16-MFMA chunk later, with every other wave of the CU doing the
+// same -- the line has left the 32 KB L1: measured 86 TFLOP/s against 115 with the activation loads removed.  Here a
+// lane fetches the 64 bytes it will need from the line (its k-group's four channels of FOUR consecutive chunks) with
+// four back-to-back 16-byte loads, the partner k-group's lanes take the other 64, and the 64 MFMAs of the block run on
+// registers.  Activations double-buffered per 32-channel block, weights per 8-channel chunk.
 template <int NJ>
 struct NhwcWideA {
     float a[2][4 * NJ];   // [pixel tile][chunk j * 4 + k-step]
@@ -240,95 +296,38 @@ struct NhwcWideA {
 struct NhwcWideW {
     float b[2][4];    // [channel tile][k-step]
 };
-// NJ = 8-channel chunks per block (4: a whole 128-byte line per pixel); WP4: weights packed [K/4][cout][4] (one 16-byte load
-// per channel tile and chunk) or TensorFlow's [kh,kw,cin,cout] as given to the public gs_conv2d_nhwc (four dword loads)
+// NJ = 8-channel chunks per block (4: a whole 128-byte line per pixel)
 template <int NJ, bool WP4>
 __global__ void __launch_bounds__(256) conv2d_nhwc_wide_kernel(const ConvNhwcArgs a)
 {
     static_assert(NJ % 2 == 0, "the weight registers ping-pong by chunk parity across blocks");
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    const int r = lane & 31, kq = lane >> 5;
-    const long long npix = (long long)a.n * a.ho * a.wo;
-    const long long pix0 = ((long long)blockIdx.x * 4 + wid) * 64;
-    const int co0 = blockIdx.y * 64;
-    if (pix0 >= npix)
+    NhwcTile T;
+    if (!T.init(a))
         return;
-    constexpr int OOB = 0x7ffffff0;
-    const unsigned in_bytes = (unsigned)min((long long)a.n * a.h * a.w_ * a.cin * 4, (long long)0x7fffffff);
-    const unsigned w_bytes = (unsigned)((long long)a.kh * a.kw * a.cin * a.cout * 4);
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.in), 0, in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.w), 0, w_bytes, 0x00020000);
-    int oy[2], ox[2];
-    long long ibase[2];
-    bool pv[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const long long pix = pix0 + t * 32 + r;
-        pv[t] = pix < npix;
-        const long long pc = pv[t] ? pix : 0;
-        ox[t] = (int)(pc % a.wo);
-        oy[t] = (int)((pc / a.wo) % a.ho);
-        ibase[t] = (pc / ((long long)a.wo * a.ho)) * a.h;
-    }
-    const bool cv[2] = {co0 + r < a.cout, co0 + 32 + r < a.cout};
     const int nblk = a.cin / (8 * NJ);
     const int total = a.kh * a.kw * nblk;   // blocks of the flattened (tap, channel) axis
 
-    // activation iterator over (tap, block), block fastest; the tap-dependent part is computed once per tap
-    int f_blk = 0, f_ky = 0, f_kx = 0;
-    int f_aoff[2];
-    auto set_tap = [&]() {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int iy = oy[t] * a.stride - a.pad + f_ky, ix = ox[t] * a.stride - a.pad + f_kx;
-            const bool ok = pv[t] && iy >= 0 && iy < a.h && ix >= 0 && ix < a.w_;
-            f_aoff[t] = ok ? (int)((((ibase[t] + iy) * a.w_ + ix) * a.cin + 4 * kq) * 4) : OOB;
-        }
-    };
-    set_tap();
+    // activations: (tap, block), block fastest
+    NhwcTapIter f;
+    int f_blk = 0;
+    f.set_tap(a, T);
     auto fetch_a = [&](NhwcWideA<NJ> &q) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const nhwc_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rin, f_aoff[t] == OOB ? OOB : f_aoff[t] + f_blk * (NJ * 32) + j * 32, 0, 0);
-                const unsigned e0 = v[0], e1 = v[1], e2 = v[2], e3 = v[3];   // (bit_cast straight from v[i] reads element 0)
-                q.a[t][4 * j + 0] = __builtin_bit_cast(float, e0);
-                q.a[t][4 * j + 1] = __builtin_bit_cast(float, e1);
-                q.a[t][4 * j + 2] = __builtin_bit_cast(float, e2);
-                q.a[t][4 * j + 3] = __builtin_bit_cast(float, e3);
-            }
+            for (int j = 0; j < NJ; ++j)
+                nhwc_load4(T.rin, f.aoff[t] == NHWC_OOB ? NHWC_OOB : f.aoff[t] + f_blk * (NJ * 32) + j * 32, &q.a[t][4 * j]);
         if (++f_blk == nblk) {   // (uniform) next tap
             f_blk = 0;
-            if (++f_kx == a.kw) {
-                f_kx = 0;
-                ++f_ky;
-            }
-            set_tap();
+            f.next_tap(a, T);
         }
     };
-    // weights: chunk g of the flattened (tap, channel) axis starts at k = 8g (+ 4 for the second k-group), so the offset is
-    // linear in g in both layouts
-    int w_off = WP4 ? (kq * a.cout + co0 + r) * 16 : (4 * kq * a.cout + co0 + r) * 4;
-    const int wstep = WP4 ? 2 * a.cout * 16 : 8 * a.cout * 4;
+    // weights: chunk g of the flattened (tap, channel) axis starts at k = 8g, so one offset steps through all of K
+    int w_off = nhwc_w_off<WP4>(a, T, 0);
+    const int wstep = nhwc_w_step<WP4>(a);
     auto fetch_w = [&](NhwcWideW &q) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            if (WP4) {
-                const nhwc_u4 v = __builtin_amdgcn_raw_buffer_load_b128(rw, cv[u] ? w_off + 32 * u * 16 : OOB, 0, 0);
-                const unsigned e0 = v[0], e1 = v[1], e2 = v[2], e3 = v[3];
-                q.b[u][0] = __builtin_bit_cast(float, e0);
-                q.b[u][1] = __builtin_bit_cast(float, e1);
-                q.b[u][2] = __builtin_bit_cast(float, e2);
-                q.b[u][3] = __builtin_bit_cast(float, e3);
-                continue;
-            }
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                q.b[u][s] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, cv[u] ? w_off + (s * a.cout + 32 * u) * 4 : OOB, 0, 0));
-        }
-        w_off += wstep;   // (beyond the last chunk the offset leaves the descriptor: the load returns zeros)
+        nhwc_fetch_w<WP4>(a, T, w_off, q.b);
+        w_off += wstep;
     };
 
     f32x16 acc[2][2];
@@ -365,26 +364,7 @@ __global__ void __launch_bounds__(256) conv2d_nhwc_wide_kernel(const ConvNhwcArg
         if (it + 1 < total)
             block(a1, a0, it + 2 < total);
     }
-    // D: column = lane & 31 (channel), row = (reg & 3) + 8 * (reg >> 2) + 4 * kq (pixel)
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int co = co0 + 32 * u + r;
-        if (co >= a.cout)
-            continue;
-        const float b = a.bias ? a.bias[co] : 0.0f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const long long p = pix0 + t * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kq;
-                if (p < npix) {
-                    float v = acc[t][u][reg] + b;
-                    if (a.relu)
-                        v = fmaxf(v, 0.0f);
-                    a.out[p * a.cout + co] = v;
-                }
-            }
-    }
+    nhwc_epilogue(a, T, acc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -403,51 +383,33 @@ __global__ void __launch_bounds__(256) conv2d_nhwc_smallcin_kernel(const ConvNhw
         lut[k] = k < K ? (ky << 20 | kx << 10 | c) : -1;
     }
     __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    const int r = lane & 31, kq = lane >> 5;
-    const long long npix = (long long)a.n * a.ho * a.wo;
-    const long long pix0 = ((long long)blockIdx.x * 4 + wid) * 64;
-    const int co0 = blockIdx.y * 64;
-    if (pix0 >= npix)
+    NhwcTile T;
+    if (!T.init(a))
         return;
-    constexpr int OOB = 0x7ffffff0;
-    const unsigned in_bytes = (unsigned)min((long long)a.n * a.h * a.w_ * a.cin * 4, (long long)0x7fffffff);
-    const unsigned w_bytes = (unsigned)((long long)K * a.cout * 4);
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.in), 0, in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.w), 0, w_bytes, 0x00020000);
-    int iy0[2], ix0[2];
-    long long ibase[2];
-    bool pv[2];
+    int iy0[2], ix0[2];   // input position of tap (0, 0)
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-        const long long pix = pix0 + t * 32 + r;
-        pv[t] = pix < npix;
-        const long long pc = pv[t] ? pix : 0;
-        ix0[t] = (int)(pc % a.wo) * a.stride - a.pad;
-        iy0[t] = (int)((pc / a.wo) % a.ho) * a.stride - a.pad;
-        ibase[t] = (pc / ((long long)a.wo * a.ho)) * a.h;
+        ix0[t] = T.ox[t] * a.stride - a.pad;
+        iy0[t] = T.oy[t] * a.stride - a.pad;
     }
-    const bool cv[2] = {co0 + r < a.cout, co0 + 32 + r < a.cout};
     const int nstep = (K + 1) / 2;
     struct Ops {
         float a[2], b[2];
     };
     auto fetch = [&](int s, Ops &q) {
-        const int k = 2 * s + kq;
+        const int k = 2 * s + T.kq;
         const int e = lut[k];
         const int ky = e >> 20, kx = (e >> 10) & 1023, c = e & 1023;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int iy = iy0[t] + ky, ix = ix0[t] + kx;
-            const bool ok = e >= 0 && pv[t] && iy >= 0 && iy < a.h && ix >= 0 && ix < a.w_;
-            const long long off = (((ibase[t] + iy) * a.w_ + ix) * a.cin + c) * 4;
-            q.a[t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rin, ok ? (int)off : OOB, 0, 0));
+            const bool ok = e >= 0 && T.pv[t] && iy >= 0 && iy < a.h && ix >= 0 && ix < a.w_;
+            const long long off = (((T.ibase[t] + iy) * a.w_ + ix) * a.cin + c) * 4;
+            q.a[t] = nhwc_load1(T.rin, ok ? (int)off : NHWC_OOB);
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u)
-            q.b[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                   rw, (e >= 0 && cv[u]) ? (k * a.cout + co0 + 32 * u + r) * 4 : OOB, 0, 0));
+            q.b[u] = nhwc_load1(T.rw, (e >= 0 && T.cv[u]) ? (k * a.cout + T.co0 + 32 * u + T.r) * 4 : NHWC_OOB);
     };
     f32x16 acc[2][2];
 #pragma unroll
@@ -468,25 +430,7 @@ __global__ void __launch_bounds__(256) conv2d_nhwc_smallcin_kernel(const ConvNhw
                 acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.a[t], cur.b[u], acc[t][u], 0, 0, 0);
         cur = nxt;
     }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int co = co0 + 32 * u + r;
-        if (co >= a.cout)
-            continue;
-        const float b = a.bias ? a.bias[co] : 0.0f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const long long p = pix0 + t * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kq;
-                if (p < npix) {
-                    float v = acc[t][u][reg] + b;
-                    if (a.relu)
-                        v = fmaxf(v, 0.0f);
-                    a.out[p * a.cout + co] = v;
-                }
-            }
-    }
+    nhwc_epilogue(a, T, acc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -746,11 +690,6 @@ using namespace gs;
 
 namespace gs {
 
-bool conv2d_nhwc_can_pack4(int n, int h, int w, int cin, int kh, int kw, int cout)
-{
-    return cin % 8 == 0 && (long long)n * h * w * cin * 4 < 0x7fffffffLL && (long long)kh * kw * cin * cout * 4 < 0x7fffffffLL;
-}
-
 // [kh,kw,cin,cout] -> [(kh*kw*cin) / 4][cout][4]  (host)
 void conv2d_nhwc_pack4(const float *w, int kh, int kw, int cin, int cout, float *dst)
 {
@@ -760,24 +699,46 @@ void conv2d_nhwc_pack4(const float *w, int kh, int kw, int cin, int cout, float 
             dst[((size_t)(k / 4) * cout + co) * 4 + (k & 3)] = w[(size_t)k * cout + co];
 }
 
-gs_status conv2d_nhwc_packed4(ConvNhwcArgs a, hipStream_t stream)
+// The one way to a NHWC convolution kernel: fills ho / wo and picks the kernel.  packed: a.w is in conv2d_nhwc_pack4's layout
+// (only the tiled and wide kernels read it); otherwise TensorFlow's [kh,kw,cin,cout].
+gs_status launch_conv2d_nhwc(ConvNhwcArgs a, bool packed, hipStream_t stream)
 {
     a.ho = (a.h + 2 * a.pad - a.kh) / a.stride + 1;
     a.wo = (a.w_ + 2 * a.pad - a.kw) / a.stride + 1;
-    const long long npix = (long long)a.n * a.ho * a.wo;
-    if (a.ho <= 0 || a.wo <= 0 || !conv2d_nhwc_can_pack4(a.n, a.h, a.w_, a.cin, a.kh, a.kw, a.cout)) {
+    const bool empty = a.ho <= 0 || a.wo <= 0;
+    // the 64 x 64 kernels address the input and the weights with 32-bit byte offsets
+    const bool in32 = (long long)a.n * a.h * a.w_ * a.cin * 4 < 0x7fffffffLL;
+    const bool w32 = (long long)a.kh * a.kw * a.cin * a.cout * 4 < 0x7fffffffLL;
+    const bool tiled = a.cin % 8 == 0 && in32 && w32;   // 8-channel chunks
+    if (packed && (empty || !tiled)) {
+        // (the message keeps the name of the entry point this check used to live in)
         set_error("conv2d_nhwc_packed4: shape not supported by the packed-weight kernel");
         return GS_ERR_UNSUPPORTED;
     }
-    dim3 grid((unsigned)((npix + 255) / 256), (unsigned)((a.cout + 63) / 64));
-    // whole-line activation fetches where a pixel has at least a line of channels and the map is not a handful of pixels.
-    // Measured on the detector (16 windows of 1000 x 1000): 64..256-channel backbone layers 86-90 -> 98-119 TFLOP/s; the
-    // 16-channel first layer at two chunks per block 876 -> 1026 us and the box head's 7x7 -> 4x4 layer 264 -> 312 us,
-    // so those stay on the chunk-at-a-time kernel.
-    if (a.cin % 32 == 0 && a.ho * a.wo >= 64)
-        hipLaunchKernelGGL((conv2d_nhwc_wide_kernel<4, true>), grid, dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL(conv2d_nhwc_tiled_kernel<true>, grid, dim3(256), 0, stream, a);
+    GS_REQUIRE(!empty, "gs_conv2d_nhwc: empty output");
+    const long long npix = (long long)a.n * a.ho * a.wo;
+    const dim3 grid64((unsigned)((npix + 255) / 256), (unsigned)((a.cout + 63) / 64));
+    if (tiled) {
+        // whole-line activation fetches where a pixel has at least a line of channels and the map is not a handful of pixels.
+        // Measured on the detector (16 windows of 1000 x 1000): 64..256-channel backbone layers 86-90 -> 98-119 TFLOP/s; the
+        // 16-channel first layer at two chunks per block 876 -> 1026 us and the box head's 7x7 -> 4x4 layer 264 -> 312 us,
+        // so those stay on the chunk-at-a-time kernel.
+        const bool wide = a.cin % 32 == 0 && a.ho * a.wo >= 64;
+        if (wide && packed)
+            hipLaunchKernelGGL((conv2d_nhwc_wide_kernel<4, true>), grid64, dim3(256), 0, stream, a);
+        else if (wide)
+            hipLaunchKernelGGL((conv2d_nhwc_wide_kernel<4, false>), grid64, dim3(256), 0, stream, a);
+        else if (packed)
+            hipLaunchKernelGGL(conv2d_nhwc_tiled_kernel<true>, grid64, dim3(256), 0, stream, a);
+        else
+            hipLaunchKernelGGL(conv2d_nhwc_tiled_kernel<false>, grid64, dim3(256), 0, stream, a);
+    } else if (a.cin < 8 && (long long)a.kh * a.kw * a.cin <= 512 && a.kh < 1024 && a.kw < 1024 && in32) {
+        // few input channels: flattened-K kernel (K = kh*kw*cin up to 512, channel / tap indices below 1024)
+        hipLaunchKernelGGL(conv2d_nhwc_smallcin_kernel, grid64, dim3(256), 0, stream, a);
+    } else {
+        const dim3 grid32((unsigned)((npix + 127) / 128), (unsigned)((a.cout + 31) / 32));
+        hipLaunchKernelGGL(conv2d_nhwc_kernel, grid32, dim3(256), 0, stream, a);
+    }
     GS_HIP(hipGetLastError());
     return GS_OK;
 }
@@ -876,32 +837,8 @@ gs_status gs_conv2d_nhwc(const float *in, int n, int h, int w, int cin, const fl
     GS_REQUIRE(in && weight && out, "gs_conv2d_nhwc: null pointer");
     GS_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && kh > 0 && kw > 0 && stride > 0 && pad >= 0,
                "gs_conv2d_nhwc: bad dimensions");
-    ConvNhwcArgs a{in, weight, bias_or_null, out, n, h, w, cin, kh, kw, cout, stride, pad, relu, 0, 0};
-    a.ho = (h + 2 * pad - kh) / stride + 1;
-    a.wo = (w + 2 * pad - kw) / stride + 1;
-    GS_REQUIRE(a.ho > 0 && a.wo > 0, "gs_conv2d_nhwc: empty output");
-    const long long npix = (long long)n * a.ho * a.wo;
-    // tiled kernel: 8-channel chunks, 32-bit byte offsets into the input and the weights
-    if (cin % 8 == 0 && (long long)n * h * w * cin * 4 < 0x7fffffffLL && (long long)kh * kw * cin * cout * 4 < 0x7fffffffLL) {
-        dim3 grid((unsigned)((npix + 255) / 256), (unsigned)((cout + 63) / 64));
-        if (cin % 32 == 0 && a.ho * a.wo >= 64)   // whole-line activation fetches (see conv2d_nhwc_packed4)
-            hipLaunchKernelGGL((conv2d_nhwc_wide_kernel<4, false>), grid, dim3(256), 0, static_cast<hipStream_t>(hip_stream), a);
-        else
-            hipLaunchKernelGGL(conv2d_nhwc_tiled_kernel<false>, grid, dim3(256), 0, static_cast<hipStream_t>(hip_stream), a);
-        GS_HIP(hipGetLastError());
-        return GS_OK;
-    }
-    // few input channels: flattened-K kernel (K = kh*kw*cin up to 512, channel / tap indices below 1024)
-    if (cin < 8 && (long long)kh * kw * cin <= 512 && kh < 1024 && kw < 1024 && (long long)n * h * w * cin * 4 < 0x7fffffffLL) {
-        dim3 grid((unsigned)((npix + 255) / 256), (unsigned)((cout + 63) / 64));
-        hipLaunchKernelGGL(conv2d_nhwc_smallcin_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(hip_stream), a);
-        GS_HIP(hipGetLastError());
-        return GS_OK;
-    }
-    dim3 grid((unsigned)((npix + 127) / 128), (unsigned)((cout + 31) / 32));
-    hipLaunchKernelGGL(conv2d_nhwc_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(hip_stream), a);
-    GS_HIP(hipGetLastError());
-    return GS_OK;
+    const ConvNhwcArgs a{in, weight, bias_or_null, out, n, h, w, cin, kh, kw, cout, stride, pad, relu, 0, 0};
+    return launch_conv2d_nhwc(a, false, static_cast<hipStream_t>(hip_stream));
 }
 
 gs_status gs_roialign(const float *feat, int n, int h, int w, int c, const float *boxes, const int *box_image, int n_boxes,

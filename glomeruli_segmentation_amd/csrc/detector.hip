@@ -598,7 +598,7 @@ static inline unsigned nblk(long long items) { return (unsigned)((items + 255) /
 static gs_status conv(const Detector &d, const DetLayer &l, const float *in, int n, int h, int w, int relu, float *out, hipStream_t s)
 {
     ConvNhwcArgs a{in, d.dblob + l.w, d.dblob + l.b, out, n, h, w, l.cin, l.k, l.k, l.cout, l.stride, l.pad, relu, 0, 0};
-    return conv2d_nhwc_packed4(a, s);
+    return launch_conv2d_nhwc(a, true, s);
 }
 static inline int conv_out(int x, const DetLayer &l) { return (x + 2 * l.pad - l.k) / l.stride + 1; }
 

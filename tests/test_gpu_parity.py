@@ -528,21 +528,26 @@ def test_detector_primitives_self_consistency(torch_mod):
         assert (out.cpu() - ref).abs().max() <= 2e-4, (ci, kk)
     # the tiled kernel (cin % 8 == 0): ragged pixel and channel tiles, stride 1 and 2, with and without bias / relu
     # ... and its whole-line-fetch form (cin % 32 == 0 and at least 64 output pixels per image)
-    for (cn, hh, ww, ci, co, st, relu, use_bias) in ((2, 21, 37, 16, 70, 1, 1, True), (3, 30, 19, 24, 64, 2, 0, False),
-                                                    (1, 9, 300, 8, 130, 1, 1, True), (2, 21, 37, 32, 70, 1, 1, True),
-                                                    (1, 30, 19, 64, 64, 2, 0, False), (3, 11, 13, 96, 40, 1, 1, True),
-                                                    (1, 7, 9, 32, 33, 1, 0, True)):
-        x = torch.randn(cn, hh, ww, ci, generator=g)
-        w = torch.randn(3, 3, ci, co, generator=g) * 0.1
-        bias = torch.randn(co, generator=g)
-        ref = torch.nn.functional.conv2d(x.permute(0, 3, 1, 2), w.permute(3, 2, 0, 1), bias if use_bias else None, st, 1)
+    # ... and two 1x1 / pad-0 layers (the detector has three): wide kernel with a ragged second channel tile on 442 pixels,
+    # tiled kernel with one partial pixel tile and cout below a lane row (a generator of their own: the draws above and
+    # below stay what they were)
+    g1 = torch.Generator().manual_seed(31)
+    for (cn, hh, ww, ci, co, kk, st, pd, relu, use_bias, gen) in (
+            (2, 21, 37, 16, 70, 3, 1, 1, 1, True, g), (3, 30, 19, 24, 64, 3, 2, 1, 0, False, g), (1, 9, 300, 8, 130, 3, 1, 1, 1, True, g),
+            (2, 21, 37, 32, 70, 3, 1, 1, 1, True, g), (1, 30, 19, 64, 64, 3, 2, 1, 0, False, g), (3, 11, 13, 96, 40, 3, 1, 1, 1, True, g),
+            (1, 7, 9, 32, 33, 3, 1, 1, 0, True, g),
+            (2, 13, 17, 64, 72, 1, 1, 0, 1, True, g1), (1, 5, 5, 8, 6, 1, 1, 0, 1, True, g1)):
+        x = torch.randn(cn, hh, ww, ci, generator=gen)
+        w = torch.randn(kk, kk, ci, co, generator=gen) * 0.1
+        bias = torch.randn(co, generator=gen)
+        ref = torch.nn.functional.conv2d(x.permute(0, 3, 1, 2), w.permute(3, 2, 0, 1), bias if use_bias else None, st, pd)
         ref = (torch.relu(ref) if relu else ref).permute(0, 2, 3, 1).contiguous()
         xd, wd, bd = x.cuda(), w.cuda(), bias.cuda()
         out = torch.full(ref.shape, float("nan"), device="cuda")
-        _lib.check(lib.gs_conv2d_nhwc(xd.data_ptr(), cn, hh, ww, ci, wd.data_ptr(), 3, 3, co, bd.data_ptr() if use_bias else None,
-                                      st, 1, relu, out.data_ptr(), None))
+        _lib.check(lib.gs_conv2d_nhwc(xd.data_ptr(), cn, hh, ww, ci, wd.data_ptr(), kk, kk, co, bd.data_ptr() if use_bias else None,
+                                      st, pd, relu, out.data_ptr(), None))
         torch.cuda.synchronize()
-        assert (out.cpu() - ref).abs().max() <= 2e-4, (cn, hh, ww, ci, co, st)
+        assert (out.cpu() - ref).abs().max() <= 2e-4, (cn, hh, ww, ci, co, kk, st)
     # crop_and_resize
     feat = torch.randn(2, 11, 13, 5, generator=g)
     boxes = torch.tensor([[0.1, 0.2, 0.7, 0.9], [0.0, 0.0, 1.0, 1.0], [-0.2, 0.3, 0.5, 1.2]])
@@ -1163,6 +1168,19 @@ def test_detector_small_against_oracle(torch_mod):
     for i in range(2):
         missing = [v for v in ref["scores"][i] if np.abs(out["scores"][i] - v).min() > 1e-4]
         assert len(missing) <= 2, (i, missing)
+    # one 150x170 window: 6375 / 1634 / 418 / 110 pixels per layer and 14 700 head pixels, none a multiple of 64, so the
+    # packed-weight kernels take their partial pixel tile (every layer of the windows above is whole tiles).  Dense stages
+    # only: the detection list of a new input is one NMS near-tie away from the oracle's and is not what this case is for
+    H, W = 150, 170
+    img = np.random.default_rng(12).integers(0, 256, (1, H, W, 3), dtype=np.uint8)
+    out = {k: v.cpu().numpy() for k, v in det.forward_device(torch.from_numpy(img).cuda(), taps=True).items()}
+    ref = do.detect(img, sd)
+    assert out["features"].shape == ref["features"].shape == (1, 10, 11, 256)
+    assert np.abs(out["features"] - ref["features"]).max() <= 1e-4 * max(1.0, np.abs(ref["features"]).max())
+    assert np.abs(out["rpn"] - ref["rpn"]).max() <= 1e-4 * max(1.0, np.abs(ref["rpn"]).max())
+    nv = int((np.abs(out["proposals"][0]).sum(1) > 0).sum())
+    head = do.box_head(out["features"][0], out["proposals"][0], H, W, sd)
+    assert nv > 0 and np.abs(out["head"][:nv] - head[:nv]).max() <= 2e-4 * max(1.0, np.abs(head).max())
     det.close()
 
 

@@ -9,7 +9,9 @@
   cfg 5  5-fold ensemble (softmax mean over the five shipped folds) on a batch of 32 tiles
 
 Prints one JSON object; `python tools/bench_aux.py > profiles/rNN_aux_bench.json` on the GPU box.
+`--cfg3` stops after the cfg 3 legs (an A/B of the detector half).
 """
+import argparse
 import ctypes
 import json
 import os
@@ -38,6 +40,9 @@ def timeit(fn, reps=20, warm=3):
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--cfg3", action="store_true", help="stop after the cfg 3 legs")
+    args = ap.parse_args()
     lib = _lib.load()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
@@ -101,6 +106,9 @@ def main():
         "note": "synthetic weights (the reference's graph is external); uint8 windows resident in HBM -> detect_box tensors"}
     det.close()
     del wins
+    if args.cfg3:
+        print(json.dumps(out, indent=1))
+        return
 
     # ---- cfg 4: crop stage + compositor ----------------------------------------------------------
     mean, std = FOLD_MEAN_STD[1]
