@@ -18,6 +18,7 @@ GS_IN_F32_NCHW = 1
 ABI_VERSION = 8
 GS_BUILD_DIAG = 1
 GS_FORM_NONE = -1
+GS_MAX_ENSEMBLE_C = 8      # most ESPNet-C members of an ensemble (include/glomseg.h)
 MAX_CROPS_PER_CALL = 64
 
 STATUS_NAMES = {0: "GS_OK", 1: "GS_ERR_INVALID", 2: "GS_ERR_HIP", 3: "GS_ERR_NOMEM", 4: "GS_ERR_UNSUPPORTED",

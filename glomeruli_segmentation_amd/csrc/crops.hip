@@ -4,7 +4,8 @@
 // kernel argument, so a call allocates nothing, copies nothing and is stream-ordered like any other launch.
 //
 //   crops_prep_kernel    :107-116  (x - mean) / std at crop resolution -> cv2.resize INTER_LINEAR -> / 255 -> fp32 NCHW
-//   (forward)            :123,128  espnet_forward_ex: the mask comes out of the decoder tail (ESPNet-C: of enc_head_kernel), no logits
+//   (forward)            :123,128  espnet_forward_ex: the mask comes out of the decoder tail (ESPNet-C: of enc_head_kernel; an ensemble
+//                                  of ESPNet-C members: K trunks, then one enc_head_ens_kernel), no logits
 //   crops_back_kernel    :129,151-155  cv2.resize INTER_NEAREST back to every crop's size + per-class counts of THAT map
 //   crops_paste_kernel   eval_wsi_segmentation.py:311-312  np.max into the 1/ds slide map
 //
@@ -319,15 +320,25 @@ static gs_status check_common(gs_espnet *const *models, int n_models, const floa
     GS_REQUIRE(models && n_models > 0 && means && stds, "segment_crops: null argument");
     GS_REQUIRE(net_h >= 8 && net_w >= 8 && net_h % 8 == 0 && net_w % 8 == 0,
                "network size must be a positive multiple of 8 in both dimensions (got %dx%d)", net_h, net_w);
-    for (int k = 0; k < n_models; ++k) {
+    for (int k = 0; k < n_models; ++k)
         GS_REQUIRE(models[k], "model %d is null", k);
-        // (one ESPNet-C handle is served: its head kernel writes the network-resolution map where the decoder tail does)
-        GS_REQUIRE(n_models == 1 || espnet_is_full_net(models[k]), "ensemble member %d is an ESPNet-C handle: ensembles need full ESPNet members", k);
-        GS_REQUIRE(espnet_classes(models[k]) == espnet_classes(models[0]), "model %d has %d classes, model 0 has %d", k,
-                   espnet_classes(models[k]), espnet_classes(models[0]));
+    if (n_models > 1) {
+        // all full networks, or all ESPNet-C handles (at most GS_MAX_ENSEMBLE_C, run_batch: one head over their logits).
+        // A mixed list is refused HERE, in the crop entries' own words; ensemble_kind below (shared with
+        // gs_espnet_ensemble_forward) would refuse it too, with that entry's text, and is never reached with one: what it
+        // adds for the crop entries is the class counts, the member limit and the repeated handle.
+        bool any_full = false, enc_only = false;
+        for (int k = 0; k < n_models; ++k)
+            any_full = any_full || espnet_is_full_net(models[k]);
+        for (int k = 0; k < n_models; ++k)
+            GS_REQUIRE(!any_full || espnet_is_full_net(models[k]),
+                       "ensemble member %d is an ESPNet-C handle in a list with full networks: mixed ensembles need full ESPNet members", k);
+        const gs_status st = ensemble_kind(models, n_models, &enc_only);   // class counts, the member limit, repeated handles
+        if (st != GS_OK) return st;
+    }
+    for (int k = 0; k < n_models; ++k)
         for (int i = 0; i < 3; ++i)
             GS_REQUIRE(stds[3 * k + i] != 0.0f, "model %d: std[%d] is zero", k, i);
-    }
     return GS_OK;
 }
 
@@ -353,7 +364,9 @@ static gs_status run_batch(gs_espnet *const *models, int n_models, int lane, con
         if (st != GS_OK) return st;
         net_masks = ls.net;
     }
-    if (n_models > 1) {
+    // an ensemble of ESPNet-C members has no accumulator: its members' 1/8-scale logits stay in their workspaces
+    const bool ens_c = n_models > 1 && !espnet_is_full_net(models[0]);
+    if (n_models > 1 && !ens_c) {
         st = grow(ls.prob, ls.prob_bytes, (size_t)n * classes * npx * sizeof(float), "ensemble accumulator");
         if (st != GS_OK) return st;
     }
@@ -383,9 +396,18 @@ static gs_status run_batch(gs_espnet *const *models, int n_models, int lane, con
         }
         hipLaunchKernelGGL(crops_prep_kernel, prep_grid, dim3(256), 0, s, tab, a);
         GS_HIP(hipGetLastError());
+        if (ens_c) {   // the member's trunk only
+            st = espnet_c_trunk(models[k], lane, ls.f32, GS_IN_F32_NCHW, n, net_h, net_w, nullptr, nullptr, nullptr, s);
+            if (st != GS_OK) return st;
+            continue;
+        }
         const int mode = n_models == 1 ? 0 : k == 0 ? 1 : k == n_models - 1 ? 3 : 2;
         st = espnet_forward_ex(models[k], lane, ls.f32, GS_IN_F32_NCHW, n, net_h, net_w, nullptr, nullptr, nullptr, net_masks, nullptr,
                                n_models > 1 ? ls.prob : nullptr, mode, 1.0f / (float)n_models, s);
+        if (st != GS_OK) return st;
+    }
+    if (ens_c) {   // one head over the K members' logits writes the network-resolution masks
+        st = espnet_c_ensemble_head(models, n_models, lane, n, net_h, net_w, net_masks, nullptr, s);
         if (st != GS_OK) return st;
     }
     if (packed_out || hist) {

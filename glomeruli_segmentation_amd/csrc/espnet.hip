@@ -15,6 +15,7 @@
 #include "conv_mfma.h"
 #include "dec_tail_args.h"
 #include "enc_head.h"
+#include "enc_head_ens.h"
 #include "espnet_config.h"
 #include "forward_plan.h"
 #include "espnet_kernels.h"
@@ -47,13 +48,13 @@ static constexpr bool no_vec() { return false; }
 
 enum KernelId {
     K_STEM, K_POOL, K_L2_C1S, K_L2_DOWN, K_L2_C1, K_L2_ESP, K_CAT_B2, K_L3_C1S, K_L3_DOWN, K_L3_C1, K_L3_ESP,
-    K_DEC1, K_DEC2, K_DEC3, K_DEC_CONV, K_DEC4, K_DEC_TAIL, K_ENC_HEAD, K_COUNT
+    K_DEC1, K_DEC2, K_DEC3, K_DEC_CONV, K_DEC4, K_DEC_TAIL, K_ENC_HEAD, K_ENC_HEAD_ENS, K_COUNT
 };
 static const char *kKernelNames[K_COUNT] = {
     "stem_kernel", "pool_kernel", "conv_l2_reduce_s2", "conv_l2_down_branches", "conv_l2_reduce_1x1",
     "conv_l2_esp_branches", "cat_b2_kernel", "conv_l3_reduce_s2", "conv_l3_down_branches", "conv_l3_reduce_1x1",
     "conv_l3_esp_branches", "dec1_kernel", "dec2_kernel", "dec3_kernel", "conv_dec_cbr", "dec4_kernel", "dec_tail_kernel",
-    "enc_head_kernel"};
+    "enc_head_kernel", "enc_head_ens_kernel"};
 
 struct PackedConv {   // float offsets into the device weight blob
     long long c1 = -1, br = -1;
@@ -1013,6 +1014,69 @@ gs_status espnet_forward_ex(gs_espnet *h, int lane, const void *in, int in_forma
     if (st != GS_OK) return st;
     return forward_any(&m, in, in_format, n, height, width, mean, stdv, logits, mask, hist, s, prob, ens_mode, ens_w);
 }
+
+// ---- ESPNet-C ensembles (enc_head_ens.h).  A member's trunk is its plain forward with no output asked for: it stops after
+// dec1_kernel with its 1/8-scale logits in the up_l3 buffer of its own workspace (forward_impl, `enc_logits`), and `hist`, given
+// to the first member, is zeroed by that member's stem.
+gs_status espnet_c_trunk(gs_espnet *h, int lane, const void *in, int in_format, int n, int height, int width, const float *mean,
+                         const float *stdv, unsigned long long *hist_zero, hipStream_t s)
+{
+    return espnet_forward_ex(h, lane, in, in_format, n, height, width, mean, stdv, nullptr, nullptr, hist_zero, nullptr, 0, 1.0f, s);
+}
+
+// what a list of members is: GS_OK and *enc_only (all full / all ESPNet-C), or the refusal of a mixed list, of members that
+// disagree on the class count, of more than GS_MAX_ENSEMBLE_C ESPNet-C members and of one ESPNet-C handle listed twice (its
+// workspace holds ONE set of logits)
+gs_status ensemble_kind(gs_espnet *const *models, int n_models, bool *enc_only)
+{
+    int n_enc = 0;
+    for (int k = 0; k < n_models; ++k) {
+        GS_REQUIRE(models[k], "ensemble member %d is null", k);
+        n_enc += models[k]->m.encoder_only ? 1 : 0;
+    }
+    *enc_only = n_enc == n_models;
+    for (int k = 0; k < n_models; ++k) {
+        // a mixed list, full and ESPNet-C members in either order
+        GS_REQUIRE(*enc_only || !models[k]->m.encoder_only, "ensemble member %d is not a full ESPNet", k);
+        GS_REQUIRE(models[k]->m.classes == models[0]->m.classes, "ensemble member %d has %d classes, member 0 has %d", k,
+                   models[k]->m.classes, models[0]->m.classes);
+        for (int j = 0; *enc_only && j < k; ++j)
+            GS_REQUIRE(models[j] != models[k], "ESPNet-C ensemble members %d and %d are the same handle", j, k);
+    }
+    if (*enc_only && n_models > GS_MAX_ENSEMBLE_C) {
+        set_error("an ESPNet-C ensemble has at most %d members (got %d)", GS_MAX_ENSEMBLE_C, n_models);
+        return GS_ERR_UNSUPPORTED;
+    }
+    return GS_OK;
+}
+
+// the one head launch behind the K trunks of lane `lane`: class map and counts from the members' logits where they lie
+gs_status espnet_c_ensemble_head(gs_espnet *const *models, int n_models, int lane, int n, int height, int width, uint8_t *mask,
+                                 unsigned long long *hist, hipStream_t s)
+{
+    EncHeadEnsArgs a{};
+    for (int k = 0; k < n_models; ++k) {
+        GS_REQUIRE(lane >= 0 && lane <= (int)models[k]->lanes.size(), "member %d has no lane %d (gs_espnet_set_lanes)", k, lane);
+        const Model &mk = models[k]->lane(lane);
+        GS_REQUIRE(mk.encoder_only && mk.ws && n <= mk.ws_n && height == mk.ws_h && width == mk.ws_w,
+                   "internal: member %d holds no 1/8-scale logits of this batch", k);
+        a.logits[k] = mk.o2c.base;
+    }
+    a.mask = mask;
+    a.hist = hist;
+    a.classes = models[0]->m.classes;
+    a.members = n_models;
+    a.H3 = height / 8;
+    a.W3 = width / 8;
+    a.inv_members = 1.0f / (float)n_models;
+    Model &m0 = models[0]->lane(lane);   // (the profiler of the first member times the head)
+    Launcher L{&m0, s, GS_OK, n};
+    L.run(K_ENC_HEAD_ENS, (double)height * width * (a.classes * n_models * 20), [&] {
+        launch_ens_head(a, n, s);
+        return GS_OK;
+    });
+    return L.st;
+}
 }  // namespace gs
 
 extern "C" {
@@ -1497,12 +1561,21 @@ gs_status gs_espnet_ensemble_forward(gs_espnet *const *models, int n_models, con
     gs_status st = check_shape(n, height, width);
     if (st != GS_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    for (int k = 0; k < n_models; ++k) {
-        GS_REQUIRE(models[k] && !models[k]->m.encoder_only, "ensemble member %d is not a full ESPNet", k);
-        GS_REQUIRE(models[k]->m.classes == models[0]->m.classes, "ensemble member %d has %d classes, member 0 has %d", k,
-                   models[k]->m.classes, models[0]->m.classes);
+    bool enc_only = false;
+    st = ensemble_kind(models, n_models, &enc_only);
+    if (st != GS_OK) return st;
+    for (int k = 0; k < n_models; ++k)
         for (int i = 0; i < 3; ++i)
             GS_REQUIRE(stds[3 * k + i] != 0.0f, "ensemble member %d: std[%d] is zero", k, i);
+    if (enc_only) {
+        // ESPNet-C members: the K trunks one after the other on the call's stream, then ONE head over their 1/8-scale logits
+        // (enc_head_ens.h).  No accumulator is allocated; K = 1 runs the same code.
+        for (int k = 0; k < n_models; ++k) {
+            st = espnet_c_trunk(models[k], 0, in_u8, GS_IN_U8_BGR_NHWC, n, height, width, means + 3 * k, stds + 3 * k,
+                                k == 0 ? hist : nullptr, s);
+            if (st != GS_OK) return st;
+        }
+        return espnet_c_ensemble_head(models, n_models, 0, n, height, width, mask, hist, s);
     }
     float *prob = nullptr;
     st = ensemble_scratch(models[0], n, height, width, &prob);

@@ -72,5 +72,12 @@ gs_status ensemble_scratch(gs_espnet *h, int n, int height, int width, float **p
 gs_status espnet_forward_ex(gs_espnet *h, int lane, const void *in, int in_format, int n, int height, int width, const float *mean,
                             const float *stdv, float *logits, uint8_t *mask, unsigned long long *hist, float *prob, int ens_mode,
                             float ens_w, hipStream_t s);
+// ESPNet-C ensembles (csrc/enc_head_ens.h): what a member list is (or its refusal), a member's trunk (its forward up to the
+// 1/8-scale logits, left in its workspace), and the one head launch over the K members' logits of lane `lane`
+gs_status ensemble_kind(gs_espnet *const *models, int n_models, bool *enc_only);
+gs_status espnet_c_trunk(gs_espnet *h, int lane, const void *in, int in_format, int n, int height, int width, const float *mean,
+                         const float *stdv, unsigned long long *hist_zero, hipStream_t s);
+gs_status espnet_c_ensemble_head(gs_espnet *const *models, int n_models, int lane, int n, int height, int width, uint8_t *mask,
+                                 unsigned long long *hist, hipStream_t s);
 
 }  // namespace gs

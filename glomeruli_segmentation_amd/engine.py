@@ -361,7 +361,9 @@ def segment_crops_host(engines, mean_stds, crops, net_h=512, net_w=1024, batch=3
                        want_hist=True, paste=None, origins=None, overlay=None):
     """gs_espnet_segment_crops_host: crops of any sizes in host memory -> per-crop class maps at crop size.
 
-    engines: one EspnetEngine (the plain model) or several (the cfg-5 ensemble, each with its own (mean, std) in mean_stds).
+    engines: one EspnetEngine (the plain model) or several (the cfg-5 ensemble, each with its own (mean, std) in mean_stds):
+    all full networks, or all `encoder_only` (ESPNet-C) engines -- at most _lib.GS_MAX_ENSEMBLE_C of those, each listed once; the
+    library then runs the members' trunks and one head over their 1/8-scale logits.  A list that mixes the two raises GlomsegError.
     crops: list of uint8 BGR [h,w,3] numpy arrays / CPU tensors (pinned ones are DMA'd in place).
     paste: an _lib.PasteTarget (see paste_target) + origins [(x1, y1), ...]: the crops are also max-composited into the
     slide map on the GPU.
@@ -447,7 +449,10 @@ def segment_crops_host(engines, mean_stds, crops, net_h=512, net_w=1024, batch=3
 
 def ensemble_segment(engines, tiles_u8, mean_stds):
     """cfg 5: mean over models of softmax(logits_k) (each model with its own mean/std) -> argmax mask,
-    per-class counts.  The reference has no ensemble code; the definition is this build's."""
+    per-class counts.  The reference has no ensemble code; the definition is this build's.
+    The engines are all full networks, or all `encoder_only` (ESPNet-C) engines: 1 .. _lib.GS_MAX_ENSEMBLE_C of them, each listed
+    once -- softmax of every member's x8-upsampled 1/8-scale logits, mean, first-max argmax in one head launch behind the members'
+    trunks.  A mixed list, differing class counts and a ninth ESPNet-C member raise GlomsegError."""
     lib = _lib.load()
     tiles_u8 = tiles_u8.contiguous()
     n, h, w, _ = tiles_u8.shape

@@ -29,8 +29,17 @@ def engine_classes(engine):
 def segment_crops(engine, crops, mean, std, net_h, net_w, batch=32, paste=None, origins=None, want_masks=True):
     """crops: list of uint8 BGR [h,w,3] arrays of any size -> (list of uint8 class maps [h,w], counts int64 [n,classes]) through
     the library's batched crop pipeline (gs_espnet_segment_crops_host); with `paste` (+ origins) the maps are also
-    max-composited into the slide map on the GPU, in the same launches."""
-    r = engine.segment_crops(crops, mean, std, net_h, net_w, batch, want_masks=want_masks, paste=paste, origins=origins)
+    max-composited into the slide map on the GPU, in the same launches.
+    engine: one engine, or an ensemble -- a list of engines, all full networks or all `encoder_only` (ESPNet-C) ones, with `mean`
+    and `std` then one triple per member."""
+    if isinstance(engine, (list, tuple)):
+        if len(mean) != len(engine) or len(std) != len(engine):
+            raise ValueError("an ensemble of %d engines needs %d mean and std triples" % (len(engine), len(engine)))
+        from .engine import segment_crops_host
+        r = segment_crops_host(list(engine), list(zip(mean, std)), crops, net_h, net_w, batch, want_masks=want_masks, paste=paste,
+                               origins=origins)
+    else:
+        r = engine.segment_crops(crops, mean, std, net_h, net_w, batch, want_masks=want_masks, paste=paste, origins=origins)
     return r["masks"], r["counts"]
 
 
@@ -39,8 +48,9 @@ def run_slide(engine, read_region, slide_w, slide_h, mpp_x, mpp_y, detector, mea
               net_h=512, net_w=1024, rank=0, world=1, dist=None, batch=32, detector_batch=1):
     """read_region(x, y, w, h, downsample) -> uint8 RGB [h,w,3] of the slide at that downsample (level-0 origin).
     Returns dict(boxes=merged boxes, masks=this rank's crop masks, map=1/8 class map (rank 0 / all ranks when
-    dist is None), counts=per-class pixel totals over all crops: int64 [engine.classes])."""
-    dev = engine.device
+    dist is None), counts=per-class pixel totals over all crops: int64 [engine.classes]).
+    engine: one engine or an ensemble (a list of engines with one mean / std triple per member: segment_crops above)."""
+    dev = (engine[0] if isinstance(engine, (list, tuple)) else engine).device
     level, ds = detect.pick_level(objective_power, level_downsamples)
     plan = detect.plan_windows(slide_w, slide_h, mpp_x, mpp_y, ds, window_um, overlap)
     rows = detect.scan_slide(lambda x, y, w, h: read_region(x, y, w, h, ds), detector, plan, conf_threshold, "site", "slide",

@@ -39,7 +39,9 @@ typedef enum gs_status {
 
 const char *gs_last_error(void);
 /* ABI version, bumped on any change of a signature or of what an entry accepts (8: the forward-plan entries;
- * 7: ESPNet-C handles give masks and counts). */
+ * 7: ESPNet-C handles give masks and counts).  ABI 8 libraries from the commit that added csrc/enc_head_ens.h on also accept
+ * ensembles whose members are all ESPNet-C handles (below); the number was not bumped for that: no signature changed, and a
+ * caller finds out by the call itself (an older ABI 8 library answers GS_ERR_INVALID). */
 int gs_abi_version(void);
 /* How the library was compiled: GS_BUILD_DIAG = a -DGS_DIAG experiment build (timing variants that return wrong results by
  * construction can be switched on through the environment); the product library returns 0 and reads no environment. */
@@ -101,8 +103,15 @@ typedef enum gs_input_format {
  * torch.nn.Upsample(scale_factor=8, mode='bilinear') + img_out[0].max(0)[1] (VisualizeResults_iou.py:125-128,258-261), computed
  * with the counts by one head kernel that never writes full-resolution logits (csrc/enc_head.h holds the exact expression).
  * logits and mask given together come from the same pass.  Everything below that takes a handle serves an ESPNet-C handle as
- * it serves a full one (lanes, gs_espnet_segment_host, the crop entries with one model); only the ensembles refuse it as a
- * member: gs_espnet_ensemble_forward, gs_espnet_ensemble_segment_crops, gs_espnet_segment_crops_host with n_models > 1. */
+ * it serves a full one (lanes, gs_espnet_segment_host, the crop entries with one model), the ensembles included
+ * (gs_espnet_ensemble_forward, gs_espnet_ensemble_segment_crops, gs_espnet_segment_crops_host with n_models > 1) when ALL
+ * members are ESPNet-C handles, at most GS_MAX_ENSEMBLE_C of them and each listed once: the members' trunks run one after the
+ * other, each with its own mean/std, and stop at their 1/8-scale logits; ONE head launch (csrc/enc_head_ens.h) then upsamples
+ * the K small maps, averages the K softmaxes in registers and writes the class map and the counts -- no probability
+ * accumulator exists for such an ensemble.  A list that mixes full and ESPNet-C members, in either order, is refused
+ * (GS_ERR_INVALID), as are members that disagree on the class count; more than GS_MAX_ENSEMBLE_C ESPNet-C members are
+ * GS_ERR_UNSUPPORTED. */
+#define GS_MAX_ENSEMBLE_C 8
 gs_status gs_espnet_forward(gs_espnet *h, const void *in, int in_format, int n, int height, int width,
                             const float mean[3], const float std[3], float *logits, uint8_t *mask,
                             unsigned long long *hist, void *hip_stream);
@@ -176,7 +185,9 @@ gs_status gs_espnet_segment_crops(gs_espnet *h, int lane, const uint8_t *packed_
 
 /* The same for an ensemble (cfg 5 definition: mean over members of softmax, each member with its own mean/std): every member
  * resamples the crops with its own normalisation (the reference normalises BEFORE it resizes) and adds its probabilities in
- * the decoder tail; the last member's tail writes the masks. */
+ * the decoder tail; the last member's tail writes the masks.  Members that are all ESPNet-C handles (<= GS_MAX_ENSEMBLE_C): every
+ * member resamples and runs its trunk, one head launch over the members' 1/8-scale logits writes the masks (gs_espnet_forward);
+ * what follows the masks is the same.  n_models == 1 is gs_espnet_segment_crops on lane 0. */
 gs_status gs_espnet_ensemble_segment_crops(gs_espnet *const *models, int n_models, const uint8_t *packed_in, const gs_crop_desc *descs,
                                            int n, const float *means, const float *stds, int net_h, int net_w, uint8_t *net_masks,
                                            uint8_t *packed_out, unsigned long long *hist, const gs_paste_target *paste,
@@ -205,7 +216,8 @@ typedef struct gs_crop_overlay {
  * threads); up to `batch` (<= GS_MAX_CROPS_PER_CALL) crops per step; uploads on a stream of their own, batches alternate
  * between two compute streams (and two lanes when the handle has them), results come back by SDMA.  Outputs, each optional:
  * masks[i] (host uint8 [heights[i],widths[i]]), net_masks (host uint8 [n_crops,net_h,net_w]), hist (host uint64 [n_crops,classes],
- * counts of the crop-size maps), paste + x1/y1 (level-0 origins), overlay (above).  n_models == 1 is the plain model; > 1 the ensemble.
+ * counts of the crop-size maps), paste + x1/y1 (level-0 origins), overlay (above).  n_models == 1 is the plain model; > 1 the ensemble
+ * (all members full networks, or all ESPNet-C handles: gs_espnet_ensemble_segment_crops).
  * A list shorter than four full batches is cut into a small first batch (a seventh of the list, at least eight crops: its
  * upload is the pipeline's fill) and three equal ones.
  * Page-locked masks[] that lie in ONE block, every map in a 256-byte-aligned slot right behind the previous one, are
@@ -296,7 +308,9 @@ double gs_arc_length_closed(const int *xy, int n);
 int gs_approx_poly_closed(const int *xy, int n, double epsilon, int *out_xy);
 
 /* 5-fold style ensemble (BASELINE cfg 5; definition in DESIGN.md): probability = mean over
- * models of softmax(logits_k), each model with its own mean/std; writes argmax mask. */
+ * models of softmax(logits_k), each model with its own mean/std; writes argmax mask.
+ * Members are all full networks (any number; a full-resolution fp32 accumulator owned by the first member) or all ESPNet-C
+ * handles (1 .. GS_MAX_ENSEMBLE_C, each once; softmax of the x8-upsampled 1/8-scale logits, no accumulator: gs_espnet_forward). */
 gs_status gs_espnet_ensemble_forward(gs_espnet *const *models, int n_models, const void *in_u8, int n,
                                      int height, int width, const float *means /*[n_models*3]*/,
                                      const float *stds /*[n_models*3]*/, uint8_t *mask,

@@ -5,7 +5,10 @@ slides, ONE SLIDE PER RANK (all five folds resident on every rank, no
 class totals are gathered once at the end).  `--gpus N` spawns the ranks like bench.py; rank r takes slides r, r+N, ...
 Secondary measurement -- bench.py owns the headline.
 
-    python tools/bench_ensemble.py [--gpus N] [--slides 8] [--size 40000]      ->  one JSON line (rank 0)
+    python tools/bench_ensemble.py [--gpus N] [--slides 8] [--size 40000] [--modelType 1|2]      ->  one JSON line (rank 0)
+
+`--modelType 2`: the five members are ESPNet-C engines (each fold's `encoder.*` weights); the same call then runs five trunks and
+one head launch over their 1/8-scale logits per batch (csrc/enc_head_ens.h) instead of five decoder tails and an accumulator.
 
 Per slide: the example-slide box pattern (tools/bench_slide.grid_boxes, 56 crops at 40k) is read from the synthetic
 slide at level 0 -- every crop at its own size, as make_seg_data.py:357-361 cuts them -- and goes through ONE call of the
@@ -37,6 +40,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--slides", type=int, default=8)
     ap.add_argument("--size", type=int, default=40000)
+    ap.add_argument("--modelType", type=int, default=1, choices=(1, 2), help="1 = ESPNet (default), 2 = ESPNet-C members")
     ap.add_argument("--dry-run", action="store_true",
                     help="control flow only with CPU stand-ins over gloo (tools/dry.py): the CPU test suite's 8-rank rehearsal; never a measurement")
     args = ap.parse_args()
@@ -90,7 +94,11 @@ def main():
             engines.append(stand_ins.DryEngine())
             continue
         z = np.load(os.path.join(REPO, "tests", "golden", "weights_fold%d.npz" % f))
-        engines.append(EspnetEngine({k: z[k] for k in z.files}, lanes=2))
+        sd = {k: z[k] for k in z.files}
+        if args.modelType == 2:
+            engines.append(EspnetEngine({k[len("encoder."):]: v for k, v in sd.items() if k.startswith("encoder.")}, encoder_only=True, lanes=2))
+        else:
+            engines.append(EspnetEngine(sd, lanes=2))
     mean_stds = [FOLD_MEAN_STD[f] for f in folds]
     example = np.load(os.path.join(REPO, "tests", "golden", "merge.npz"))["example_boxes"]
     boxes = bench_slide.grid_boxes(S, example)
@@ -134,7 +142,7 @@ def main():
         print(json.dumps({
             "config": "cfg 5: five-fold ensemble over %d synthetic %d x %d slides, one slide per rank, %d rank(s)" % (args.slides, S, S, world),
             "data": "dry-run (CPU stand-ins, no device work)" if dry else "synthetic",
-            "slides": args.slides, "crops_per_slide": len(boxes), "folds": len(folds),
+            "slides": args.slides, "crops_per_slide": len(boxes), "folds": len(folds), "model_type": args.modelType,
             "gpu_leg_s": round(t_gpu_m, 3), "slides_per_s": round(args.slides / t_gpu_m, 2),
             "crops_per_s": round(crops_all / t_gpu_m, 1), "model_passes_per_s": round(crops_all * len(folds) / t_gpu_m, 1),
             "synthetic_region_generation_s": round(t_read_m, 3), "total_s": round(t_total_m, 3),
