@@ -51,6 +51,11 @@ class CropOverlay(ctypes.Structure):
                 ("out_bgr", ctypes.POINTER(ctypes.c_void_p))]
 
 
+class CropScoring(ctypes.Structure):
+    _fields_ = [("labels", ctypes.POINTER(ctypes.c_void_p)), ("conf", ctypes.c_void_p), ("seen", ctypes.c_void_p),
+                ("gt_overlay_bgr", ctypes.POINTER(ctypes.c_void_p)), ("gt_clamp", ctypes.c_int32)]
+
+
 class EvalBox(ctypes.Structure):
     _fields_ = [("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("x1", ctypes.c_int32), ("y1", ctypes.c_int32),
                 ("raster_w", ctypes.c_int32), ("raster_h", ctypes.c_int32), ("offset", ctypes.c_int64)]
@@ -123,6 +128,12 @@ PROTOTYPES = {
     "gs_detector_detect_host": (_I, [_P, ctypes.POINTER(_P), _I, _I, _I, _I, _P, _P, _P, _P]),
 }
 
+# every symbol include/glomseg_scoring.h declares (additions to ABI 8 with a header of their own)
+SCORING_PROTOTYPES = {
+    "gs_espnet_score_crops": (_I, [_P, _P, ctypes.POINTER(CropDesc), _I, _I, _I, _I, _P, _P, _P]),
+    "gs_espnet_segment_crops_host_scored": (_I, PROTOTYPES["gs_espnet_segment_crops_host"][1] + [ctypes.POINTER(CropScoring)]),
+}
+
 _lib = None
 
 
@@ -137,7 +148,7 @@ def load():
             "%s is missing: build it with `python -m glomeruli_segmentation_amd.build` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in list(PROTOTYPES.items()) + list(SCORING_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -8,13 +8,20 @@
 //                                  of ESPNet-C members: K trunks, then one enc_head_ens_kernel), no logits
 //   crops_back_kernel    :129,151-155  cv2.resize INTER_NEAREST back to every crop's size + per-class counts of THAT map
 //   crops_paste_kernel   eval_wsi_segmentation.py:311-312  np.max into the 1/ds slide map
+//   crops_score_kernel   :195-203 (IOUEval.py:19-21), :196  a labelled batch: every crop's label nearest-resized to the network
+//                                  size on the fly, its confusion matrix against the network-resolution mask and the set of
+//                                  label values (np.unique), one launch per batch (gs_espnet_score_crops, glomseg_scoring.h)
+//   crops_overlay_kernel :139-146, :218-222  palette colouring + addWeighted of the prediction; launched a second time over the
+//                                  packed labels for the ground-truth overlay
 //
-// All four are bandwidth-bound byte / fp32 streams (bound: HBM); per 1024x512 network tile and ~0.6 Mpx crop they move
-// 6.3 MB (fp32 tensor out) + ~1.8 MB (crop in), 0.5 MB + 0.6 MB, and a few KB.
+// The first four are bandwidth-bound byte / fp32 streams (bound: HBM); per 1024x512 network tile and ~0.6 Mpx crop they move
+// 6.3 MB (fp32 tensor out) + ~1.8 MB (crop in), 0.5 MB + 0.6 MB, and a few KB.  crops_score_kernel reads 0.5 MB of mask and the
+// gathered label bytes per crop and is bound by its counters, not by HBM.
 #include <algorithm>
 #include <memory>
 #include <vector>
 
+#include "../../include/glomseg_scoring.h"
 #include "crop_plan.h"
 #include "crop_sample.h"
 #include "gs_internal.h"
@@ -153,6 +160,7 @@ struct OverlayArgs {
     unsigned char *out;           // packed overlays, at in_off
     float wa, wb;
     int n_colours;
+    int clamp;                    // a class beyond the table: 0 = black, 1 = the table's last row (the ground-truth overlay)
     unsigned char pal[GS_MAX_PALETTE * 3];   // RGB rows
 };
 
@@ -178,7 +186,9 @@ __global__ void __launch_bounds__(256) crops_overlay_kernel(const CropTable t, c
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int c = (int)((cw >> (8 * k)) & 0xffu);
+            int c = (int)((cw >> (8 * k)) & 0xffu);
+            if (a.clamp && c >= a.n_colours)
+                c = a.n_colours - 1;
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {
                 const int bi = k * 3 + ch;
@@ -197,6 +207,145 @@ __global__ void __launch_bounds__(256) crops_overlay_kernel(const CropTable t, c
             for (int k = 0; k < np * 3; ++k)
                 dst[base * 3 + k] = (unsigned char)(ow[k >> 2] >> (8 * (k & 3)));
         }
+    }
+}
+
+// Scoring of a labelled batch at network resolution (VisualizeResults_iou.py:195-203): for every network pixel of crop i the
+// label byte g at the pixel's INTER_NEAREST source in the crop-size label (the reference resizes the label to the network size,
+// :195; a label already at that size is the identity case of the same rule) and the mask byte p; conf_i[g][p] += 1 for
+// g < classes (IOUEval.py:19-21; a mask byte >= classes, which no forward writes, is dropped too) and bit g of seen_i set for
+// every g (np.unique of the resized label, :196).  One thread = four consecutive mask bytes of one row (one dword; net_w is a
+// multiple of 8), about eight such dwords per thread.  Nearly every pixel is background on both sides, so no counter is bumped
+// per pixel in memory of any kind:
+//   REG (classes <= 5)  crops_back_kernel's packed counters, one 64-bit word of five 12-bit fields per ground-truth row, five
+//                       words per lane (at most 4 added to a field per iteration and the grid keeps a lane under 33
+//                       iterations: <= 132 of 4095), a butterfly add over the wave per field, one LDS add per wave;
+//   general (6 .. 20)   80 words of registers do not fit: bin (0,0) is counted in a register per lane, every other bin is
+//                       aggregated over the wave first -- the lanes that hold the leader's bin are counted with a ballot and
+//                       the leader adds the count to the workgroup's LDS histogram: one LDS add per DISTINCT bin of a wave
+//                       instruction (one, for a crop whose glomerulus fills the tile).
+// Label values below 64 are collected in a register per lane and OR-reduced over the wave; the others (a 255 "ignore" byte) go
+// to the LDS set only when the lane's value changes.  One global add per non-zero bin and one OR per non-zero word per workgroup;
+// conf and seen are zeroed on the stream by the launcher.
+struct ScoreArgs {
+    const unsigned char *net;      // [n][net_h][net_w]
+    const unsigned char *labels;   // packed crop-size labels (gs_crop_desc::out_off)
+    unsigned long long *conf;      // [n][classes][classes], rows = ground truth
+    unsigned long long *seen;      // [n][4]: 256-bit set, or null
+    int net_h, net_w, classes;
+};
+
+// CFG_SCORE_FORM -- 0: the register form up to five classes, the ballot form above (the product); 1 / 2: the ballot form / the
+// wave-private LDS histograms (one LDS add per pixel into the wave's own copy of the matrix, the copies summed at the end) for
+// EVERY class count: the A/B of tools/crop_scoring_rate.py (DESIGN.md section 4 has the figures)
+#ifndef CFG_SCORE_FORM
+#define CFG_SCORE_FORM 0
+#endif
+enum { SCORE_REG = 0, SCORE_BALLOT = 1, SCORE_WAVE_HIST = 2 };
+
+template <int FORM>
+__global__ void __launch_bounds__(256) crops_score_kernel(const CropTable t, const ScoreArgs a)
+{
+    constexpr bool REG = FORM == SCORE_REG;
+    constexpr int NBINS = GS_MAX_CLASSES * GS_MAX_CLASSES;
+    constexpr int NB = REG ? 25 : FORM == SCORE_WAVE_HIST ? 4 * NBINS : NBINS;
+    __shared__ unsigned lh[NB];
+    __shared__ unsigned ls[8];
+    const int i = blockIdx.y, lane = threadIdx.x & 63, cl = a.classes;
+    for (int k = threadIdx.x; k < NB; k += 256)
+        lh[k] = 0;
+    if (threadIdx.x < 8)
+        ls[threadIdx.x] = 0;
+    __syncthreads();
+    const int h = t.d[i].h, w = t.d[i].w;
+    const unsigned char *msk = a.net + (long long)i * a.net_h * a.net_w;
+    const unsigned char *lab = a.labels + t.d[i].out_off;
+    const double sfy = cv_inv_scale(a.net_h, h), sfx = cv_inv_scale(a.net_w, w);
+    const int w4 = a.net_w / 4, quads = a.net_h * w4;
+    unsigned long long rows[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
+    unsigned long long lo = 0ull;   // label values 0 .. 63 this lane has met
+    int n00 = 0, last = -1;
+    // (the loop bound is the wave's, not the lane's: the ballots below see whole waves)
+    for (int q0 = blockIdx.x * 256 + (threadIdx.x - lane); q0 < quads; q0 += gridDim.x * 256) {
+        const int q = q0 + lane;
+        const bool valid = q < quads;
+        const int oy = valid ? q / w4 : 0, ox = valid ? (q - oy * w4) * 4 : 0;
+        const unsigned mw = valid ? *reinterpret_cast<const unsigned *>(msk + (long long)oy * a.net_w + ox) : 0u;
+        const unsigned char *lrow = lab + (long long)nearest_src(oy, sfy, h) * w;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int g = lrow[nearest_src(ox + k, sfx, w)], p = (int)((mw >> (8 * k)) & 0xffu);
+            if (valid) {
+                if (g < 64) {
+                    lo |= 1ull << g;
+                } else if (g != last) {
+                    atomicOr(&ls[g >> 5], 1u << (g & 31));
+                    last = g;
+                }
+            }
+            const bool counted = valid && g < cl && p < cl;
+            if (REG) {
+                const unsigned long long inc = counted ? 1ull << (12 * p) : 0ull;
+#pragma unroll
+                for (int r = 0; r < 5; ++r)
+                    rows[r] += g == r ? inc : 0ull;
+            } else if (FORM == SCORE_WAVE_HIST) {
+                if (counted)
+                    atomicAdd(&lh[(threadIdx.x >> 6) * NBINS + g * cl + p], 1u);
+            } else {
+                const int bin = g * cl + p;
+                n00 += counted && bin == 0 ? 1 : 0;
+                const bool active = counted && bin != 0;
+                unsigned long long todo = __ballot(active);
+                while (todo) {
+                    const int leader = __ffsll((long long)todo) - 1;
+                    const int lb = __shfl(bin, leader, 64);
+                    const unsigned long long m = __ballot(active && bin == lb);
+                    if (lane == leader)
+                        atomicAdd(&lh[lb], (unsigned)__popcll(m));
+                    todo &= ~m;
+                }
+            }
+        }
+    }
+    if (REG) {
+#pragma unroll
+        for (int k = 0; k < 25; ++k) {
+            int c = (int)((rows[k / 5] >> (12 * (k % 5))) & 0xfffull);
+#pragma unroll
+            for (int sh = 32; sh >= 1; sh >>= 1)
+                c += __shfl_xor(c, sh, 64);
+            if (lane == 0 && c)
+                atomicAdd(&lh[k], (unsigned)c);
+        }
+    } else if (FORM == SCORE_BALLOT) {
+#pragma unroll
+        for (int sh = 32; sh >= 1; sh >>= 1)
+            n00 += __shfl_xor(n00, sh, 64);
+        if (lane == 0 && n00)
+            atomicAdd(&lh[0], (unsigned)n00);
+    }
+    unsigned lo0 = (unsigned)lo, lo1 = (unsigned)(lo >> 32);
+#pragma unroll
+    for (int sh = 32; sh >= 1; sh >>= 1) {
+        lo0 |= __shfl_xor(lo0, sh, 64);
+        lo1 |= __shfl_xor(lo1, sh, 64);
+    }
+    if (lane == 0) {
+        if (lo0) atomicOr(&ls[0], lo0);
+        if (lo1) atomicOr(&ls[1], lo1);
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < cl * cl; b += 256) {
+        const unsigned v = REG ? lh[(b / cl) * 5 + b % cl]
+                           : FORM == SCORE_WAVE_HIST ? lh[b] + lh[NBINS + b] + lh[2 * NBINS + b] + lh[3 * NBINS + b] : lh[b];
+        if (v)
+            atomicAdd(&a.conf[(long long)i * cl * cl + b], (unsigned long long)v);
+    }
+    if (a.seen && threadIdx.x < 4) {
+        const unsigned long long v = (unsigned long long)ls[2 * threadIdx.x] | ((unsigned long long)ls[2 * threadIdx.x + 1] << 32);
+        if (v)
+            atomicOr(&a.seen[(long long)i * 4 + threadIdx.x], v);
     }
 }
 
@@ -263,10 +412,12 @@ struct CropPipe {
         Staging<unsigned char> in, out, net;   // packed crops, packed crop-size maps, network-resolution maps
         Staging<unsigned char> ov;             // overlays (allocated on first use, sized like the packed input)
         Staging<unsigned long long> hist;
+        Staging<unsigned char> lab, gov;       // a scored call: packed labels (laid out like `out`), ground-truth overlays (like `ov`)
+        Staging<unsigned long long> score;     // its results: conf [count][classes][classes], then seen [count][4]
         bool out_direct = false, ov_direct = false;
         std::vector<gs_crop_desc> descs;
         size_t in_bytes = 0, out_bytes = 0;    // packed sizes of the batch (fill_crop_descs)
-        void free_staging() { in.free(), out.free(), net.free(), ov.free(), hist.free(); }
+        void free_staging() { in.free(), out.free(), net.free(), ov.free(), hist.free(), lab.free(), gov.free(), score.free(); }
     };
     HostPipe<Slot, 4> host;
 };
@@ -342,11 +493,51 @@ static gs_status check_common(gs_espnet *const *models, int n_models, const floa
     return GS_OK;
 }
 
+// crops_score_kernel over a complete table: zeroes conf / seen on the stream, then one launch
+static gs_status launch_score(const CropTable &tab, int n, const unsigned char *net_masks, const unsigned char *labels, int net_h,
+                              int net_w, int classes, unsigned long long *conf, unsigned long long *seen, hipStream_t s)
+{
+    const size_t conf_words = (size_t)n * classes * classes;
+    const bool joined = seen == conf + conf_words;   // the host pipeline's layout: one fill
+    GS_HIP(hipMemsetAsync(conf, 0, (conf_words + (joined ? (size_t)n * 4 : 0)) * sizeof(unsigned long long), s));
+    if (seen && !joined)
+        GS_HIP(hipMemsetAsync(seen, 0, (size_t)n * 4 * sizeof(unsigned long long), s));
+    ScoreArgs a{};
+    a.net = net_masks;
+    a.labels = labels;
+    a.conf = conf;
+    a.seen = seen;
+    a.net_h = net_h;
+    a.net_w = net_w;
+    a.classes = classes;
+    // about eight dwords of mask per thread; at the grid limit a lane makes 2^29 / (65535 * 256) < 33 iterations
+    const long long quads = (long long)net_h * net_w / 4;
+    const long long gx = std::min(std::max((quads + 8 * 256 - 1) / (8 * 256), 1ll), 65535ll);
+    const dim3 grid((unsigned)gx, (unsigned)n);
+    if (CFG_SCORE_FORM == 0 && classes <= 5)
+        hipLaunchKernelGGL(crops_score_kernel<SCORE_REG>, grid, dim3(256), 0, s, tab, a);
+    else if (CFG_SCORE_FORM == 2)
+        hipLaunchKernelGGL(crops_score_kernel<SCORE_WAVE_HIST>, grid, dim3(256), 0, s, tab, a);
+    else
+        hipLaunchKernelGGL(crops_score_kernel<SCORE_BALLOT>, grid, dim3(256), 0, s, tab, a);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
+// the device side of a gs_crop_scoring block for one batch
+struct BatchScoring {
+    const unsigned char *labels;   // packed at out_off
+    unsigned long long *conf, *seen;
+    unsigned char *gt_overlay;     // packed at in_off, or null
+    int gt_clamp;
+};
+
 // One batch, everything on stream s: the table is complete (offsets within packed_in / packed_out).
 static gs_status run_batch(gs_espnet *const *models, int n_models, int lane, const unsigned char *packed_in, const gs_crop_desc *descs,
                            int n, const float *means, const float *stds, int net_h, int net_w, unsigned char *net_masks,
                            unsigned char *packed_out, unsigned long long *hist, const gs_paste_target *paste, hipStream_t s,
-                           const gs_crop_overlay *overlay = nullptr, unsigned char *overlay_out = nullptr)
+                           const gs_crop_overlay *overlay = nullptr, unsigned char *overlay_out = nullptr,
+                           const BatchScoring *score = nullptr)
 {
     CropPipe *pipe = pipe_of(models[0]);
     GS_REQUIRE(pipe, "out of host memory");
@@ -423,18 +614,32 @@ static gs_status run_batch(gs_espnet *const *models, int n_models, int lane, con
         }
         GS_HIP(hipGetLastError());
     }
-    if (overlay && overlay_out) {   // needs the crop-size maps: the caller passes packed_out with it
+    if (score) {   // reads the network-resolution masks only
+        st = launch_score(tab, n, net_masks, score->labels, net_h, net_w, classes, score->conf, score->seen, s);
+        if (st != GS_OK) return st;
+    }
+    const bool gt_overlay = score && score->gt_overlay && overlay;
+    if ((overlay && overlay_out) || gt_overlay) {   // needs the crop-size maps: the caller passes packed_out with it
         OverlayArgs oa{};
         oa.crops = packed_in;
-        oa.maps = packed_out;
-        oa.out = overlay_out;
         oa.wa = overlay->wa;
         oa.wb = overlay->wb;
         oa.n_colours = overlay->n_colours;
         std::memcpy(oa.pal, overlay->palette_rgb, (size_t)overlay->n_colours * 3);
         const long long gx = std::min(std::max((max_hw + 8 * 1024 - 1) / (8 * 1024), 1ll), 65535ll);
-        hipLaunchKernelGGL(crops_overlay_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, s, tab, oa);
-        GS_HIP(hipGetLastError());
+        if (overlay_out) {
+            oa.maps = packed_out;
+            oa.out = overlay_out;
+            hipLaunchKernelGGL(crops_overlay_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, s, tab, oa);
+            GS_HIP(hipGetLastError());
+        }
+        if (gt_overlay) {   // the same kernel over the packed labels (VisualizeResults_iou.py:218-222)
+            oa.maps = score->labels;
+            oa.out = score->gt_overlay;
+            oa.clamp = score->gt_clamp ? 1 : 0;
+            hipLaunchKernelGGL(crops_overlay_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, s, tab, oa);
+            GS_HIP(hipGetLastError());
+        }
     }
     if (paste) {
         const unsigned gx = (unsigned)std::min<long long>((max_cells + 255) / 256, 4096);
@@ -508,6 +713,24 @@ gs_status gs_espnet_segment_crops(gs_espnet *h, int lane, const uint8_t *packed_
                      static_cast<hipStream_t>(hip_stream));
 }
 
+gs_status gs_espnet_score_crops(const uint8_t *net_masks, const uint8_t *packed_labels, const gs_crop_desc *descs, int n, int net_h,
+                                int net_w, int classes, unsigned long long *conf, unsigned long long *seen, void *hip_stream)
+{
+    GS_REQUIRE(n >= 1 && n <= MAXC, "score_crops: 1 to %d crops per call (got %d)", MAXC, n);
+    GS_REQUIRE(classes >= 2 && classes <= GS_MAX_CLASSES, "score_crops: 2 to %d classes (got %d)", GS_MAX_CLASSES, classes);
+    GS_REQUIRE(packed_labels, "score_crops: null label buffer");
+    GS_REQUIRE(conf, "score_crops: null conf");
+    GS_REQUIRE(net_masks && (reinterpret_cast<uintptr_t>(net_masks) & 3u) == 0, "score_crops: net_masks is null or not 4-byte aligned");
+    GS_REQUIRE(net_h >= 8 && net_w >= 8 && net_h % 8 == 0 && net_w % 8 == 0 && (long long)net_h * net_w < (1ll << 29),
+               "network size must be a positive multiple of 8 in both dimensions (got %dx%d)", net_h, net_w);
+    const gs_status st = check_descs(descs, n, true);
+    if (st != GS_OK) return st;
+    CropTable tab;
+    std::memset(&tab, 0, sizeof tab);
+    std::copy(descs, descs + n, tab.d);
+    return launch_score(tab, n, net_masks, packed_labels, net_h, net_w, classes, conf, seen, static_cast<hipStream_t>(hip_stream));
+}
+
 gs_status gs_plan_crop_batches(const int *heights, const int *widths, int n_crops, int batch, int *starts, int cap, int *n_batches)
 {
     GS_REQUIRE(heights && widths && n_batches, "gs_plan_crop_batches: null argument");
@@ -531,11 +754,29 @@ gs_status gs_espnet_segment_crops_host(gs_espnet *const *models, int n_models, c
                                        int batch, uint8_t *const *masks, uint8_t *net_masks, unsigned long long *hist,
                                        const gs_paste_target *paste, const int *x1, const int *y1, const gs_crop_overlay *overlay)
 {
+    return gs_espnet_segment_crops_host_scored(models, n_models, crops, heights, widths, n_crops, means, stds, net_h, net_w, batch, masks,
+                                               net_masks, hist, paste, x1, y1, overlay, nullptr);
+}
+
+gs_status gs_espnet_segment_crops_host_scored(gs_espnet *const *models, int n_models, const uint8_t *const *crops, const int *heights,
+                                              const int *widths, int n_crops, const float *means, const float *stds, int net_h,
+                                              int net_w, int batch, uint8_t *const *masks, uint8_t *net_masks,
+                                              unsigned long long *hist, const gs_paste_target *paste, const int *x1, const int *y1,
+                                              const gs_crop_overlay *overlay, const gs_crop_scoring *scoring)
+{
+    if (scoring) {   // (its own refusals first: they need no handle)
+        GS_REQUIRE(scoring->labels, "scoring: null label list");
+        GS_REQUIRE(scoring->conf, "scoring: null conf");
+        for (int i = 0; i < n_crops; ++i)
+            GS_REQUIRE(scoring->labels[i] && (!scoring->gt_overlay_bgr || scoring->gt_overlay_bgr[i]),
+                       "scoring: crop %d has a null label or no ground-truth overlay buffer", i);
+        GS_REQUIRE(!scoring->gt_overlay_bgr || overlay, "scoring: a ground-truth overlay needs the overlay argument's palette and weights");
+    }
     gs_status st = check_common(models, n_models, means, stds, net_h, net_w);
     if (st != GS_OK) return st;
     GS_REQUIRE(crops && heights && widths && n_crops > 0, "segment_crops_host: null crop list");
     GS_REQUIRE(batch > 0, "batch must be positive");
-    GS_REQUIRE(masks || net_masks || hist || paste || overlay, "nothing to compute: every output is NULL");
+    GS_REQUIRE(masks || net_masks || hist || paste || overlay || scoring, "nothing to compute: every output is NULL");
     GS_REQUIRE(!paste || (x1 && y1), "a paste target needs the crops' level-0 origins");
     if (overlay) {
         GS_REQUIRE(overlay->palette_rgb && overlay->out_bgr && overlay->n_colours >= 1 && overlay->n_colours <= GS_MAX_PALETTE,
@@ -558,6 +799,8 @@ gs_status gs_espnet_segment_crops_host(gs_espnet *const *models, int n_models, c
         if (espnet_lanes(models[k]) < 2) nl = 1;
     const size_t npx = (size_t)net_h * net_w;
     const size_t ncl = (size_t)espnet_classes(models[0]);   // hist is [n_crops][classes]
+    const size_t ncc = ncl * ncl;                           // conf is [n_crops][classes][classes]
+    uint8_t *const *gt_ov = scoring ? scoring->gt_overlay_bgr : nullptr;
     // which crops go into which batch, and the staging a batch needs (csrc/crop_plan.h: host-only, sanitised on its own)
     const CropBatchPlan plan = plan_crop_batches(heights, widths, n_crops, batch, MAXC);
     const std::vector<int> &starts = plan.starts;
@@ -572,6 +815,11 @@ gs_status gs_espnet_segment_crops_host(gs_espnet *const *models, int n_models, c
             s.net.grow(npx * batch, fail);
             s.hist.grow(sizeof(unsigned long long) * GS_MAX_CLASSES * batch, fail);
             if (overlay) s.ov.grow(s.in.bytes, fail);
+            if (scoring) {
+                s.lab.grow(s.out.bytes, fail);
+                s.score.grow(sizeof(unsigned long long) * (GS_MAX_CLASSES * GS_MAX_CLASSES + 4) * batch, fail);
+                if (gt_ov) s.gov.grow(s.in.bytes, fail);
+            }
         }))
         return fail.rc;
     const bool net_pinned = net_masks && host_is_pinned(net_masks), hist_pinned = hist && host_is_pinned(hist);
@@ -620,11 +868,25 @@ gs_status gs_espnet_segment_crops_host(gs_espnet *const *models, int n_models, c
                 });
                 fail(hipMemcpyAsync(s.in.d, s.in.h, s.in_bytes, hipMemcpyHostToDevice, h2d), "H2D copy");
             }
+            if (scoring) {   // the labels ride with the crops: packed like the crop-size maps, one copy
+                parallel_jobs(cnt, 4, [&](int j) {
+                    std::memcpy(s.lab.h + s.descs[j].out_off, scoring->labels[first + j], (size_t)s.descs[j].h * s.descs[j].w);
+                });
+                fail(hipMemcpyAsync(s.lab.d, s.lab.h, s.out_bytes, hipMemcpyHostToDevice, h2d), "H2D copy");
+            }
         },
         [&](int bi, Slot &s, hipStream_t compute) {
+            BatchScoring bs{};
+            if (scoring) {
+                bs.labels = s.lab.d;
+                bs.conf = s.score.d;
+                bs.seen = s.score.d + (size_t)s.count * ncc;
+                bs.gt_overlay = gt_ov ? s.gov.d : nullptr;
+                bs.gt_clamp = scoring->gt_clamp;
+            }
             return run_batch(models, n_models, bi % nl, s.in.d, s.descs.data(), s.count, means, stds, net_h, net_w, s.net.d,
                              (masks || overlay) ? s.out.d : nullptr, hist ? s.hist.d : nullptr, paste, compute, overlay,
-                             overlay ? s.ov.d : nullptr);
+                             overlay ? s.ov.d : nullptr, scoring ? &bs : nullptr);
         },
         [&](int, Slot &s, hipStream_t compute) {
             const int first = s.first, cnt = s.count;
@@ -648,6 +910,12 @@ gs_status gs_espnet_segment_crops_host(gs_espnet *const *models, int n_models, c
             if (net_masks)
                 fail(hipMemcpy2DAsync(net_pinned ? net_masks + (size_t)first * npx : s.net.h, npx, s.net.d, npx, npx, cnt,
                                       hipMemcpyDeviceToHost, compute), "D2H copy");
+            if (gt_ov)
+                fail(hipMemcpy2DAsync(s.gov.h, oi, s.gov.d, oi, oi, 1, hipMemcpyDeviceToHost, compute), "D2H copy");
+            if (scoring) {
+                const size_t b = sizeof(unsigned long long) * (ncc + 4) * cnt;
+                fail(hipMemcpy2DAsync(s.score.h, b, s.score.d, b, b, 1, hipMemcpyDeviceToHost, compute), "D2H copy");
+            }
             if (hist) {
                 const size_t b = sizeof(unsigned long long) * ncl * cnt;
                 fail(hipMemcpy2DAsync(hist_pinned ? hist + (size_t)first * ncl : s.hist.h, b, s.hist.d, b, b, 1, hipMemcpyDeviceToHost,
@@ -667,6 +935,16 @@ gs_status gs_espnet_segment_crops_host(gs_espnet *const *models, int n_models, c
                 parallel_memcpy(net_masks + (size_t)s.first * npx, s.net.h, npx * s.count);
             if (hist && !hist_pinned)
                 std::memcpy(hist + (size_t)s.first * ncl, s.hist.h, sizeof(unsigned long long) * ncl * s.count);
+            if (gt_ov)
+                parallel_jobs(s.count, 4, [&](int j) {
+                    std::memcpy(gt_ov[s.first + j], s.gov.h + s.descs[j].in_off, (size_t)s.descs[j].h * s.descs[j].w * 3);
+                });
+            if (scoring) {
+                std::memcpy(scoring->conf + (size_t)s.first * ncc, s.score.h, sizeof(unsigned long long) * ncc * s.count);
+                if (scoring->seen)
+                    std::memcpy(scoring->seen + (size_t)s.first * 4, s.score.h + (size_t)s.count * ncc,
+                                sizeof(unsigned long long) * 4 * s.count);
+            }
         });
     return rc != GS_OK ? rc : gs_device_fault_check();
 }

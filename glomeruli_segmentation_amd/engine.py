@@ -228,6 +228,8 @@ class EspnetEngine:
                 masks.ctypes.data_as(ctypes.c_void_p), hist.ctypes.data_as(ctypes.c_void_p) if want_hist else None))
         return masks, (hist.astype(np.int64) if want_hist else None)
 
+    scores_crops = True      # segment_crops takes labels= / want_gt_overlay= (segment.segment_batch asks)
+
     def segment_crops(self, crops, mean, std, net_h=512, net_w=1024, batch=32, **kw):
         """The loop of VisualizeResults_iou.py:100-156 over crops of ANY sizes (numpy uint8 BGR [h,w,3] each, or pinned CPU
         tensors) through the library's batched pipeline; see segment_crops_host for the keywords and the result."""
@@ -357,8 +359,38 @@ def paste_target(slide_map, ds=8, luts=None):
     return t
 
 
+def seen_values(seen_words):
+    """the sorted uint8 values of a 256-bit set as gs_espnet_score_crops writes it (uint64 [4], bit v of word v // 64): np.unique of
+    the label the set was collected from"""
+    bits = np.unpackbits(np.ascontiguousarray(seen_words, dtype="<u8").view(np.uint8), bitorder="little")
+    return np.nonzero(bits)[0].astype(np.uint8)
+
+
+def score_crops_resident(net_masks, packed_labels, descs, classes, want_seen=True):
+    """Device-resident scoring stage (gs_espnet_score_crops), on the current stream: net_masks uint8 [n,net_h,net_w] and
+    packed_labels (uint8, crop i's [h,w] label at descs[i].out_off) on the GPU, descs a list of _lib.CropDesc ->
+    (conf int64 [n,classes,classes], rows = ground truth; seen int64 [n,4] bit sets | None), GPU tensors."""
+    lib = _lib.load()
+    n, net_h, net_w = (int(v) for v in net_masks.shape)
+    if n != len(descs):
+        raise ValueError("%d masks for %d descriptors" % (n, len(descs)))
+    if net_masks.dtype != torch.uint8 or packed_labels.dtype != torch.uint8 or not net_masks.is_contiguous() or not packed_labels.is_contiguous():
+        raise ValueError("expected contiguous uint8 GPU tensors")
+    need = max(int(d.out_off) + int(d.h) * int(d.w) for d in descs)
+    if packed_labels.numel() < need:
+        raise ValueError("packed_labels holds %d bytes, the descriptors reach %d" % (packed_labels.numel(), need))
+    dev = net_masks.device
+    tab = (_lib.CropDesc * n)(*descs)
+    conf = torch.empty((n, classes, classes), dtype=torch.int64, device=dev)
+    seen = torch.empty((n, 4), dtype=torch.int64, device=dev) if want_seen else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.gs_espnet_score_crops(net_masks.data_ptr(), packed_labels.data_ptr(), tab, n, net_h, net_w, classes,
+                                             conf.data_ptr(), seen.data_ptr() if seen is not None else None, _stream_ptr(dev)))
+    return conf, seen
+
+
 def segment_crops_host(engines, mean_stds, crops, net_h=512, net_w=1024, batch=32, want_masks=True, want_net_maps=False,
-                       want_hist=True, paste=None, origins=None, overlay=None):
+                       want_hist=True, paste=None, origins=None, overlay=None, labels=None, want_gt_overlay=False):
     """gs_espnet_segment_crops_host: crops of any sizes in host memory -> per-crop class maps at crop size.
 
     engines: one EspnetEngine (the plain model) or several (the cfg-5 ensemble, each with its own (mean, std) in mean_stds):
@@ -371,11 +403,22 @@ def segment_crops_host(engines, mean_stds, crops, net_h=512, net_w=1024, batch=3
     cv2.addWeighted(crop, wa, colour, wb, 0) (VisualizeResults_iou.py:139-146), computed on the GPU for the whole batch.
     Returns dict(masks=list of uint8 [h,w] numpy views of one pinned buffer | None, net_maps=uint8 [n,net_h,net_w] | None,
     counts=int64 [n,classes] counts of the crop-size maps | None, overlays=list of uint8 [h,w,3] BGR views | None).
+    labels: one uint8 [h,w] numpy array per crop, of the crop's size: the batch is also SCORED on the GPU
+    (gs_espnet_segment_crops_host_scored, VisualizeResults_iou.py:195-203): the dict gains conf (int64 [n,classes,classes]: the
+    confusion matrix, rows = ground truth, of the network-resolution map and the label nearest-resized to the network size) and
+    seen (list of sorted uint8 arrays: np.unique of that resized label); with want_gt_overlay (needs `overlay`) also gt_overlays,
+    the label coloured and blended like the prediction (:218-222; a value beyond the palette takes its last row).  Without
+    labels the three are None.
     """
     lib = _lib.load()
     n = len(crops)
+    if labels is not None and len(labels) != n:
+        raise ValueError("%d labels for %d crops" % (len(labels), n))
+    if want_gt_overlay and (labels is None or overlay is None):
+        raise ValueError("want_gt_overlay needs labels and overlay")
     if n == 0:
-        return {"masks": [] if want_masks else None, "net_maps": None, "counts": None, "overlays": [] if overlay is not None else None}
+        return {"masks": [] if want_masks else None, "net_maps": None, "counts": None, "overlays": [] if overlay is not None else None,
+                "conf": None, "seen": [] if labels is not None else None, "gt_overlays": [] if want_gt_overlay else None}
     keep = []      # keeps converted inputs alive for the duration of the call
     ptrs = (ctypes.c_void_p * n)()
     hs, ws = (ctypes.c_int * n)(), (ctypes.c_int * n)()
@@ -427,14 +470,38 @@ def segment_crops_host(engines, mean_stds, crops, net_h=512, net_w=1024, batch=3
         ov_ptrs = (ctypes.c_void_p * n)(*[ov_buf.data_ptr() + int(ov_offs[i]) for i in range(n)])
         ov.out_bgr = ctypes.cast(ov_ptrs, ctypes.POINTER(ctypes.c_void_p))
         keep.append(ov_ptrs)
+    sc, conf, seen, gt_buf = None, None, None, None
+    if labels is not None:
+        lab_ptrs = (ctypes.c_void_p * n)()
+        for i, lb in enumerate(labels):
+            if not isinstance(lb, np.ndarray) or lb.dtype != np.uint8 or lb.shape != (int(hs[i]), int(ws[i])):
+                raise ValueError("label %d: expected a uint8 [%d,%d] array" % (i, int(hs[i]), int(ws[i])))
+            lb = np.ascontiguousarray(lb)
+            keep.append(lb)
+            lab_ptrs[i] = lb.ctypes.data
+        conf = np.zeros((n, eng0.classes, eng0.classes), dtype=np.uint64)
+        seen = np.zeros((n, 4), dtype=np.uint64)
+        sc = _lib.CropScoring()
+        sc.labels = ctypes.cast(lab_ptrs, ctypes.POINTER(ctypes.c_void_p))
+        sc.conf, sc.seen = conf.ctypes.data, seen.ctypes.data
+        sc.gt_clamp = 1
+        keep.append(lab_ptrs)
+        if want_gt_overlay:     # laid out like the overlays
+            gt_buf = torch.empty(int(ov_offs[-1]), dtype=torch.uint8, pin_memory=True)
+            gt_ptrs = (ctypes.c_void_p * n)(*[gt_buf.data_ptr() + int(ov_offs[i]) for i in range(n)])
+            sc.gt_overlay_bgr = ctypes.cast(gt_ptrs, ctypes.POINTER(ctypes.c_void_p))
+            keep.append(gt_ptrs)
     for e in engines:
         e.quiesce()
-    with torch.cuda.device(eng0.device):
-        _lib.check(lib.gs_espnet_segment_crops_host(
-            handles, len(engines), ptrs, hs, ws, n, means, stds, net_h, net_w, batch, out_ptrs,
+    args = (handles, len(engines), ptrs, hs, ws, n, means, stds, net_h, net_w, batch, out_ptrs,
             ctypes.c_void_p(net.data_ptr()) if net is not None else None,
             ctypes.c_void_p(hist.data_ptr()) if hist is not None else None,
-            ctypes.byref(paste) if paste is not None else None, x1, y1, ctypes.byref(ov) if ov is not None else None))
+            ctypes.byref(paste) if paste is not None else None, x1, y1, ctypes.byref(ov) if ov is not None else None)
+    with torch.cuda.device(eng0.device):
+        if sc is None:
+            _lib.check(lib.gs_espnet_segment_crops_host(*args))
+        else:
+            _lib.check(lib.gs_espnet_segment_crops_host_scored(*args, ctypes.byref(sc)))
     masks = None
     if want_masks:
         flat = out_buf.numpy()
@@ -443,8 +510,14 @@ def segment_crops_host(engines, mean_stds, crops, net_h=512, net_w=1024, batch=3
     if ov is not None:
         flat = ov_buf.numpy()
         overlays = [flat[int(ov_offs[i]):int(ov_offs[i]) + int(hs[i]) * int(ws[i]) * 3].reshape(int(hs[i]), int(ws[i]), 3) for i in range(n)]
+    gt_overlays = None
+    if gt_buf is not None:
+        flat = gt_buf.numpy()
+        gt_overlays = [flat[int(ov_offs[i]):int(ov_offs[i]) + int(hs[i]) * int(ws[i]) * 3].reshape(int(hs[i]), int(ws[i]), 3) for i in range(n)]
     return {"masks": masks, "net_maps": net.numpy() if net is not None else None,
-            "counts": hist.numpy() if hist is not None else None, "overlays": overlays}
+            "counts": hist.numpy() if hist is not None else None, "overlays": overlays,
+            "conf": conf.astype(np.int64) if conf is not None else None,
+            "seen": [seen_values(seen[i]) for i in range(n)] if seen is not None else None, "gt_overlays": gt_overlays}
 
 
 def ensemble_segment(engines, tiles_u8, mean_stds):

@@ -43,6 +43,21 @@ def segment_crops(engine, crops, mean, std, net_h, net_w, batch=32, paste=None, 
     return r["masks"], r["counts"]
 
 
+def segment_crops_scored(engine, crops, labels, mean, std, net_h, net_w, batch=32, overlay=None, want_gt_overlay=False, **kw):
+    """segment_crops for labelled crops (labels: one uint8 [h,w] array per crop, of the crop's size): the batch is also scored on
+    the GPU (gs_espnet_segment_crops_host_scored).  Returns the whole result dict of engine.segment_crops_host -- masks, counts,
+    conf (int64 [n,classes,classes], rows = ground truth), seen (np.unique of every label at network resolution) and, with
+    `overlay` (palette, wa, wb), overlays and (want_gt_overlay) gt_overlays.  engine, mean, std and **kw (paste, origins, want_masks,
+    want_net_maps) as for segment_crops."""
+    if isinstance(engine, (list, tuple)):
+        if len(mean) != len(engine) or len(std) != len(engine):
+            raise ValueError("an ensemble of %d engines needs %d mean and std triples" % (len(engine), len(engine)))
+        from .engine import segment_crops_host
+        return segment_crops_host(list(engine), list(zip(mean, std)), crops, net_h, net_w, batch, overlay=overlay, labels=labels,
+                                  want_gt_overlay=want_gt_overlay, **kw)
+    return engine.segment_crops(crops, mean, std, net_h, net_w, batch, overlay=overlay, labels=labels, want_gt_overlay=want_gt_overlay, **kw)
+
+
 def run_slide(engine, read_region, slide_w, slide_h, mpp_x, mpp_y, detector, mean, std, window_um=2000, overlap=0.1,
               conf_threshold=0.2, overlap_threshold=0.35, objective_power=40, level_downsamples=(1.0, 2.0, 4.0, 8.0),
               net_h=512, net_w=1024, rank=0, world=1, dist=None, batch=32, detector_batch=1):

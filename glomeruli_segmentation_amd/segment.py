@@ -86,14 +86,32 @@ def metric_right(hist):
 OVERLAY_WEIGHTS = (0.4, 0.6)      # cv2.addWeighted(img_orig, 0.4, classMap_numpy_color, 0.6, 0), VisualizeResults_iou.py:145
 
 
-def segment_batch(engine, images, mean, std, width, height, batch, want_net_maps=False, want_overlay=False):
+def can_score(engine, images, labels):
+    """whether a labelled batch takes the scored GPU path: the engine's segment_crops scores (engine.scores_crops) and every crop
+    has a label that is a 2-D uint8 array of the crop's size; any other batch is scored on the host as before"""
+    return bool(images) and getattr(engine, "scores_crops", False) and hasattr(engine, "segment_crops") and \
+        labels is not None and len(labels) == len(images) and \
+        all(isinstance(lb, np.ndarray) and lb.dtype == np.uint8 and lb.ndim == 2 and lb.shape == im.shape[:2]
+            for im, lb in zip(images, labels))
+
+
+def segment_batch(engine, images, mean, std, width, height, batch, want_net_maps=False, want_overlay=False, labels=None):
     """What the loop body needs from the GPU for one batch of crops (:107-129, :139-146, :151-155), as a dict:
     masks (crop-size class maps), net_maps (network-resolution maps | None), counts (int64 [n, classes]: pixels per class of the
     crop-size maps) and overlays (the palette-coloured map blended over the crop, BGR | None) -- counts and overlays come out of
     the batched crop pipeline with the maps (gs_espnet_segment_crops_host: crops_back_kernel counts, crops_overlay_kernel
     blends), the host only encodes.  ESPNet-C (modelType 2) goes the same way: its maps come out of the library's head kernel where
     the full network's come out of the decoder tail.  An engine without the batched entry (the CPU tests' stand-ins) gets its maps
-    from segment_images and the two by-products from _byproducts."""
+    from segment_images and the two by-products from _byproducts.
+    labels (one per crop; the caller has checked can_score): the batch is scored in the same GPU pass (crops_score_kernel: the
+    label's nearest resize to the network size, the confusion matrix against the network-resolution map and np.unique of the
+    resized label, :195-203; a second crops_overlay_kernel launch for the ground-truth overlay, :218-222) and the dict also
+    holds conf (int64 [n, classes, classes]), seen (list of sorted value arrays) and gt_overlays."""
+    if labels is not None:
+        r = engine.segment_crops(images, mean, std, height, width, batch, want_masks=True, want_net_maps=want_net_maps, want_hist=True,
+                                 overlay=(imageops.PALETTE, OVERLAY_WEIGHTS[0], OVERLAY_WEIGHTS[1]), labels=labels, want_gt_overlay=True)
+        return {"masks": r["masks"], "net_maps": list(r["net_maps"]) if want_net_maps else None, "counts": r["counts"],
+                "overlays": r["overlays"], "conf": r["conf"], "seen": r["seen"], "gt_overlays": r["gt_overlays"]}
     if not hasattr(engine, "segment_crops") or not images:
         masks, net = segment_images(engine, images, mean, std, width, height, batch, want_net_maps=True)
         counts, overlays = _byproducts(engine, images, masks, want_overlay)
@@ -187,13 +205,14 @@ STAGE_SECONDS = None          # tools/bench_cli.py sets a dict here to collect t
 _STAGE_LOCK = threading.Lock()
 
 
-def _emit_crop(args, img_name, label_name, img, cmap, net_map, lab, lab_r, counts, overlayed):
+def _emit_crop(args, img_name, label_name, img, cmap, net_map, lab, lab_r, counts, overlayed, scored=None):
     """Everything the loop body writes for ONE crop after the forward (:131-231): overlay / original images, the counts row,
     the class map, the labelme JSON, with a label the per-image accuracy row and the combined image.  Host work only -- PNG /
     JPEG encoding, contour tracing, base64 -- and no state shared with other crops, so it runs on a worker thread while the
     GPU is busy with the next batch.  `counts` (pixels per class of the crop-size map, :151-155) and `overlayed` (:139-146; None
     when neither --colored nor a label asks for it) arrive from the GPU pass.  Returns what the summary files need: (pixel row,
-    accuracy row | None, (patient, label values) | None, confusion matrix | None)."""
+    accuracy row | None, (patient, label values) | None, confusion matrix | None).  `scored` = (hist, uniq, ground-truth overlay)
+    when the GPU pass scored the crop (segment_batch with labels): net_map and lab_r are then None."""
     from PIL import Image
     from .contours import labelme_dict
     patient = os.path.basename(os.path.dirname(img_name))
@@ -227,8 +246,13 @@ def _emit_crop(args, img_name, label_name, img, cmap, net_map, lab, lab_r, count
         return row_pixel, None, None, None
     # the reference scores at network resolution (:195-203): the label is nearest-resized to the network size (lab_r, made on
     # the GPU by the caller) and compared with img_out.max(1)[1] itself, NOT with the map that went to crop size and back
-    hist = confusion(net_map.ravel(), lab_r.ravel(), args.classes)
-    uniq = np.unique(lab_r)
+    if scored is not None:
+        hist, uniq, gt_overlayed = scored
+    else:
+        hist = confusion(net_map.ravel(), lab_r.ravel(), args.classes)
+        uniq = np.unique(lab_r)
+        gt_colour = imageops.colourise(np.minimum(lab, len(imageops.PALETTE) - 1).astype(np.uint8))
+        gt_overlayed = imageops.add_weighted(img, 0.4, gt_colour, 0.6)
     _, _, per_iu, _ = metric_right(hist)
     union = hist.sum(1) + hist.sum(0) - np.diag(hist)
     miou_each = np.nanmean(np.diag(hist)[uniq] / union[uniq])                               # :208-209
@@ -236,8 +260,7 @@ def _emit_crop(args, img_name, label_name, img, cmap, net_map, lab, lab_r, count
     row_acc = "{}/{},{},{},{},{},{},{},{},{},{},{}\n".format(
         patient, name.replace(args.img_extn, 'png'), *flags, *per_iu[:5], miou_each)
     # original | ground truth overlay | prediction overlay (:215-231)
-    gt_colour = imageops.colourise(np.minimum(lab, len(imageops.PALETTE) - 1).astype(np.uint8))
-    combined = np.concatenate([img, imageops.add_weighted(img, 0.4, gt_colour, 0.6), overlayed], axis=1)
+    combined = np.concatenate([img, gt_overlayed, overlayed], axis=1)
     cdir = os.path.join(args.savedir, "combined_images", patient)
     os.makedirs(cdir, exist_ok=True)
     imageops.imwrite_bgr(os.path.join(cdir, name.replace(args.img_extn, 'png')), combined)
@@ -299,9 +322,11 @@ def evaluate(args, engine, rgb_list, label_list, rank=0, world=1, dist=None):
             if bi + 1 < len(starts):      # decode ahead
                 nxt = load(starts[bi + 1])
             want_overlay = bool(args.colored or any(l_ is not None for l_ in label_names))      # (:139, :215-231)
+            # a fully labelled batch of uint8 maps is scored in the GPU pass itself; the network-resolution maps then stay there
+            scored = all(l_ is not None for l_ in label_names) and can_score(engine, images, labels)
             t_gpu = time.perf_counter()
-            r = segment_batch(engine, images, mean, std, args.inWidth, args.inHeight, args.batch, want_net_maps=True,
-                              want_overlay=want_overlay)
+            r = segment_batch(engine, images, mean, std, args.inWidth, args.inHeight, args.batch, want_net_maps=not scored,
+                              want_overlay=want_overlay, **({"labels": labels} if scored else {}))
             if STAGE_SECONDS is not None:
                 with _STAGE_LOCK:
                     STAGE_SECONDS["gpu_pass"] = STAGE_SECONDS.get("gpu_pass", 0.0) + time.perf_counter() - t_gpu
@@ -314,6 +339,9 @@ def evaluate(args, engine, rgb_list, label_list, rank=0, world=1, dist=None):
                     continue
                 assert os.path.basename(img_name) == os.path.basename(label_name)
                 assert lab.shape[:2] == img.shape[:2]
+                if scored:      # (hist, uniq and the ground-truth overlay came out of the GPU pass)
+                    labs_r.append(None)
+                    continue
                 if lab.shape[:2] == (args.inHeight, args.inWidth):
                     labs_r.append(lab)
                 else:
@@ -321,9 +349,14 @@ def evaluate(args, engine, rgb_list, label_list, rank=0, world=1, dist=None):
                     from .engine import mask_resize_nearest
                     labs_r.append(mask_resize_nearest(torch.from_numpy(np.array(lab, dtype=np.uint8)).to(engine.device),
                                                       args.inHeight, args.inWidth).cpu().numpy())      # :195 cv2.resize INTER_NEAREST
+            if net_maps is None:
+                net_maps = [None] * len(images)
+            extra = [None] * len(images) if not scored else \
+                [(np.array(cf), np.array(sn), np.array(go)) for cf, sn, go in zip(r["conf"], r["seen"], r["gt_overlays"])]
             futs = [run(_emit_crop, args, n_, l_, im, np.array(cm), np.array(nm) if nm is not None else None, lb, lr,
-                        [int(v) for v in cn], None if ov is None else np.array(ov))
-                    for n_, l_, im, cm, nm, lb, lr, cn, ov in zip(names, label_names, images, masks, net_maps, labels, labs_r, counts, overlays)]
+                        [int(v) for v in cn], None if ov is None else np.array(ov), ex)
+                    for n_, l_, im, cm, nm, lb, lr, cn, ov, ex in zip(names, label_names, images, masks, net_maps, labels, labs_r, counts,
+                                                                      overlays, extra)]
             # (np.array: the maps and overlays are views of the pipeline's pinned output buffers, which the next call may reuse)
             pending.append(futs)
             if len(pending) > 2:          # write behind: at most two batches of outputs in flight

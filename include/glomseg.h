@@ -41,7 +41,10 @@ const char *gs_last_error(void);
 /* ABI version, bumped on any change of a signature or of what an entry accepts (8: the forward-plan entries;
  * 7: ESPNet-C handles give masks and counts).  ABI 8 libraries from the commit that added csrc/enc_head_ens.h on also accept
  * ensembles whose members are all ESPNet-C handles (below); the number was not bumped for that: no signature changed, and a
- * caller finds out by the call itself (an older ABI 8 library answers GS_ERR_INVALID). */
+ * caller finds out by the call itself (an older ABI 8 library answers GS_ERR_INVALID).  Likewise not bumped for the two entries
+ * of glomseg_scoring.h (scoring of labelled crops in the batched crop pass: gs_espnet_score_crops and
+ * gs_espnet_segment_crops_host_scored, of which gs_espnet_segment_crops_host below is the call with a NULL scoring block): they
+ * are additions with a header of their own, and a caller finds out by looking the symbols up. */
 int gs_abi_version(void);
 /* How the library was compiled: GS_BUILD_DIAG = a -DGS_DIAG experiment build (timing variants that return wrong results by
  * construction can be switched on through the environment); the product library returns 0 and reads no environment. */

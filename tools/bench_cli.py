@@ -11,7 +11,14 @@ with the default worker pool (decode-ahead / write-behind while a batch is on th
 rank's share of the cores on an 8-GPU node.  The work is host-bound -- PNG decode and three PNG / JPEG encodes per crop against
 ~0.1 ms of GPU time -- so the figure scales with the cores the process has; the core count is in the line.  The serial run also
 gives the per-stage breakdown of the host time (segment.STAGE_SECONDS): decode / GPU pass (counts and overlays included) /
-overlay JPEG / original PNG / class-map PNG / contours / base64 PNG / JSON."""
+overlay JPEG / original PNG / class-map PNG / contours / base64 PNG / JSON.
+
+    python tools/bench_cli.py --labelled [--crops 128] [--out FILE]
+
+The labelled leg: the same crops with a uint8 label map of every crop's size beside them, `--label_data_dir` given.  Per run it
+reports the wall time, the seconds inside the GPU pass (segment.segment_batch) and the main-thread seconds between a GPU pass and
+the first crop's host work -- where the per-crop label resizes (launch, blocking download) sit when the batch is not scored in the
+GPU pass.  It uses nothing of the scored path's interface, so the same file measures a checkout from before it."""
 import argparse
 import json
 import os
@@ -31,6 +38,8 @@ def main():
     ap.add_argument("--crops", type=int, default=448)
     ap.add_argument("--out", default=None)
     ap.add_argument("--keep", action="store_true")
+    ap.add_argument("--labelled", action="store_true", help="the labelled leg only (--label_data_dir)")
+    ap.add_argument("--repeat", type=int, default=2, help="labelled leg: timed runs per mode")
     a = ap.parse_args()
     from PIL import Image
     from glomeruli_segmentation_amd import segment
@@ -53,6 +62,9 @@ def main():
         mean, std = FOLD_MEAN_STD[1]
         common = ["--rgb_data_dir", rgb, "--weights", wpath, "--gpu_id", "0", "--classes", "5", "--img_extn", "PNG", "--decoder",
                   "--colored", "--overlay", "--cityFormat", "--mean"] + [str(v) for v in mean] + ["--std"] + [str(v) for v in std]
+        if a.labelled:
+            labelled_leg(a, segment, base, rgb, root, common)
+            return
         res = {}
         cores = segment.default_workers()
         allowed = sorted(os.sched_getaffinity(0))
@@ -100,6 +112,60 @@ def main():
     finally:
         if not a.keep:
             shutil.rmtree(root, ignore_errors=True)
+
+
+def labelled_leg(a, segment, base, rgb, root, common):
+    from PIL import Image
+    lab = os.path.join(root, "label")
+    for i in range(a.crops):
+        d = os.path.join(lab, "slide%02d" % (i // 56))
+        os.makedirs(d, exist_ok=True)
+        tile = base[i % len(base)]
+        Image.fromarray(((tile[:, :, 1] < 150) * (1 + (tile[:, :, 0] // 64) % 4)).astype(np.uint8)).save(
+            os.path.join(d, "xmin%d_ymin%d_xmax%d_ymax%d.PNG" % (i, i, i + 100, i + 100)), compress_level=1)
+    # timestamps around the GPU pass and at the first crop's host work behind it
+    marks = {"gpu": 0.0, "between": 0.0, "exit": None, "batches": 0}
+    real_batch, real_emit = segment.segment_batch, segment._emit_crop
+    import threading
+    lock = threading.Lock()          # with --workers > 0 _emit_crop runs on pool threads
+
+    def timed_batch(*args, **kw):
+        t0 = time.perf_counter()
+        r = real_batch(*args, **kw)
+        with lock:
+            marks["exit"] = time.perf_counter()
+            marks["gpu"] += marks["exit"] - t0
+            marks["batches"] += 1
+        return r
+
+    def timed_emit(*args, **kw):
+        with lock:
+            t, marks["exit"] = marks["exit"], None
+            if t is not None:
+                marks["between"] += time.perf_counter() - t
+        return real_emit(*args, **kw)
+    segment.segment_batch, segment._emit_crop = timed_batch, timed_emit
+    runs = []
+    cores = segment.default_workers()
+    for tag, workers in [("warmup", cores)] + [("serial", 0), ("overlapped", cores)] * a.repeat:
+        out = os.path.join(root, "out_lab_" + tag)
+        shutil.rmtree(out, ignore_errors=True)
+        marks.update(gpu=0.0, between=0.0, exit=None, batches=0)
+        t0 = time.perf_counter()
+        rc = segment.main(common + ["--label_data_dir", lab, "--savedir", out, "--workers", str(workers)])
+        el = time.perf_counter() - t0
+        assert rc == 0
+        rec = {"mode": tag, "workers": workers, "wall_s": round(el, 3), "gpu_pass_s": round(marks["gpu"], 4),
+               "main_thread_between_batches_s": round(marks["between"], 4), "batches": marks["batches"]}
+        print(rec, flush=True)
+        if tag != "warmup":
+            runs.append(rec)
+    line = {"what": "segment --label_data_dir end to end, %d labelled PNG crops of the example slide's sizes, batch 32" % a.crops,
+            "crops": a.crops, "host_cores_of_the_process": cores, "runs": runs}
+    print(json.dumps(line))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(line, f, indent=1)
 
 
 if __name__ == "__main__":
