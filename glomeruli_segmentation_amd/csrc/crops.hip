@@ -4,7 +4,7 @@
 // kernel argument, so a call allocates nothing, copies nothing and is stream-ordered like any other launch.
 //
 //   crops_prep_kernel    :107-116  (x - mean) / std at crop resolution -> cv2.resize INTER_LINEAR -> / 255 -> fp32 NCHW
-//   (forward)            :123,128  espnet_forward_ex: the mask comes out of the decoder tail (ESPNet-C: of enc_head_kernel; an ensemble
+//   (forward)            :123,128  espnet_forward: the mask comes out of the decoder tail (ESPNet-C: of enc_head_kernel; an ensemble
 //                                  of ESPNet-C members: K trunks, then one enc_head_ens_kernel), no logits
 //   crops_back_kernel    :129,151-155  cv2.resize INTER_NEAREST back to every crop's size + per-class counts of THAT map
 //   crops_paste_kernel   eval_wsi_segmentation.py:311-312  np.max into the 1/ds slide map
@@ -404,8 +404,6 @@ struct CropPipe {
         size_t f32_bytes = 0;
         unsigned char *net = nullptr;   // network-resolution masks when the caller keeps none
         size_t net_bytes = 0;
-        float *prob = nullptr;          // ensemble accumulator [n,classes,net_h,net_w]
-        size_t prob_bytes = 0;
     } lane[4];
     // host pipeline (host_pipe.h): four slots
     struct Slot : PipeSlot {
@@ -430,7 +428,6 @@ void crop_pipe_destroy(CropPipe *p)
     for (auto &l : p->lane) {
         if (l.f32) hipFree(l.f32);
         if (l.net) hipFree(l.net);
-        if (l.prob) hipFree(l.prob);
     }
     delete p;
 }
@@ -446,26 +443,6 @@ static CropPipe *pipe_of(gs_espnet *h)
     return p;
 }
 
-template <typename T>
-static gs_status grow(T *&buf, size_t &have, size_t need, const char *what)
-{
-    if (have >= need)
-        return GS_OK;
-    if (buf) {
-        GS_HIP(hipDeviceSynchronize());   // work in flight may still use the old buffer
-        GS_HIP(hipFree(buf));
-        buf = nullptr;
-        have = 0;
-    }
-    if (hipMalloc(reinterpret_cast<void **>(&buf), need) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("%s allocation of %zu bytes failed", what, need);
-        return GS_ERR_NOMEM;
-    }
-    have = need;
-    return GS_OK;
-}
-
 static gs_status check_common(gs_espnet *const *models, int n_models, const float *means, const float *stds, int net_h, int net_w)
 {
     GS_REQUIRE(models && n_models > 0 && means && stds, "segment_crops: null argument");
@@ -474,7 +451,7 @@ static gs_status check_common(gs_espnet *const *models, int n_models, const floa
     for (int k = 0; k < n_models; ++k)
         GS_REQUIRE(models[k], "model %d is null", k);
     if (n_models > 1) {
-        // all full networks, or all ESPNet-C handles (at most GS_MAX_ENSEMBLE_C, run_batch: one head over their logits).
+        // all full networks, or all ESPNet-C handles (at most GS_MAX_ENSEMBLE_C, run_ensemble: one head over their logits).
         // A mixed list is refused HERE, in the crop entries' own words; ensemble_kind below (shared with
         // gs_espnet_ensemble_forward) would refuse it too, with that entry's text, and is never reached with one: what it
         // adds for the crop entries is the class counts, the member limit and the repeated handle.
@@ -555,12 +532,6 @@ static gs_status run_batch(gs_espnet *const *models, int n_models, int lane, con
         if (st != GS_OK) return st;
         net_masks = ls.net;
     }
-    // an ensemble of ESPNet-C members has no accumulator: its members' 1/8-scale logits stay in their workspaces
-    const bool ens_c = n_models > 1 && !espnet_is_full_net(models[0]);
-    if (n_models > 1 && !ens_c) {
-        st = grow(ls.prob, ls.prob_bytes, (size_t)n * classes * npx * sizeof(float), "ensemble accumulator");
-        if (st != GS_OK) return st;
-    }
     CropTable tab;
     std::memset(&tab, 0, sizeof tab);
     long long max_hw = 1, max_cells = 1;
@@ -571,7 +542,8 @@ static gs_status run_batch(gs_espnet *const *models, int n_models, int lane, con
             max_cells = std::max(max_cells, (long long)(descs[i].w / paste->ds + 3) * (descs[i].h / paste->ds + 3));
     }
     const dim3 prep_grid((unsigned)((net_h * (net_w / 4) + 255) / 256), (unsigned)n);
-    for (int k = 0; k < n_models; ++k) {
+    // member k resamples the crops with its own mean / std into the lane's tensor; the first launch also zeroes the counts
+    auto prepare = [&](int k) -> gs_status {
         PrepArgs a{};
         a.in = packed_in;
         a.out = ls.f32;
@@ -587,20 +559,20 @@ static gs_status run_batch(gs_espnet *const *models, int n_models, int lane, con
         }
         hipLaunchKernelGGL(crops_prep_kernel, prep_grid, dim3(256), 0, s, tab, a);
         GS_HIP(hipGetLastError());
-        if (ens_c) {   // the member's trunk only
-            st = espnet_c_trunk(models[k], lane, ls.f32, GS_IN_F32_NCHW, n, net_h, net_w, nullptr, nullptr, nullptr, s);
-            if (st != GS_OK) return st;
-            continue;
-        }
-        const int mode = n_models == 1 ? 0 : k == 0 ? 1 : k == n_models - 1 ? 3 : 2;
-        st = espnet_forward_ex(models[k], lane, ls.f32, GS_IN_F32_NCHW, n, net_h, net_w, nullptr, nullptr, nullptr, net_masks, nullptr,
-                               n_models > 1 ? ls.prob : nullptr, mode, 1.0f / (float)n_models, s);
-        if (st != GS_OK) return st;
+        return GS_OK;
+    };
+    ForwardReq r;   // the network-resolution masks only: the counts are those of the crop-size maps (crops_back_kernel)
+    r.in = ls.f32, r.n = n, r.H = net_h, r.W = net_w, r.mask = net_masks, r.s = s;
+    if (n_models > 1) {
+        st = run_ensemble(models, n_models, lane, r, nullptr, nullptr, prepare);
+    } else {
+        // NOT the runner's one-member ensemble (role SOLE): a single crop model takes the argmax of its logits (role NONE, as
+        // gs_espnet_forward does), a one-member ensemble takes the argmax of its softmax, and the two can differ where fp32
+        // rounds two close logits to equal probabilities.
+        st = prepare(0);
+        if (st == GS_OK) st = espnet_forward(models[0], lane, r);
     }
-    if (ens_c) {   // one head over the K members' logits writes the network-resolution masks
-        st = espnet_c_ensemble_head(models, n_models, lane, n, net_h, net_w, net_masks, nullptr, s);
-        if (st != GS_OK) return st;
-    }
+    if (st != GS_OK) return st;
     if (packed_out || hist) {
         long long gx = (max_hw + 8 * 1024 - 1) / (8 * 1024);   // about eight iterations per workgroup, never more than 512
         gx = std::max(gx, (max_hw + 512 * 1024 - 1) / (512 * 1024));

@@ -377,7 +377,7 @@ __global__ void __launch_bounds__(WAVES * 64) dec_tail_kernel(const DecTailArgs 
                     // (yo >= yb: the rows a shifted last band shares with its neighbour belong to the neighbour -- a mask store may
                     // be repeated, an accumulation may not)
                     if (ok && yo >= yb) {
-                        if (a.ens_mode == 2 || a.ens_mode == 3) {
+                        if (ens_reads(a.ens_mode)) {
 #pragma unroll
                             for (int o = 0; o < CLS; ++o) {
                                 const float4 old = *reinterpret_cast<const float4 *>(
@@ -388,7 +388,7 @@ __global__ void __launch_bounds__(WAVES * 64) dec_tail_kernel(const DecTailArgs 
                                 pr[o][3] = old.w + pr[o][3];
                             }
                         }
-                        if (a.ens_mode == 1 || a.ens_mode == 2) {
+                        if (ens_writes(a.ens_mode)) {
 #pragma unroll
                             for (int o = 0; o < CLS; ++o)
                                 *reinterpret_cast<float4 *>(a.prob + (((long long)n * CLS + o) * H + 2 * yo + dy) * W + 2 * x) =

@@ -19,11 +19,9 @@ struct DecTailArgs {
     float *ff;            // optional: the CBR output (stage "conv") as a gs::Act
     long long ff_sn;
     int ff_sc, ff_pitch, ff_off;
-    // ensemble (BASELINE cfg 5, definition in DESIGN.md): prob [N][CLS][2*H1][2*W1] accumulates ens_w * softmax(logits) over the
-    // member models.  ens_mode 1: first member (store), 2: a middle member (add), 3: the last member (add, then argmax of the
-    // sum -> mask + counts; nothing is written back), 4: a single member (softmax -> argmax, prob untouched).  0: no ensemble.
+    // ensemble: prob [N][CLS][2*H1][2*W1] accumulates ens_w * softmax(logits) over the member models
     float *prob;
-    int ens_mode;
+    int ens_mode;         // an EnsRole (gs_internal.h)
     float ens_w;
     int N, H1, W1;
     int xbase, nstrips;   // this launch covers strips of 16P-2 output columns starting at column xbase

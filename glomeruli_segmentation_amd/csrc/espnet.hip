@@ -77,7 +77,7 @@ struct Model {
     float stem_params[537] = {0};   // host copy of level1 weights + folded bn1 + folded b1: they travel as kernel arguments
     long long w1, bn1, b1, b2, b3, wcls, br, wup3, w3c, cbr0, wcc, bncc, wup2, bnu2, wclassifier, wtail;
     long long wconv = -1;   // the generic decoder tail's conv_mfma image (class counts other than five)
-    long long wcc_mfma = -1;   // twelve classes and more: combine_l2_l3.1 as a conv_mfma image (see forward_impl)
+    long long wcc_mfma = -1;   // twelve classes and more: combine_l2_l3.1 as a conv_mfma image (see decode)
     PackedConv l2_0;
     std::vector<PackedConv> l2, l3;
     PackedConv l3_0;
@@ -87,9 +87,16 @@ struct Model {
     size_t ws_bytes = 0;
     int ws_n = 0, ws_h = 0, ws_w = 0;
     Act a0c, a0, inp1, inp2, r2[2], bb[3], a1, r3[2], cc[3], o2c, tt, t3, ee, ff;
-    float *prob = nullptr;   // ensemble scratch
+    float *prob = nullptr;   // ensemble scratch of this lane (ensemble_scratch: the first member's handle owns it)
     size_t prob_bytes = 0;
     std::map<std::string, std::pair<Act, int>> stages;   // name -> (activation, channels) of the last forward
+    // a ping-pong buffer that is written again no longer holds the stage recorded for it earlier
+    void set_stage(const std::string &name, const Act &act, int C)
+    {
+        for (auto it = stages.begin(); it != stages.end();)
+            it = it->second.first.base == act.base ? stages.erase(it) : std::next(it);
+        stages[name] = {act, C};
+    }
     int last_n = 0;
     bool b2_lazy = false;    // planes 64..127 of the stage "b2" are not materialised by the last forward (read_stage fills them)
 
@@ -409,7 +416,7 @@ static ConvArgs conv_args(const Act &in, const float *wpack, const Act &out, con
 static inline unsigned blocks_for(long long items) { return (unsigned)((items + 255) / 256); }
 
 // Timing / stamp variants of the forward (GS_VARIANT: ablations, per-wave stamps, the kernels a round replaced) live in
-// espnet_diag.inc and exist in -DGS_DIAG builds only.  forward_impl offers them its launch sites through GS_DIAG_TRY; in the
+// espnet_diag.inc and exist in -DGS_DIAG builds only.  The forward offers them its launch sites through GS_DIAG_TRY; in the
 // product build that macro expands to nothing (its arguments are not even evaluated), so what follows is the shipped
 // schedule and nothing else.
 #ifdef GS_DIAG
@@ -428,7 +435,7 @@ static inline unsigned blocks_for(long long items) { return (unsigned)((items + 
 
 // ------------------------------------------------------------------------------------------
 // The per-class dispatch: every conv_mfma_kernel instantiation of the forward is spelled here, once -- one `case` per form of
-// forward_plan.h's table.  forward_impl and the single-block hook (gs_espnet_block_forward) launch through these and decide
+// forward_plan.h's table.  The forward (encode / decode) and the single-block hook (gs_espnet_block_forward) launch through these and decide
 // nothing themselves; the caller has put the second / third output of a fused form into `ca` (with_dual / with_fused).
 static gs_status not_planned(const char *launch_class)
 {
@@ -588,32 +595,24 @@ static gs_status launch_dec_conv(const Model *m, form::dec_conv f, const ConvArg
     return not_planned("dec_conv");
 }
 
-template <int CLS>
-static gs_status forward_impl(Model *m, const void *in, int in_format, int n, int H, int W, const float *mean,
-                              const float *stdv, float *logits, uint8_t *mask, unsigned long long *hist, hipStream_t s,
-                              float *prob = nullptr, int ens_mode = 0, float ens_w = 1.0f)
+// The forward is the encoder (stem .. the last level-3 block), the same code for every class count, then the decoder instantiated
+// for the padded class count (forward_any).  What the decoder needs of the encoder's run: cc[last] holds the last block's output
+struct Encoded { int last; bool lazy_b2; };
+static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const ForwardReq &r)
 {
     const float *wb = m->dblob;
-    Launcher L{m, s, GS_OK, n};
-    const ForwardPlan plan = plan_forward(n, H, W, m->p, m->q, CLS, m->num_cus, no_vec());   // every choice of a kernel form
-    const int H1 = H / 2, W1 = W / 2, H2 = H / 4, W2 = W / 4, H3 = H / 8, W3 = W / 8;
+    const hipStream_t s = r.s;
+    const int n = r.n, H = r.H, W = r.W, H1 = H / 2, W1 = W / 2, H2 = H / 4, W2 = W / 4, H3 = H / 8, W3 = W / 8;
     const double px1 = (double)H1 * W1, px2 = (double)H2 * W2, px3 = (double)H3 * W3;
     m->stages.clear();
     m->last_n = n;
-    // a ping-pong buffer that is written again no longer holds the stage recorded for it earlier
-    auto set_stage = [&](const std::string &name, const Act &act, int C) {
-        for (auto it = m->stages.begin(); it != m->stages.end();)
-            it = it->second.first.base == act.base ? m->stages.erase(it) : std::next(it);
-        m->stages[name] = {act, C};
-    };
-
     // ---- stem (Model.py:346-350)
     L.run(K_STEM, px1 * (27 * 16 * 2), [&] {
         StemArgs a{};
-        a.in = in;
+        a.in = r.in;
         for (int i = 0; i < 3; ++i) {
-            a.mean[i] = mean ? mean[i] : 0.0f;
-            a.std[i] = stdv ? stdv[i] : 1.0f;
+            a.mean[i] = r.mean ? r.mean[i] : 0.0f;
+            a.std[i] = r.stdv ? r.stdv[i] : 1.0f;
         }
         std::memcpy(a.w1, m->stem_params, sizeof(float) * 432);
         std::memcpy(a.bn1, m->stem_params + 432, sizeof(float) * 48);
@@ -623,14 +622,12 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
         a.N = n;
         a.H = H;
         a.W = W;
-        if (hist && (ens_mode == 0 || ens_mode >= 3)) {   // zeroed by the first kernel of the forward; the last one adds into it
-            a.hist_zero = hist;
+        if (r.hist && ens_finishes((int)r.role)) {   // zeroed by the first kernel of the forward; the last one adds into it
+            a.hist_zero = r.hist;
             a.hist_count = n * m->classes;
         }
-        if (in_format == GS_IN_U8_BGR_NHWC)
-            hipLaunchKernelGGL(stem_kernel<true>, dim3(blocks_for((long long)n * H1 * ((W1 + STEM_PX - 1) / STEM_PX))), dim3(256), 0, s, a);
-        else
-            hipLaunchKernelGGL(stem_kernel<false>, dim3(blocks_for((long long)n * H1 * ((W1 + STEM_PX - 1) / STEM_PX))), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(r.in_format == GS_IN_U8_BGR_NHWC ? stem_kernel<true> : stem_kernel<false>,
+                           dim3(blocks_for((long long)n * H1 * ((W1 + STEM_PX - 1) / STEM_PX))), dim3(256), 0, s, a);
         return GS_OK;
     });
     L.run(K_POOL, 0, [&] {
@@ -638,8 +635,8 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
                            view(m->inp2), n, 3, m->p > 0 ? wb + m->b2 : nullptr, view(m->a1), 128, 131);
         return GS_OK;
     });
-    set_stage("b1", m->a0, 19);
-    set_stage("sample2", m->inp2, 3);
+    m->set_stage("b1", m->a0, 19);
+    m->set_stage("sample2", m->inp2, 3);
 
     // ---- level 2 (Model.py:351-357): DownSamplerB(19,64) then p ESP blocks
     L.run(K_L2_C1S, px2 * (19 * 9 * 12 * 2), [&] {
@@ -680,7 +677,7 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
     });
     bool have_r2 = m->l2_0.fused_next;   // the reduced map of the next block already exists
     rd2 ^= have_r2 ? 1 : 0;
-    set_stage("level2_0", m->bb[0], 64);
+    m->set_stage("level2_0", m->bb[0], 64);
     int cur2 = 0;
     for (int i = 0; i < m->p; ++i) {
         const int nxt = cur2 == 1 ? 2 : 1;
@@ -700,7 +697,7 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
         rd2 ^= have_r2 ? 1 : 0;
         cur2 = nxt;
         if (!last)
-            set_stage("level2." + std::to_string(i), m->bb[cur2], 64);
+            m->set_stage("level2." + std::to_string(i), m->bb[cur2], 64);
     }
     if (plan.cat_b2 == form::cat_b2::KERNEL) {
         L.run(K_CAT_B2, 0, [&] {
@@ -709,7 +706,7 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
             return GS_OK;
         });
     }
-    set_stage("b2", m->a1, 131);
+    m->set_stage("b2", m->a1, 131);
 
     // ---- level 3 (Model.py:361-366)
     int rd3 = 0;
@@ -727,9 +724,9 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
         return launch_l3_down(m, plan.l3_down, m->l3_0.fused_next ? with_fused(ca, m->r3[rd3 ^ 1], 25) : ca, s);
     });
     bool have_r3 = m->l3_0.fused_next;
-    set_stage("level3_reduce", m->r3[rd3], 25);      // (debug: valid until the second ESP block overwrites the map)
+    m->set_stage("level3_reduce", m->r3[rd3], 25);      // (debug: valid until the second ESP block overwrites the map)
     rd3 ^= have_r3 ? 1 : 0;
-    set_stage("level3_0", m->cc[0], 128);
+    m->set_stage("level3_0", m->cc[0], 128);
     int cur3 = 0;
     for (int i = 0; i < m->q; ++i) {
         const int nxt = cur3 == 1 ? 2 : 1;
@@ -748,18 +745,28 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
         have_r3 = fuse_next;
         rd3 ^= have_r3 ? 1 : 0;
         cur3 = nxt;
-        set_stage("level3." + std::to_string(i), m->cc[cur3], 128);
+        m->set_stage("level3." + std::to_string(i), m->cc[cur3], 128);
     }
+    return {cur3, lazy_b2};
+}
 
+// dec1_kernel .. the class map and the counts (ESPNet-C: dec1_kernel, then the head when a mask is asked for)
+template <int CLS>
+static gs_status decode(Model *m, Launcher &L, const ForwardPlan &plan, const ForwardReq &r, const Encoded &enc)
+{
+    const float *wb = m->dblob;
+    const hipStream_t s = r.s;
+    const int n = r.n, H = r.H, W = r.W, H1 = H / 2, W1 = W / 2, H2 = H / 4, W2 = W / 4, H3 = H / 8, W3 = W / 8;
+    const double px1 = (double)H1 * W1, px2 = (double)H2 * W2, px3 = (double)H3 * W3;
     // ---- b3 + classifier (+ br + up_l3)  (Model.py:368-370)
     const int ncls = m->classes;   // real class count (CLS is the padded one): algorithmic FLOPs, output widths
     // ESPNet-C: the 1/8-scale logits are an output of their own and the input of the head; a caller that wants the class map
     // only gets them in the (otherwise unused) up_l3 buffer of the workspace, which is larger than [n][classes][H3][W3]
-    float *enc_logits = !m->encoder_only ? nullptr : logits ? logits : m->o2c.base;
+    float *enc_logits = !m->encoder_only ? nullptr : r.logits ? r.logits : m->o2c.base;
     L.run(K_DEC1, px3 * (256 * ncls * 2) + px3 * (ncls * ncls * 4 * 2), [&] {
         Dec1Args a{};
         a.c0 = view(m->cc[0]);
-        a.clast = view(m->cc[cur3]);
+        a.clast = view(m->cc[enc.last]);
         a.b3w = wb + m->b3;
         a.br = m->encoder_only ? nullptr : wb + m->br;
         a.wup = m->encoder_only ? nullptr : wb + m->wup3;
@@ -774,12 +781,12 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
     });
     if (m->encoder_only) {
         // ---- x8 bilinear upsampling + argmax + counts (VisualizeResults_iou.py:125-128,151-155,258-261), enc_head.h
-        if (mask)
+        if (r.mask)
             L.run(K_ENC_HEAD, (double)H * W * (ncls * 6), [&] {
                 EncHeadArgs a{};
                 a.logits = enc_logits;
-                a.mask = mask;
-                a.hist = hist;
+                a.mask = r.mask;
+                a.hist = r.hist;
                 a.classes = ncls;
                 a.H3 = H3;
                 a.W3 = W3;
@@ -788,7 +795,7 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
             });
         return L.st;
     }
-    set_stage("up_l3", m->o2c, ncls);
+    m->set_stage("up_l3", m->o2c, ncls);
 
     // ---- level3_C + cat + BR (Model.py:372-373)
     L.run(K_DEC2, px2 * (131 * ncls * 2), [&] {
@@ -797,7 +804,7 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
         a.raw = view(m->bb[0]);
         a.b2 = wb + m->b2;
         a.raw_c0 = 64;
-        a.raw_cn = lazy_b2 ? 64 : 0;
+        a.raw_cn = enc.lazy_b2 ? 64 : 0;
         a.o2c = view(m->o2c);
         a.w3c = wb + m->w3c;
         a.br = wb + m->cbr0;
@@ -808,7 +815,7 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
         return GS_OK;
     });
     if (ncls == CLS)   // (with padding planes in between the two halves are not one contiguous stage)
-        set_stage("combine_t", m->tt, 2 * CLS);
+        m->set_stage("combine_t", m->tt, 2 * CLS);
     // ---- CBR(2c,c,3) + up_l2 (Model.py:373)
     if constexpr (dec3_on_mfma(CLS)) {
         // many classes: the 3x3 over 2 * CLS planes is 7 200 FMAs per pixel at twenty classes -- on the matrix cores (a plain
@@ -842,7 +849,7 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
             return GS_OK;
         });
     }
-    set_stage("up_l2", m->ee, ncls);
+    m->set_stage("up_l2", m->ee, ncls);
     // ---- conv CBR(19+c,c,3) + classifier deconv + argmax + counts (Model.py:375-377, VisualizeResults_iou.py:128,151-155)
     if constexpr (dec_tail_fused(CLS)) {
         L.run(K_DEC_TAIL, px1 * ((19 + CLS) * 9 * CLS * 2) + px1 * (CLS * CLS * 4 * 2), [&] {
@@ -854,13 +861,13 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
             a.in_off = m->a0c.off;
             a.in_img_bytes = (unsigned)(m->a0c.sn * sizeof(float));
             a.wpack = wb + m->wtail;
-            a.logits = logits;
-            a.mask = mask;
-            a.hist = (ens_mode == 1 || ens_mode == 2) ? nullptr : hist;   // only the last member of an ensemble counts
-            a.prob = prob;
-            a.ens_mode = ens_mode;
-            a.ens_w = ens_w;
-            if (logits) {   // debug / test path: the half-resolution CBR output is kept as stage "conv"
+            a.logits = r.logits;
+            a.mask = r.mask;
+            a.hist = ens_finishes((int)r.role) ? r.hist : nullptr;   // only the last member of an ensemble counts
+            a.prob = r.prob;
+            a.ens_mode = (int)r.role;
+            a.ens_w = r.ens_w;
+            if (r.logits) {   // debug / test path: the half-resolution CBR output is kept as stage "conv"
                 a.ff = m->ff.base;
                 a.ff_sn = m->ff.sn;
                 a.ff_sc = m->ff.sc;
@@ -872,8 +879,8 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
             a.W1 = W1;
             return launch_dec_tail(a, m->num_cus, s);
         });
-        if (logits)
-            set_stage("conv", m->ff, CLS);
+        if (r.logits)
+            m->set_stage("conv", m->ff, CLS);
     } else {
         // Any other class count (Model.py:311: `classes` is free, 20 by default): the 3x3 over the 19 + classes planes of the concat
         // buffer as a plain conv_mfma launch (MFMA rows = the padded output channels, BN + PReLU in its epilogue), then the
@@ -881,24 +888,21 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
         L.run(K_DEC_CONV, px1 * ((19 + ncls) * 9 * ncls * 2), [&] {
             return launch_dec_conv<CLS>(m, plan.dec_conv, conv_args(m->a0c, wb + m->wconv, m->ff, nullptr, n), s);
         });
-        set_stage("conv", m->ff, ncls);
+        m->set_stage("conv", m->ff, ncls);
         L.run(K_DEC4, px1 * (ncls * ncls * 4 * 2), [&] {
             Dec4Args a{};
             a.f = view(m->ff);
             a.wcl = wb + m->wclassifier;
-            a.logits = logits;
-            a.mask = mask;
-            a.hist = hist;
-            a.prob = prob;
-            a.ens_mode = ens_mode;
-            a.ens_w = ens_w;
+            a.logits = r.logits;
+            a.mask = r.mask;
+            a.hist = r.hist;
+            a.prob = r.prob;
+            a.ens_mode = (int)r.role;
+            a.ens_w = r.ens_w;
             a.N = n;
             a.classes = ncls;
             const dim3 grid(blocks_for(((long long)H1 * W1 + dec4_px<CLS>() - 1) / dec4_px<CLS>()), n);
-            if (ens_mode)
-                hipLaunchKernelGGL((dec4_kernel<CLS, true>), grid, dim3(256), 0, s, a);
-            else
-                hipLaunchKernelGGL((dec4_kernel<CLS, false>), grid, dim3(256), 0, s, a);
+            hipLaunchKernelGGL((r.role != EnsRole::NONE ? dec4_kernel<CLS, true> : dec4_kernel<CLS, false>), grid, dim3(256), 0, s, a);
             return GS_OK;
         });
     }
@@ -906,17 +910,18 @@ static gs_status forward_impl(Model *m, const void *in, int in_format, int n, in
 }
 
 // the decoder kernels exist for the padded class counts 4, 5, 8, 12, 16, 20 (Model::cp)
-static gs_status forward_any(Model *m, const void *in, int in_format, int n, int H, int W, const float *mean, const float *stdv,
-                             float *logits, uint8_t *mask, unsigned long long *hist, hipStream_t s, float *prob = nullptr,
-                             int ens_mode = 0, float ens_w = 1.0f)
+static gs_status forward_any(Model *m, const ForwardReq &r)
 {
+    Launcher L{m, r.s, GS_OK, r.n};
+    const ForwardPlan plan = plan_forward(r.n, r.H, r.W, m->p, m->q, m->cp, m->num_cus, no_vec());   // every choice of a kernel form
+    const Encoded e = encode(m, L, plan, r);
     switch (m->cp) {
-    case 5: return forward_impl<5>(m, in, in_format, n, H, W, mean, stdv, logits, mask, hist, s, prob, ens_mode, ens_w);
-    case 4: return forward_impl<4>(m, in, in_format, n, H, W, mean, stdv, logits, mask, hist, s, prob, ens_mode, ens_w);
-    case 8: return forward_impl<8>(m, in, in_format, n, H, W, mean, stdv, logits, mask, hist, s, prob, ens_mode, ens_w);
-    case 12: return forward_impl<12>(m, in, in_format, n, H, W, mean, stdv, logits, mask, hist, s, prob, ens_mode, ens_w);
-    case 16: return forward_impl<16>(m, in, in_format, n, H, W, mean, stdv, logits, mask, hist, s, prob, ens_mode, ens_w);
-    case 20: return forward_impl<20>(m, in, in_format, n, H, W, mean, stdv, logits, mask, hist, s, prob, ens_mode, ens_w);
+    case 5: return decode<5>(m, L, plan, r, e);
+    case 4: return decode<4>(m, L, plan, r, e);
+    case 8: return decode<8>(m, L, plan, r, e);
+    case 12: return decode<12>(m, L, plan, r, e);
+    case 16: return decode<16>(m, L, plan, r, e);
+    case 20: return decode<20>(m, L, plan, r, e);
     }
     set_error("internal: no decoder instantiation for %d padded classes", m->cp);
     return GS_ERR_UNSUPPORTED;
@@ -979,49 +984,24 @@ int espnet_device(gs_espnet *h) { return h->m.device; }
 int espnet_is_full_net(gs_espnet *h) { return h->m.encoder_only ? 0 : 1; }
 int espnet_lanes(gs_espnet *h) { return 1 + (int)h->lanes.size(); }
 int espnet_classes(gs_espnet *h) { return h->m.classes; }
-// the ensemble's fp32 probability accumulator [n][classes][height][width], owned by the first member's handle
-gs_status ensemble_scratch(gs_espnet *h, int n, int height, int width, float **prob)
+// the ensemble's fp32 probability accumulator [n][classes][height][width] of lane `lane`, owned by the first member's handle (one
+// per lane: the crop host pipeline has two lanes' batches in flight on two streams)
+static gs_status ensemble_scratch(gs_espnet *h, int lane, int n, int height, int width, float **prob)
 {
-    Model &m0 = h->m;
-    const size_t need = (size_t)n * m0.classes * height * width * sizeof(float);
-    if (m0.prob_bytes < need) {
-        if (m0.prob) {
-            GS_HIP(hipDeviceSynchronize());
-            GS_HIP(hipFree(m0.prob));
-        }
-        m0.prob = nullptr;
-        m0.prob_bytes = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&m0.prob), need) != hipSuccess) {
-            set_error("ensemble scratch allocation of %zu bytes failed", need);
-            return GS_ERR_NOMEM;
-        }
-        m0.prob_bytes = need;
-    }
+    GS_REQUIRE(lane >= 0 && lane <= (int)h->lanes.size(), "lane %d does not exist (gs_espnet_set_lanes)", lane);
+    Model &m0 = h->lane(lane);
+    const gs_status st = grow(m0.prob, m0.prob_bytes, (size_t)n * m0.classes * height * width * sizeof(float), "ensemble scratch");
     *prob = m0.prob;
-    return GS_OK;
+    return st;
 }
-// the forward with every option (ensemble accumulator included); arguments are the caller's responsibility beyond the
-// checks of gs_espnet_forward_lane
-gs_status espnet_forward_ex(gs_espnet *h, int lane, const void *in, int in_format, int n, int height, int width, const float *mean,
-                            const float *stdv, float *logits, uint8_t *mask, unsigned long long *hist, float *prob, int ens_mode,
-                            float ens_w, hipStream_t s)
+gs_status espnet_forward(gs_espnet *h, int lane, const ForwardReq &r)
 {
-    GS_REQUIRE(h && in, "forward: null handle or input");
+    GS_REQUIRE(h && r.in, "forward: null handle or input");
     GS_REQUIRE(lane >= 0 && lane <= (int)h->lanes.size(), "lane %d does not exist (gs_espnet_set_lanes)", lane);
     Model &m = h->lane(lane);
-    GS_REQUIRE(!m.encoder_only || ens_mode == 0, "an ESPNet-C handle cannot be an ensemble member");
-    gs_status st = layout_workspace(&m, n, height, width);
-    if (st != GS_OK) return st;
-    return forward_any(&m, in, in_format, n, height, width, mean, stdv, logits, mask, hist, s, prob, ens_mode, ens_w);
-}
-
-// ---- ESPNet-C ensembles (enc_head_ens.h).  A member's trunk is its plain forward with no output asked for: it stops after
-// dec1_kernel with its 1/8-scale logits in the up_l3 buffer of its own workspace (forward_impl, `enc_logits`), and `hist`, given
-// to the first member, is zeroed by that member's stem.
-gs_status espnet_c_trunk(gs_espnet *h, int lane, const void *in, int in_format, int n, int height, int width, const float *mean,
-                         const float *stdv, unsigned long long *hist_zero, hipStream_t s)
-{
-    return espnet_forward_ex(h, lane, in, in_format, n, height, width, mean, stdv, nullptr, nullptr, hist_zero, nullptr, 0, 1.0f, s);
+    GS_REQUIRE(!m.encoder_only || r.role == EnsRole::NONE, "an ESPNet-C handle cannot be an ensemble member");
+    const gs_status st = layout_workspace(&m, r.n, r.H, r.W);
+    return st != GS_OK ? st : forward_any(&m, r);
 }
 
 // what a list of members is: GS_OK and *enc_only (all full / all ESPNet-C), or the refusal of a mixed list, of members that
@@ -1050,32 +1030,57 @@ gs_status ensemble_kind(gs_espnet *const *models, int n_models, bool *enc_only)
     return GS_OK;
 }
 
-// the one head launch behind the K trunks of lane `lane`: class map and counts from the members' logits where they lie
-gs_status espnet_c_ensemble_head(gs_espnet *const *models, int n_models, int lane, int n, int height, int width, uint8_t *mask,
-                                 unsigned long long *hist, hipStream_t s)
+// ESPNet-C ensembles (enc_head_ens.h): the one head launch behind the K trunks of lane `lane`, class map and counts from the
+// members' 1/8-scale logits where they lie (the up_l3 buffer of each member's workspace: decode, `enc_logits`); `r`: the ensemble's request
+static gs_status espnet_c_ensemble_head(gs_espnet *const *models, int n_models, int lane, const ForwardReq &r)
 {
     EncHeadEnsArgs a{};
     for (int k = 0; k < n_models; ++k) {
-        GS_REQUIRE(lane >= 0 && lane <= (int)models[k]->lanes.size(), "member %d has no lane %d (gs_espnet_set_lanes)", k, lane);
         const Model &mk = models[k]->lane(lane);
-        GS_REQUIRE(mk.encoder_only && mk.ws && n <= mk.ws_n && height == mk.ws_h && width == mk.ws_w,
+        GS_REQUIRE(mk.encoder_only && mk.ws && r.n <= mk.ws_n && r.H == mk.ws_h && r.W == mk.ws_w,
                    "internal: member %d holds no 1/8-scale logits of this batch", k);
         a.logits[k] = mk.o2c.base;
     }
-    a.mask = mask;
-    a.hist = hist;
+    a.mask = r.mask;
+    a.hist = r.hist;
     a.classes = models[0]->m.classes;
     a.members = n_models;
-    a.H3 = height / 8;
-    a.W3 = width / 8;
+    a.H3 = r.H / 8;
+    a.W3 = r.W / 8;
     a.inv_members = 1.0f / (float)n_models;
     Model &m0 = models[0]->lane(lane);   // (the profiler of the first member times the head)
-    Launcher L{&m0, s, GS_OK, n};
-    L.run(K_ENC_HEAD_ENS, (double)height * width * (a.classes * n_models * 20), [&] {
-        launch_ens_head(a, n, s);
+    Launcher L{&m0, r.s, GS_OK, r.n};
+    L.run(K_ENC_HEAD_ENS, (double)r.H * r.W * (a.classes * n_models * 20), [&] {
+        launch_ens_head(a, r.n, r.s);
         return GS_OK;
     });
     return L.st;
+}
+
+gs_status run_ensemble(gs_espnet *const *models, int n_models, int lane, const ForwardReq &shared, const float *means,
+                       const float *stds, const std::function<gs_status(int)> &prepare)
+{
+    const bool enc_only = models[0]->m.encoder_only;   // (ensemble_kind: then every member is)
+    ForwardReq r = shared;
+    r.ens_w = 1.0f / (float)n_models;
+    // Full networks: every member's decoder tail turns its logits into probabilities in registers and adds 1/K of them into ONE
+    // fp32 accumulator (the first member stores, middle members add, the last adds and goes on to the argmax and the counts): the
+    // logits are never written, and the accumulator is read K-1 and written K-1 times.
+    // ESPNet-C members: the K trunks one after the other on the call's stream -- a trunk is a forward that is asked for no mask
+    // (ForwardReq::hist) -- then ONE head over their 1/8-scale logits.  No accumulator; K = 1 runs the same code.
+    gs_status st = GS_OK;
+    if (!enc_only && (st = ensemble_scratch(models[0], lane, r.n, r.H, r.W, &r.prob)) != GS_OK) return st;
+    for (int k = 0; k < n_models; ++k) {
+        if (prepare && (st = prepare(k)) != GS_OK) return st;
+        r.mean = means ? means + 3 * k : nullptr, r.stdv = stds ? stds + 3 * k : nullptr;
+        if (enc_only)   // (the first trunk's stem zeroes what the head counts into)
+            r.mask = nullptr, r.hist = k == 0 ? shared.hist : nullptr;
+        else
+            r.role = ens_role(k, n_models);
+        st = espnet_forward(models[k], lane, r);
+        if (st != GS_OK) return st;
+    }
+    return enc_only ? espnet_c_ensemble_head(models, n_models, lane, shared) : GS_OK;
 }
 }  // namespace gs
 
@@ -1302,26 +1307,26 @@ gs_status gs_espnet_create(const float *blob, const gs_layer_desc *table, int n_
     return GS_OK;
 }
 
+// what a lane owns on the device (the weight blob is the handle's); the caller has synchronised
+static void free_lane(Model &l)
+{
+    for (auto &ev : l.events) {
+        hipEventDestroy(ev.a);
+        hipEventDestroy(ev.b);
+    }
+    if (l.ws) hipFree(l.ws);
+    if (l.prob) hipFree(l.prob);
+}
+
 void gs_espnet_destroy(gs_espnet *h)
 {
     if (!h)
         return;
     hipDeviceSynchronize();
-    for (auto &ev : h->m.events) {
-        hipEventDestroy(ev.a);
-        hipEventDestroy(ev.b);
-    }
     h->tile_pipe.destroy();
     crop_pipe_destroy(h->crop_pipe);
-    for (auto &l : h->lanes) {
-        for (auto &ev : l->events) {
-            hipEventDestroy(ev.a);
-            hipEventDestroy(ev.b);
-        }
-        if (l->ws) hipFree(l->ws);
-    }
-    if (h->m.ws) hipFree(h->m.ws);
-    if (h->m.prob) hipFree(h->m.prob);
+    for (int k = 0; k <= (int)h->lanes.size(); ++k)
+        free_lane(h->lane(k));
     if (h->m.dblob) hipFree(h->m.dblob);
     delete h;
 }
@@ -1352,7 +1357,7 @@ gs_status gs_espnet_set_lanes(gs_espnet *h, int n_lanes)
     GS_REQUIRE(n_lanes >= 1 && n_lanes <= 4, "gs_espnet_set_lanes: 1 to 4 lanes (got %d)", n_lanes);
     GS_HIP(hipDeviceSynchronize());
     while ((int)h->lanes.size() > n_lanes - 1) {
-        if (h->lanes.back()->ws) hipFree(h->lanes.back()->ws);
+        free_lane(*h->lanes.back());
         h->lanes.pop_back();
     }
     while ((int)h->lanes.size() < n_lanes - 1) {
@@ -1389,16 +1394,16 @@ gs_status gs_espnet_forward_lane(gs_espnet *h, int lane, const void *in, int in_
     if (st != GS_OK) return st;
     GS_REQUIRE(in_format == GS_IN_U8_BGR_NHWC || in_format == GS_IN_F32_NCHW, "unknown input format %d", in_format);
     GS_REQUIRE(in_format != GS_IN_U8_BGR_NHWC || (mean && std), "uint8 input needs mean and std");
-    Model &m = h->lane(lane);
     // (an ESPNet-C handle's logits are the 1/8-scale ones; its mask and counts come from the head kernel, enc_head.h)
     GS_REQUIRE(logits || mask, "nothing to compute: logits and mask are both NULL");
     GS_REQUIRE(!hist || mask, "hist requires the mask output");
     if (in_format == GS_IN_U8_BGR_NHWC)
         for (int i = 0; i < 3; ++i)
             GS_REQUIRE(std[i] != 0.0f, "std[%d] is zero", i);
-    st = layout_workspace(&m, n, height, width);
-    if (st != GS_OK) return st;
-    return forward_any(&m, in, in_format, n, height, width, mean, std, logits, mask, hist, static_cast<hipStream_t>(hip_stream));
+    ForwardReq r;
+    r.in = in, r.in_format = in_format, r.n = n, r.H = height, r.W = width;
+    r.mean = mean, r.stdv = std, r.logits = logits, r.mask = mask, r.hist = hist, r.s = static_cast<hipStream_t>(hip_stream);
+    return espnet_forward(h, lane, r);
 }
 
 gs_status gs_espnet_read_stage(gs_espnet *h, const char *stage, int image, float *dst, size_t cap, int dims[3])
@@ -1560,36 +1565,16 @@ gs_status gs_espnet_ensemble_forward(gs_espnet *const *models, int n_models, con
     GS_REQUIRE(models && n_models > 0 && in_u8 && means && stds && mask, "gs_espnet_ensemble_forward: null argument");
     gs_status st = check_shape(n, height, width);
     if (st != GS_OK) return st;
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
     bool enc_only = false;
     st = ensemble_kind(models, n_models, &enc_only);
     if (st != GS_OK) return st;
     for (int k = 0; k < n_models; ++k)
         for (int i = 0; i < 3; ++i)
             GS_REQUIRE(stds[3 * k + i] != 0.0f, "ensemble member %d: std[%d] is zero", k, i);
-    if (enc_only) {
-        // ESPNet-C members: the K trunks one after the other on the call's stream, then ONE head over their 1/8-scale logits
-        // (enc_head_ens.h).  No accumulator is allocated; K = 1 runs the same code.
-        for (int k = 0; k < n_models; ++k) {
-            st = espnet_c_trunk(models[k], 0, in_u8, GS_IN_U8_BGR_NHWC, n, height, width, means + 3 * k, stds + 3 * k,
-                                k == 0 ? hist : nullptr, s);
-            if (st != GS_OK) return st;
-        }
-        return espnet_c_ensemble_head(models, n_models, 0, n, height, width, mask, hist, s);
-    }
-    float *prob = nullptr;
-    st = ensemble_scratch(models[0], n, height, width, &prob);
-    if (st != GS_OK) return st;
-    // Every member's decoder tail turns its five logits into probabilities in registers and adds 1/K of them into ONE fp32
-    // accumulator (first member stores, middle members add, the last adds and goes on to the argmax and the counts): the
-    // logits are never written, and the accumulator is read K-1 and written K-1 times.
-    for (int k = 0; k < n_models; ++k) {
-        const int mode = n_models == 1 ? 4 : k == 0 ? 1 : k == n_models - 1 ? 3 : 2;
-        st = espnet_forward_ex(models[k], 0, in_u8, GS_IN_U8_BGR_NHWC, n, height, width, means + 3 * k, stds + 3 * k, nullptr, mask,
-                               hist, prob, mode, 1.0f / (float)n_models, s);
-        if (st != GS_OK) return st;
-    }
-    return GS_OK;
+    ForwardReq r;
+    r.in = in_u8, r.in_format = GS_IN_U8_BGR_NHWC, r.n = n, r.H = height, r.W = width;
+    r.mask = mask, r.hist = hist, r.s = static_cast<hipStream_t>(hip_stream);
+    return run_ensemble(models, n_models, 0, r, means, stds);
 }
 
 gs_status gs_espnet_segment_host(gs_espnet *h, const uint8_t *tiles, int n_tiles, int height, int width,

@@ -32,7 +32,7 @@ constexpr int L2SP = 4;   // pixels per lane of the level-2 branch kernels (the 
 #define CFG_L3_BR_P2F    32, 8,   26,  9,   1,     5,   28,   25,   2, 3    // with the fused 1x1: 32 more accumulators
 #define CFG_L3_BR_P2R    32, 8,   26,  9,   1,     5,   28,   25,   2, 13   // shipped fused ESP form: a third of a dilation in flight
 // small batches (launches with fewer tasks than SIMDs): 32-pixel strips -- the same accumulation chain per pixel, four /
-// two times the tasks (forward_impl picks the shape per launch from the task count; tools/latency.py)
+// two times the tasks (the forward picks the shape per launch from the task count; tools/latency.py)
 #ifndef CFG_SMALL_AGL
 #define CFG_SMALL_AGL 1   // the small-batch level-3 forms take their weights from L2 through the operand ring (F_A_GLOBAL: no LDS staging
                           // phase in front of a lone wave's task; one tile 0.492 -> 0.481 ms, 0.0358 -> 0.0347 ms per launch; at full batches

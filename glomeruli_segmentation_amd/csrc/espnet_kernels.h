@@ -692,8 +692,9 @@ __global__ void __launch_bounds__(256) dec3b_kernel(const Dec3Args a)
 // reference: Model.py:377; VisualizeResults_iou.py:128 (argmax), :151-155 (counts)
 // This two-kernel tail is what every class count other than 5 runs (the five-class networks take dec_tail.h's fused kernel):
 // round 1's tail, generalised.  ENS: the ensemble of BASELINE cfg 5 (definition in DESIGN.md) -- prob [N][classes][H][W]
-// accumulates ens_w * softmax(logits) over the member models exactly as dec_tail_kernel does for five classes (mode 1: first
-// member stores, 2: a middle member adds, 3: the last adds and goes on to the first-max argmax of the sum, 4: a single member).
+// accumulates ens_w * softmax(logits) over the member models exactly as dec_tail_kernel does for five classes.  ens_mode is an
+// EnsRole (gs_internal.h); its tests stay literals here (== 2 || == 3: ens_reads, == 1 || == 2: ens_writes, >= 3: ens_finishes of a
+// mode that is never NONE under ENS) -- with the predicates the compiler emits other code for this kernel.
 struct Dec4Args {
     ActV f;              // concat_features: conv CBR output, CLS channels at 1/2 scale
     const float *wcl;    // classifier.weight [CLS][CLS][2][2]

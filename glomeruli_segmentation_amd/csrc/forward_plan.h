@@ -1,6 +1,6 @@
 // The kernel-form plan of the ESPNet forward: which conv_mfma_kernel instantiation (or plain kernel) each launch class of
-// forward_impl (espnet.hip) runs for a batch size, a tile size, a model depth, a padded class count and a CU count.
-// plan_forward decides, forward_impl executes: it switches over the plan's forms and asks nothing about widths or task counts
+// the forward (espnet.hip: encode, decode) runs for a batch size, a tile size, a model depth, a padded class count and a CU count.
+// plan_forward decides, the forward executes: it switches over the plan's forms and asks nothing about widths or task counts
 // itself.  Host-only and free of HIP calls; gs_espnet_plan_forward / gs_espnet_form_info (include/glomseg.h) expose the
 // function and the table to CPU tests, which is how tests/test_kernel_forms.py knows what a GPU case runs.
 // A new form is added in three places: a row of the table, a branch of plan_forward, one `case` of its class's launch_*

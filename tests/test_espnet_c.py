@@ -198,7 +198,7 @@ def test_source_tripwire_and_abi():
     assert espnet.count('"an ESPNet-C handle cannot be an ensemble member"') == 1
     assert espnet.count('"ensemble member %d is not a full ESPNet"') == 1
     assert crops.count("ensembles need full ESPNet members") == 1
-    body = espnet[espnet.index("static gs_status forward_impl("):espnet.index("static gs_status forward_any(")]
+    body = espnet[espnet.index("static Encoded encode("):espnet.index("static gs_status forward_any(")]
     assert body.count("launch_enc_head(") == 1 and body.index("dec1_kernel<CLS, CB>") < body.index("launch_enc_head(") < body.index("K_DEC2")
     assert '#include "enc_head.h"' in espnet
     head = _read("enc_head.h")

@@ -179,7 +179,7 @@ def test_header_and_prototypes():
     csrc = os.path.join(REPO, "glomeruli_segmentation_amd", "csrc")
     espnet = open(os.path.join(csrc, "espnet.hip")).read()
     assert '#include "enc_head_ens.h"' in espnet and "launch_ens_head(" in open(os.path.join(csrc, "enc_head_ens.h")).read()
-    body = espnet[espnet.index("static gs_status forward_impl("):espnet.index("static gs_status forward_any(")]
+    body = espnet[espnet.index("static Encoded encode("):espnet.index("static gs_status forward_any(")]
     assert "launch_ens_head(" not in body          # the ensemble head is launched behind the K trunks, outside the forward
 
 

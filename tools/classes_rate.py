@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Resident throughput of the forward at class counts other than five (the two-kernel decoder tail, csrc/espnet.hip forward_impl):
+"""Resident throughput of the forward at class counts other than five (the two-kernel decoder tail, csrc/espnet.hip decode):
 ESPNet(classes, 2, 8) with random weights (tests/conftest.random_state_dict), 32 uint8 tiles of 1024x512 -> masks + counts, one
 lane; five classes (the fused tail) in the same run for comparison.      python tools/classes_rate.py [--out profiles/r05_classes_rate.json]"""
 import argparse
