@@ -15,7 +15,7 @@ if os.environ.get("GLOMSEG_LIB") and os.environ.get("GLOMSEG_EXPERIMENT") == "1"
 GS_OK = 0
 GS_IN_U8_BGR_NHWC = 0
 GS_IN_F32_NCHW = 1
-ABI_VERSION = 8
+ABI_VERSION = 9
 GS_BUILD_DIAG = 1
 GS_FORM_NONE = -1
 GS_MAX_ENSEMBLE_C = 8      # most ESPNet-C members of an ensemble (include/glomseg.h)
@@ -65,6 +65,16 @@ class EvalSet(ctypes.Structure):
     _fields_ = [("rasters", ctypes.c_void_p), ("raster_bytes", ctypes.c_int64), ("boxes", ctypes.c_void_p),
                 ("n_boxes", ctypes.c_int32), ("win_ptr", ctypes.c_void_p), ("win_idx", ctypes.c_void_p), ("n_idx", ctypes.c_int32),
                 ("small_map", ctypes.c_void_p)]
+
+
+class DetectorLayerPlan(ctypes.Structure):
+    _fields_ = [("images", ctypes.c_int64), ("in_h", ctypes.c_int32), ("in_w", ctypes.c_int32), ("out_h", ctypes.c_int32),
+                ("out_w", ctypes.c_int32), ("form", ctypes.c_int32)]
+
+
+class DetectorPlan(ctypes.Structure):
+    _fields_ = [("hf", ctypes.c_int32), ("wf", ctypes.c_int32), ("workspace_bytes", ctypes.c_int64), ("n_layers", ctypes.c_int32),
+                ("layers", DetectorLayerPlan * 16)]
 
 
 class KernelTime(ctypes.Structure):
@@ -117,12 +127,15 @@ PROTOTYPES = {
     "gs_confusion_u8": (_I, [_P, _P, ctypes.c_longlong, _I, _P, _P]),
     "gs_wsi_eval_windows": (_I, [_I, _I, _I, _I, ctypes.POINTER(EvalSet), ctypes.POINTER(EvalSet), _P, _P, _I, _I, _P, _P, _P]),
     "gs_conv2d_nhwc": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P]),
+    "gs_conv2d_nhwc_form": (_I, [_I] * 10 + [ctypes.POINTER(ctypes.c_char_p)]),
     "gs_roialign": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
     "gs_nms": (_I, [_P, _P, _I, ctypes.c_float, ctypes.c_float, _I, _P, _P, _P]),
     "gs_detector_create": (_I, [_P, ctypes.POINTER(LayerDesc), _I, ctypes.POINTER(_P)]),
     "gs_detector_destroy": (None, [_P]),
     "gs_detector_max_detections": (_I, []),
     "gs_detector_num_proposals": (_I, []),
+    "gs_detector_layer_info": (_I, [_I, ctypes.POINTER(ctypes.c_char_p)] + [ctypes.POINTER(_I)] * 6),
+    "gs_detector_plan": (_I, [_I, _I, _I, ctypes.POINTER(DetectorPlan)]),
     "gs_detector_set_thresholds": (_I, [_P, ctypes.c_float, ctypes.c_float, ctypes.c_float]),
     "gs_detector_forward": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gs_detector_detect_host": (_I, [_P, ctypes.POINTER(_P), _I, _I, _I, _I, _P, _P, _P, _P]),

@@ -9,6 +9,8 @@
 #include <vector>
 
 #include "crop_sample.h"
+#include "detect_math.h"
+#include "detect_plan.h"
 #include "gs_internal.h"
 
 namespace gs {
@@ -440,9 +442,6 @@ __global__ void __launch_bounds__(256)
 roialign_kernel(const float *feat, int n, int h, int w, int c, const float *boxes, const int *box_image, int n_boxes,
                 int crop, float *out)
 {
-    // no fused multiply-add here: a sample that lands exactly on the border of the feature map is inside or extrapolated
-    // by the last bit of in_y / in_x, and TensorFlow rounds every operation (see det_crop_pool_kernel)
-#pragma clang fp contract(off)
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long total = (long long)n_boxes * crop * crop * c;
     if (idx >= total)
@@ -454,22 +453,8 @@ roialign_kernel(const float *feat, int n, int h, int w, int c, const float *boxe
     const float y1 = boxes[b * 4 + 0], x1 = boxes[b * 4 + 1], y2 = boxes[b * 4 + 2], x2 = boxes[b * 4 + 3];
     const int img = box_image[b];
     float v = 0.0f;
-    if (img >= 0 && img < n) {
-        const float hs = crop > 1 ? (y2 - y1) * (float)(h - 1) / (float)(crop - 1) : 0.0f;
-        const float ws = crop > 1 ? (x2 - x1) * (float)(w - 1) / (float)(crop - 1) : 0.0f;
-        const float in_y = crop > 1 ? y1 * (float)(h - 1) + (float)y * hs : 0.5f * (y1 + y2) * (float)(h - 1);
-        const float in_x = crop > 1 ? x1 * (float)(w - 1) + (float)x * ws : 0.5f * (x1 + x2) * (float)(w - 1);
-        if (in_y >= 0.0f && in_y <= (float)(h - 1) && in_x >= 0.0f && in_x <= (float)(w - 1)) {
-            const int ty = (int)floorf(in_y), by = (int)ceilf(in_y);
-            const int lx = (int)floorf(in_x), rx = (int)ceilf(in_x);
-            const float fy = in_y - (float)ty, fx = in_x - (float)lx;
-            const float *base = feat + (long long)img * h * w * c + ch;
-            const float tl = base[((long long)ty * w + lx) * c], tr = base[((long long)ty * w + rx) * c];
-            const float bl = base[((long long)by * w + lx) * c], br = base[((long long)by * w + rx) * c];
-            const float top = tl + (tr - tl) * fx, bot = bl + (br - bl) * fx;
-            v = top + (bot - top) * fy;
-        }
-    }
+    if (img >= 0 && img < n)
+        v = crop_resize_sample<float>(feat, img, h, w, c, ch, y1, x1, y2, x2, crop, y, x);
     out[idx] = v;
 }
 
@@ -477,17 +462,12 @@ roialign_kernel(const float *feat, int n, int h, int w, int c, const float *boxe
 // NMS.  (1) rank boxes by descending score (ties: lower index first) with an O(k^2) count, which
 // also yields the sorted order without a sort network; (2) 64-bit suppression masks with one wave
 // ballot per 64x64 block; (3) one wave walks the sorted list.
+// the caller's boxes may have their corners in either order: normalise, then the detector's IoU (detect_math.h)
 __device__ __forceinline__ float box_iou(const float *a, const float *b)
 {
-    const float ay1 = fminf(a[0], a[2]), ax1 = fminf(a[1], a[3]), ay2 = fmaxf(a[0], a[2]), ax2 = fmaxf(a[1], a[3]);
-    const float by1 = fminf(b[0], b[2]), bx1 = fminf(b[1], b[3]), by2 = fmaxf(b[0], b[2]), bx2 = fmaxf(b[1], b[3]);
-    const float aa = (ay2 - ay1) * (ax2 - ax1), ab = (by2 - by1) * (bx2 - bx1);
-    if (aa <= 0.0f || ab <= 0.0f)
-        return 0.0f;
-    const float ih = fmaxf(fminf(ay2, by2) - fmaxf(ay1, by1), 0.0f);
-    const float iw = fmaxf(fminf(ax2, bx2) - fmaxf(ax1, bx1), 0.0f);
-    const float inter = ih * iw;
-    return inter / (aa + ab - inter);
+    const float an[4] = {fminf(a[0], a[2]), fminf(a[1], a[3]), fmaxf(a[0], a[2]), fmaxf(a[1], a[3])};
+    const float bn[4] = {fminf(b[0], b[2]), fminf(b[1], b[3]), fmaxf(b[0], b[2]), fmaxf(b[1], b[3])};
+    return iou_yxyx(an, bn);
 }
 
 __global__ void __launch_bounds__(256) nms_rank_kernel(const float *scores, int k, float score_thr, int *order, int *n_valid)
@@ -699,48 +679,44 @@ void conv2d_nhwc_pack4(const float *w, int kh, int kw, int cin, int cout, float 
             dst[((size_t)(k / 4) * cout + co) * 4 + (k & 3)] = w[(size_t)k * cout + co];
 }
 
-// The one way to a NHWC convolution kernel: fills ho / wo and picks the kernel.  packed: a.w is in conv2d_nhwc_pack4's layout
-// (only the tiled and wide kernels read it); otherwise TensorFlow's [kh,kw,cin,cout].
-gs_status launch_conv2d_nhwc(ConvNhwcArgs a, bool packed, hipStream_t stream)
+// The one way to a NHWC convolution kernel: runs what conv_nhwc_form (detect_plan.h) decided and decides nothing itself.
+// packed: a.w is in conv2d_nhwc_pack4's layout (only the tiled and wide kernels read it); otherwise TensorFlow's [kh,kw,cin,cout].
+gs_status launch_conv2d_nhwc(ConvNhwcArgs a, const ConvPlan &p, bool packed, hipStream_t stream)
 {
-    a.ho = (a.h + 2 * a.pad - a.kh) / a.stride + 1;
-    a.wo = (a.w_ + 2 * a.pad - a.kw) / a.stride + 1;
-    const bool empty = a.ho <= 0 || a.wo <= 0;
-    // the 64 x 64 kernels address the input and the weights with 32-bit byte offsets
-    const bool in32 = (long long)a.n * a.h * a.w_ * a.cin * 4 < 0x7fffffffLL;
-    const bool w32 = (long long)a.kh * a.kw * a.cin * a.cout * 4 < 0x7fffffffLL;
-    const bool tiled = a.cin % 8 == 0 && in32 && w32;   // 8-channel chunks
-    if (packed && (empty || !tiled)) {
-        // (the message keeps the name of the entry point this check used to live in)
-        set_error("conv2d_nhwc_packed4: shape not supported by the packed-weight kernel");
-        return GS_ERR_UNSUPPORTED;
+    if (p.status != GS_OK) {
+        set_error("%s", p.message);
+        return p.status;
     }
-    GS_REQUIRE(!empty, "gs_conv2d_nhwc: empty output");
-    const long long npix = (long long)a.n * a.ho * a.wo;
-    const dim3 grid64((unsigned)((npix + 255) / 256), (unsigned)((a.cout + 63) / 64));
-    if (tiled) {
-        // whole-line activation fetches where a pixel has at least a line of channels and the map is not a handful of pixels.
-        // Measured on the detector (16 windows of 1000 x 1000): 64..256-channel backbone layers 86-90 -> 98-119 TFLOP/s; the
-        // 16-channel first layer at two chunks per block 876 -> 1026 us and the box head's 7x7 -> 4x4 layer 264 -> 312 us,
-        // so those stay on the chunk-at-a-time kernel.
-        const bool wide = a.cin % 32 == 0 && a.ho * a.wo >= 64;
-        if (wide && packed)
-            hipLaunchKernelGGL((conv2d_nhwc_wide_kernel<4, true>), grid64, dim3(256), 0, stream, a);
-        else if (wide)
-            hipLaunchKernelGGL((conv2d_nhwc_wide_kernel<4, false>), grid64, dim3(256), 0, stream, a);
-        else if (packed)
-            hipLaunchKernelGGL(conv2d_nhwc_tiled_kernel<true>, grid64, dim3(256), 0, stream, a);
+    a.ho = p.ho;
+    a.wo = p.wo;
+    const dim3 grid(p.grid_x, p.grid_y);
+    switch (p.form) {
+    case GS_CONV_WIDE:
+        if (packed)
+            hipLaunchKernelGGL((conv2d_nhwc_wide_kernel<4, true>), grid, dim3(256), 0, stream, a);
         else
-            hipLaunchKernelGGL(conv2d_nhwc_tiled_kernel<false>, grid64, dim3(256), 0, stream, a);
-    } else if (a.cin < 8 && (long long)a.kh * a.kw * a.cin <= 512 && a.kh < 1024 && a.kw < 1024 && in32) {
-        // few input channels: flattened-K kernel (K = kh*kw*cin up to 512, channel / tap indices below 1024)
-        hipLaunchKernelGGL(conv2d_nhwc_smallcin_kernel, grid64, dim3(256), 0, stream, a);
-    } else {
-        const dim3 grid32((unsigned)((npix + 127) / 128), (unsigned)((a.cout + 31) / 32));
-        hipLaunchKernelGGL(conv2d_nhwc_kernel, grid32, dim3(256), 0, stream, a);
+            hipLaunchKernelGGL((conv2d_nhwc_wide_kernel<4, false>), grid, dim3(256), 0, stream, a);
+        break;
+    case GS_CONV_TILED:
+        if (packed)
+            hipLaunchKernelGGL(conv2d_nhwc_tiled_kernel<true>, grid, dim3(256), 0, stream, a);
+        else
+            hipLaunchKernelGGL(conv2d_nhwc_tiled_kernel<false>, grid, dim3(256), 0, stream, a);
+        break;
+    case GS_CONV_SMALLCIN:
+        hipLaunchKernelGGL(conv2d_nhwc_smallcin_kernel, grid, dim3(256), 0, stream, a);
+        break;
+    case GS_CONV_GENERIC:
+        hipLaunchKernelGGL(conv2d_nhwc_kernel, grid, dim3(256), 0, stream, a);
+        break;
     }
     GS_HIP(hipGetLastError());
     return GS_OK;
+}
+
+gs_status launch_conv2d_nhwc(const ConvNhwcArgs &a, bool packed, hipStream_t stream)
+{
+    return launch_conv2d_nhwc(a, conv_nhwc_form({a.n, a.h, a.w_, a.cin, a.kh, a.kw, a.cout, a.stride, a.pad}, packed), packed, stream);
 }
 
 }  // namespace gs
@@ -841,6 +817,21 @@ gs_status gs_conv2d_nhwc(const float *in, int n, int h, int w, int cin, const fl
     return launch_conv2d_nhwc(a, false, static_cast<hipStream_t>(hip_stream));
 }
 
+gs_status gs_conv2d_nhwc_form(int n, int h, int w, int cin, int kh, int kw, int cout, int stride, int pad, int packed,
+                              const char **form_name)
+{
+    GS_REQUIRE(form_name, "gs_conv2d_nhwc_form: null pointer");
+    GS_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && kh > 0 && kw > 0 && stride > 0 && pad >= 0,
+               "gs_conv2d_nhwc_form: bad dimensions");
+    const ConvPlan p = conv_nhwc_form({n, h, w, cin, kh, kw, cout, stride, pad}, packed != 0);
+    if (p.status != GS_OK) {
+        set_error("%s", p.message);
+        return p.status;
+    }
+    *form_name = kConvFormNames[p.form];
+    return GS_OK;
+}
+
 gs_status gs_roialign(const float *feat, int n, int h, int w, int c, const float *boxes, const int *box_image, int n_boxes,
                       int crop, float *out, void *hip_stream)
 {
@@ -860,6 +851,10 @@ gs_status gs_nms(const float *boxes, const float *scores, int k, float iou_thres
 {
     GS_REQUIRE(boxes && scores && keep && n_keep, "gs_nms: null pointer");
     GS_REQUIRE(k >= 0 && max_out >= 0, "gs_nms: negative count");
+    // These three kernels and the detector's det_nms_mask_kernel / det_nms_scan_kernel (detector.hip) share the IoU and
+    // nothing else, on purpose: here one list in the caller's order behind an order indirection, its valid count on the
+    // device; there a batch of lists already sorted, the count read off the scores, and a walk over an LDS-resident
+    // matrix (a measured choice for K <= 1024).  One kernel for both would branch on its caller.
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     if (k == 0 || max_out == 0) {
         GS_HIP(hipMemsetAsync(n_keep, 0, sizeof(int), s));

@@ -17,21 +17,13 @@
 #include <string>
 #include <vector>
 
+#include "detect_math.h"
+#include "detect_plan.h"
 #include "gs_internal.h"
 #include "host_copy.h"
 #include "host_pipe.h"
 
 namespace gs {
-
-constexpr int DET_A = 12;            // anchors per cell: scales {0.25,0.5,1,2} x aspect ratios {0.5,1,2}
-constexpr int DET_STRIDE = 16;       // feature stride
-constexpr float DET_BASE = 256.0f;   // anchor base size (TF object-detection grid_anchor_generator)
-constexpr int DET_PRE_NMS = 1024;    // RPN candidates kept by score before NMS
-constexpr int DET_PROPOSALS = 300;   // first_stage_max_proposals
-constexpr int DET_CROP = 14;         // initial_crop_size; followed by a 2x2 max-pool
-constexpr int DET_MAX_DET = 100;     // max_total_detections
-constexpr int DET_CF = 256;          // feature channels
-constexpr int DET_CH = 128;          // box-head channels
 
 // ---------------------------------------------------------------------------------------------
 // uint8 RGB -> [-1,1] floats (2/255 x - 1, the TF-OD Faster R-CNN preprocessor), 2x2 space-to-depth, channels padded to
@@ -92,17 +84,13 @@ __global__ void __launch_bounds__(256) det_maxpool_kernel(const float *in, long 
     *reinterpret_cast<float4 *>(out + p * c + cq * 4) = m;
 }
 
-// tf.image.crop_and_resize (bilinear, extrapolation 0; the arithmetic of gs_roialign) of a crop x crop grid followed by the
+// tf.image.crop_and_resize (bilinear, extrapolation 0; gs_roialign's sample: crop_resize_sample, detect_math.h) of a crop x crop grid followed by the
 // 2x2 / stride-2 max-pool, in one pass: the 14x14 crops (0.96 GB for 4800 boxes of 256 channels) are neither written nor
 // read back.  One thread per (box, pooled y, pooled x, four channels).
 __global__ void __launch_bounds__(256)
 det_crop_pool_kernel(const float *feat, int n, int h, int w, int c, const float *boxes, const int *box_image, int n_boxes, int crop,
                      float *out)
 {
-    // every product and sum rounded on its own in this kernel (no fused multiply-add): whether the last sample of a box
-    // that ends exactly on the feature map's border is inside (<= h-1) or extrapolated (0) hangs on the last bit of in_y /
-    // in_x, and tf.image.crop_and_resize (and the oracle) round each operation
-#pragma clang fp contract(off)
     const int half = crop / 2, c4 = c / 4;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long long)n_boxes * half * half * c4)
@@ -112,8 +100,6 @@ det_crop_pool_kernel(const float *feat, int n, int h, int w, int c, const float 
     const int b = (int)(idx / ((long long)c4 * half * half));
     const float y1 = boxes[b * 4 + 0], x1 = boxes[b * 4 + 1], y2 = boxes[b * 4 + 2], x2 = boxes[b * 4 + 3];
     const int img = box_image[b];
-    const float hs = (y2 - y1) * (float)(h - 1) / (float)(crop - 1);
-    const float ws = (x2 - x1) * (float)(w - 1) / (float)(crop - 1);
     float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
 #pragma unroll
     for (int dy = 0; dy < 2; ++dy)
@@ -121,24 +107,8 @@ det_crop_pool_kernel(const float *feat, int n, int h, int w, int c, const float 
         for (int dx = 0; dx < 2; ++dx) {
             const int y = 2 * py + dy, x = 2 * px + dx;
             float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            const float in_y = y1 * (float)(h - 1) + (float)y * hs;
-            const float in_x = x1 * (float)(w - 1) + (float)x * ws;
-            if (img >= 0 && img < n && in_y >= 0.0f && in_y <= (float)(h - 1) && in_x >= 0.0f && in_x <= (float)(w - 1)) {
-                const int ty = (int)floorf(in_y), by = (int)ceilf(in_y);
-                const int lx = (int)floorf(in_x), rx = (int)ceilf(in_x);
-                const float fy = in_y - (float)ty, fx = in_x - (float)lx;
-                const float *base = feat + (long long)img * h * w * c + cq * 4;
-                const float4 tl = *reinterpret_cast<const float4 *>(base + ((long long)ty * w + lx) * c);
-                const float4 tr = *reinterpret_cast<const float4 *>(base + ((long long)ty * w + rx) * c);
-                const float4 bl = *reinterpret_cast<const float4 *>(base + ((long long)by * w + lx) * c);
-                const float4 br = *reinterpret_cast<const float4 *>(base + ((long long)by * w + rx) * c);
-                auto lerp2 = [&](float a, float bb, float cc, float d) {
-                    const float top = a + (bb - a) * fx, bot = cc + (d - cc) * fx;
-                    return top + (bot - top) * fy;
-                };
-                v = make_float4(lerp2(tl.x, tr.x, bl.x, br.x), lerp2(tl.y, tr.y, bl.y, br.y), lerp2(tl.z, tr.z, bl.z, br.z),
-                                lerp2(tl.w, tr.w, bl.w, br.w));
-            }
+            if (img >= 0 && img < n)
+                v = crop_resize_sample<float4>(feat, img, h, w, c, cq * 4, y1, x1, y2, x2, crop, y, x);
             m.x = fmaxf(m.x, v.x);
             m.y = fmaxf(m.y, v.y);
             m.z = fmaxf(m.z, v.z);
@@ -373,17 +343,6 @@ det_rpn_decode_kernel(const float *rpn, const int *sel, int n, int hf, int wf, i
     decode_clip(ab[0], ab[1], ab[2], ab[3], d[0], d[1], d[2], d[3], H, W, o);
 }
 
-__device__ __forceinline__ float iou_yxyx(const float *a, const float *b)
-{
-    const float aa = (a[2] - a[0]) * (a[3] - a[1]), ab = (b[2] - b[0]) * (b[3] - b[1]);
-    if (aa <= 0.0f || ab <= 0.0f)
-        return 0.0f;
-    const float ih = fmaxf(fminf(a[2], b[2]) - fmaxf(a[0], b[0]), 0.0f);
-    const float iw = fmaxf(fminf(a[3], b[3]) - fmaxf(a[1], b[1]), 0.0f);
-    const float inter = ih * iw;
-    return inter / (aa + ab - inter);
-}
-
 // Batched greedy NMS over candidates that are ALREADY sorted by descending score (blockIdx.z = image):
 // 64-bit suppression masks, one wave per (64 suppressors x 64 candidates) block ...
 __global__ void __launch_bounds__(64)
@@ -573,14 +532,13 @@ det_output_kernel(const float *boxes, const float *scores, const int *keep, cons
 
 // ---------------------------------------------------------------------------------------------
 struct DetLayer {
-    long long w = -1, b = -1;   // float offsets into the device blob
-    int k = 0, cin = 0, cout = 0, stride = 1, pad = 0;
+    long long w = -1, b = -1;   // float offsets into the device blob (shape: the layer's row of kDetLayers)
 };
 
 struct Detector {
     int device = 0;
     float *dblob = nullptr;
-    DetLayer c1, c2, c3, c4, c5, c6, rpn, rpn_head, h1, h2, fc;
+    DetLayer layers[DET_LAYERS];
     float rpn_iou = 0.7f, det_iou = 0.6f, det_score = 0.0f;
     void *ws = nullptr;
     size_t ws_bytes = 0;
@@ -595,12 +553,15 @@ struct Detector {
 
 static inline unsigned nblk(long long items) { return (unsigned)((items + 255) / 256); }
 
-static gs_status conv(const Detector &d, const DetLayer &l, const float *in, int n, int h, int w, int relu, float *out, hipStream_t s)
+// layer `id` as the plan has it, from `in` to `out`
+static gs_status conv(const Detector &d, const DetectorPlan &pl, DetLayerId id, const float *in, float *out, hipStream_t s)
 {
-    ConvNhwcArgs a{in, d.dblob + l.w, d.dblob + l.b, out, n, h, w, l.cin, l.k, l.k, l.cout, l.stride, l.pad, relu, 0, 0};
-    return launch_conv2d_nhwc(a, true, s);
+    const DetLayerRow &r = kDetLayers[id];
+    const DetLayerPlan &l = pl.layer[id];
+    ConvNhwcArgs a{in, d.dblob + d.layers[id].w, d.dblob + d.layers[id].b, out, (int)l.images, l.in_h, l.in_w, r.cin, r.k, r.k, r.cout, r.stride,
+                   r.pad, r.relu, 0, 0};
+    return launch_conv2d_nhwc(a, l.conv, true, s);
 }
-static inline int conv_out(int x, const DetLayer &l) { return (x + 2 * l.pad - l.k) / l.stride + 1; }
 
 }  // namespace gs
 
@@ -614,6 +575,45 @@ struct gs_detector {
 
 int gs_detector_max_detections(void) { return DET_MAX_DET; }
 int gs_detector_num_proposals(void) { return DET_PROPOSALS; }
+
+int gs_detector_layer_info(int i, const char **name, int *k, int *cin, int *cout, int *stride, int *pad, int *relu)
+{
+    if (i < 0 || i >= DET_LAYERS)
+        return 0;
+    const DetLayerRow &r = kDetLayers[i];
+    if (name) *name = r.name;
+    if (k) *k = r.k;
+    if (cin) *cin = r.cin;
+    if (cout) *cout = r.cout;
+    if (stride) *stride = r.stride;
+    if (pad) *pad = r.pad;
+    if (relu) *relu = r.relu;
+    return 1;
+}
+
+gs_status gs_detector_plan(int n, int height, int width, gs_detector_plan_info *out)
+{
+    static_assert(DET_LAYERS <= GS_DETECTOR_MAX_LAYERS, "gs_detector_plan_info has room for every layer");
+    GS_REQUIRE(out, "gs_detector_plan: null argument");
+    const DetectorPlan pl = plan_detector(n, height, width);
+    if (pl.status != GS_OK) {
+        set_error("%s", pl.message);
+        return pl.status;
+    }
+    out->hf = pl.hf, out->wf = pl.wf;
+    out->workspace_bytes = (int64_t)pl.total;
+    out->n_layers = DET_LAYERS;
+    for (int i = 0; i < DET_LAYERS; ++i) {
+        const DetLayerPlan &l = pl.layer[i];
+        // (a layer the packed kernels refuse reports the refusal the forward would stop at)
+        if (l.conv.status != GS_OK) {
+            set_error("%s", l.conv.message);
+            return l.conv.status;
+        }
+        out->layers[i] = {(int64_t)l.images, l.in_h, l.in_w, l.conv.ho, l.conv.wo, (int32_t)l.conv.form};
+    }
+    return GS_OK;
+}
 
 gs_status gs_detector_create(const float *blob, const gs_layer_desc *table, int n_layers, gs_detector **out)
 {
@@ -633,40 +633,25 @@ gs_status gs_detector_create(const float *blob, const gs_layer_desc *table, int 
     for (int i = 0; i < n_layers; ++i)
         by_name[std::string(table[i].name)] = &table[i];
     std::vector<float> host;
-    auto take = [&](const std::string &name, DetLayer &l, int k, int cin, int cout, int stride, int pad) -> bool {
+    for (int i = 0; i < DET_LAYERS; ++i) {
+        const DetLayerRow &r = kDetLayers[i];
+        const std::string name = r.name;
         auto wi = by_name.find(name + ".weight"), bi = by_name.find(name + ".bias");
-        if (wi == by_name.end() || bi == by_name.end()) {
-            set_error("detector tensor '%s' missing from the table", name.c_str());
-            return false;
-        }
+        GS_REQUIRE(wi != by_name.end() && bi != by_name.end(), "detector tensor '%s' missing from the table", r.name);
         const gs_layer_desc *wd = wi->second, *bd = bi->second;
-        if (wd->ndim != 4 || wd->shape[0] != k || wd->shape[1] != k || wd->shape[2] != cin || wd->shape[3] != cout || bd->ndim != 1 ||
-            bd->shape[0] != cout) {
-            set_error("detector tensor '%s' has the wrong shape (want [%d,%d,%d,%d] + [%d])", name.c_str(), k, k, cin, cout, cout);
-            return false;
-        }
-        l.k = k;
-        l.cin = cin;
-        l.cout = cout;
-        l.stride = stride;
-        l.pad = pad;
+        GS_REQUIRE(wd->ndim == 4 && wd->shape[0] == r.k && wd->shape[1] == r.k && wd->shape[2] == r.cin && wd->shape[3] == r.cout &&
+                       bd->ndim == 1 && bd->shape[0] == r.cout,
+                   "detector tensor '%s' has the wrong shape (want [%d,%d,%d,%d] + [%d])", r.name, r.k, r.k, r.cin, r.cout, r.cout);
+        DetLayer &l = d.layers[i];
         l.w = (long long)host.size();
-        host.resize(host.size() + (size_t)k * k * cin * cout);
+        host.resize(host.size() + (size_t)r.k * r.k * r.cin * r.cout);
         // every layer of this graph has cin % 8 == 0: weights go to the device in the packed [K/4][cout][4] form
-        conv2d_nhwc_pack4(blob + wd->offset, k, k, cin, cout, host.data() + l.w);
+        conv2d_nhwc_pack4(blob + wd->offset, r.k, r.k, r.cin, r.cout, host.data() + l.w);
         l.b = (long long)host.size();
-        host.insert(host.end(), blob + bd->offset, blob + bd->offset + cout);
+        host.insert(host.end(), blob + bd->offset, blob + bd->offset + r.cout);
         while (host.size() % 4)
             host.push_back(0.0f);
-        return true;
-    };
-    if (!take("backbone.c1", d.c1, 3, 16, 64, 1, 1) || !take("backbone.c2", d.c2, 3, 64, 64, 1, 1) ||
-        !take("backbone.c3", d.c3, 3, 64, 128, 2, 1) || !take("backbone.c4", d.c4, 3, 128, 128, 1, 1) ||
-        !take("backbone.c5", d.c5, 3, 128, DET_CF, 2, 1) || !take("backbone.c6", d.c6, 3, DET_CF, DET_CF, 1, 1) ||
-        !take("rpn.conv", d.rpn, 3, DET_CF, DET_CF, 1, 1) || !take("rpn.head", d.rpn_head, 1, DET_CF, 6 * DET_A, 1, 0) ||
-        !take("head.h1", d.h1, 1, DET_CF, DET_CH, 1, 0) || !take("head.h2", d.h2, 3, DET_CH, DET_CH, 2, 1) ||
-        !take("head.fc", d.fc, 1, DET_CH, 6, 1, 0))
-        return GS_ERR_INVALID;
+    }
     GS_HIP(hipMalloc(reinterpret_cast<void **>(&d.dblob), host.size() * sizeof(float)));
     GS_HIP(hipMemcpy(d.dblob, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
     *out = h.release();
@@ -700,107 +685,69 @@ gs_status gs_detector_forward(gs_detector *h, const uint8_t *images_rgb, int n, 
                               float *dbg_head, void *hip_stream)
 {
     GS_REQUIRE(h && images_rgb && boxes && scores && classes && num, "gs_detector_forward: null argument");
-    GS_REQUIRE(n > 0 && height >= 32 && width >= 32, "gs_detector_forward: windows must be at least 32x32 (got %dx%d, n=%d)", height,
-               width, n);
     Detector &d = h->d;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const int h2 = (height + 1) / 2, w2 = (width + 1) / 2;          // c1 (stride-1) size
-    const int h4 = (h2 + 2 - 3) / 2 + 1, w4 = (w2 + 2 - 3) / 2 + 1;   // max-pool 3x3 s2 p1
-    const int h8 = conv_out(h4, d.c3), w8 = conv_out(w4, d.c3);
-    const int hf = conv_out(h8, d.c5), wf = conv_out(w8, d.c5);
-    const long long cells = (long long)hf * wf, anchors = cells * DET_A;
-    // (the tiled convolution addresses a whole input tensor with 32-bit byte offsets)
-    GS_REQUIRE(anchors < (1 << 24) && (long long)n * h2 * w2 * 16 * 4 < 0x7fffffffLL && (long long)n * DET_PROPOSALS * 49 * DET_CF * 4 < 0x7fffffffLL,
-               "gs_detector_forward: batch too large (n=%d windows of %dx%d): split it", n, height, width);
-    const int P = DET_PROPOSALS, K1 = DET_PRE_NMS, K2 = 512;
-    // workspace carve-up (floats unless noted)
-    struct Piece { size_t off, bytes; };
-    size_t total = 0;
-    auto piece = [&](size_t bytes) {
-        Piece p{total, bytes};
-        total += (bytes + 255) / 256 * 256;
-        return p;
-    };
-    const Piece pA = piece((size_t)n * h2 * w2 * 64 * 4);    // ping (largest: c1 output)
-    const Piece pB = piece((size_t)n * h2 * w2 * 16 * 4 > (size_t)n * h4 * w4 * 64 * 4 ? (size_t)n * h2 * w2 * 16 * 4
-                                                                                      : (size_t)n * h4 * w4 * 64 * 4);   // pong
-    const Piece pF = piece((size_t)n * cells * DET_CF * 4);
-    const Piece pR = piece((size_t)n * cells * 6 * DET_A * 4);
-    const Piece pS = piece((size_t)n * anchors * 4);
-    const Piece pI1 = piece((size_t)n * K1 * 4), pS1 = piece((size_t)n * K1 * 4), pB1 = piece((size_t)n * K1 * 16);
-    const Piece pM = piece((size_t)n * K1 * (K1 / 64) * 8);
-    const Piece pK1 = piece((size_t)n * P * 4), pN1 = piece((size_t)n * 4);
-    const Piece pP = piece((size_t)n * P * 16), pPn = piece((size_t)n * P * 16), pBi = piece((size_t)n * P * 4);
-    const Piece pC = piece((size_t)n * P * 49 * DET_CH * 4);      // box-head intermediates (the 14x14 crops are never materialised)
-    const Piece pC2 = piece((size_t)n * P * 49 * DET_CF * 4);
-    const Piece pH = piece((size_t)n * P * 6 * 4), pS2 = piece((size_t)n * P * 4), pB2 = piece((size_t)n * P * 16);
-    const Piece pI2 = piece((size_t)n * K2 * 4), pS2s = piece((size_t)n * K2 * 4), pB2s = piece((size_t)n * K2 * 16);
-    const Piece pK2 = piece((size_t)n * DET_MAX_DET * 4), pN2 = piece((size_t)n * 4);
-    if (total > d.ws_bytes) {
-        if (d.ws) {
-            GS_HIP(hipDeviceSynchronize());
-            GS_HIP(hipFree(d.ws));
-            d.ws = nullptr;
-            d.ws_bytes = 0;
-        }
-        if (hipMalloc(&d.ws, total) != hipSuccess) {
-            set_error("detector workspace allocation of %zu bytes failed (n=%d, %dx%d)", total, n, height, width);
-            return GS_ERR_NOMEM;
-        }
-        d.ws_bytes = total;
+    const DetectorPlan pl = plan_detector(n, height, width);
+    if (pl.status != GS_OK) {
+        set_error("%s", pl.message);
+        return pl.status;
     }
+    const int h2 = pl.h2, w2 = pl.w2, h4 = pl.h4, w4 = pl.w4, hf = pl.hf, wf = pl.wf;
+    const long long cells = pl.cells, anchors = pl.anchors;
+    const int P = DET_PROPOSALS, K1 = DET_PRE_NMS, K2 = DET_HEAD_K;
+    gs_status st = grow(d.ws, d.ws_bytes, pl.total, "detector workspace");
+    if (st != GS_OK) return st;
     char *base = static_cast<char *>(d.ws);
-    auto F = [&](const Piece &p) { return reinterpret_cast<float *>(base + p.off); };
-    auto I = [&](const Piece &p) { return reinterpret_cast<int *>(base + p.off); };
+    auto F = [&](const DetPiece &p) { return reinterpret_cast<float *>(base + p.off); };
+    auto I = [&](const DetPiece &p) { return reinterpret_cast<int *>(base + p.off); };
     const float Hf = (float)height, Wf = (float)width;
-    gs_status st;
 #define DET_TRY(x) do { st = (x); if (st != GS_OK) return st; } while (0)
 
     // ---- backbone
-    hipLaunchKernelGGL(det_preprocess_kernel, dim3(nblk((long long)n * h2 * w2 * 4)), dim3(256), 0, s, images_rgb, n, height, width, F(pB));
-    DET_TRY(conv(d, d.c1, F(pB), n, h2, w2, 1, F(pA), s));
-    hipLaunchKernelGGL(det_maxpool_kernel, dim3(nblk((long long)n * h4 * w4 * 16)), dim3(256), 0, s, F(pA), (long long)n, h2, w2, 64, 3, 2, 1,
-                       h4, w4, F(pB));
-    DET_TRY(conv(d, d.c2, F(pB), n, h4, w4, 1, F(pA), s));
-    DET_TRY(conv(d, d.c3, F(pA), n, h4, w4, 1, F(pB), s));
-    DET_TRY(conv(d, d.c4, F(pB), n, h8, w8, 1, F(pA), s));
-    DET_TRY(conv(d, d.c5, F(pA), n, h8, w8, 1, F(pB), s));
-    DET_TRY(conv(d, d.c6, F(pB), n, hf, wf, 1, F(pF), s));
+    hipLaunchKernelGGL(det_preprocess_kernel, dim3(nblk((long long)n * h2 * w2 * 4)), dim3(256), 0, s, images_rgb, n, height, width, F(pl.B));
+    DET_TRY(conv(d, pl, L_C1, F(pl.B), F(pl.A), s));
+    hipLaunchKernelGGL(det_maxpool_kernel, dim3(nblk((long long)n * h4 * w4 * 16)), dim3(256), 0, s, F(pl.A), (long long)n, h2, w2, 64, 3, 2, 1,
+                       h4, w4, F(pl.B));
+    DET_TRY(conv(d, pl, L_C2, F(pl.B), F(pl.A), s));
+    DET_TRY(conv(d, pl, L_C3, F(pl.A), F(pl.B), s));
+    DET_TRY(conv(d, pl, L_C4, F(pl.B), F(pl.A), s));
+    DET_TRY(conv(d, pl, L_C5, F(pl.A), F(pl.B), s));
+    DET_TRY(conv(d, pl, L_C6, F(pl.B), F(pl.F), s));
     // ---- region proposal network
-    DET_TRY(conv(d, d.rpn, F(pF), n, hf, wf, 1, F(pA), s));
-    DET_TRY(conv(d, d.rpn_head, F(pA), n, hf, wf, 0, F(pR), s));
-    hipLaunchKernelGGL(det_objectness_kernel, dim3(nblk((long long)n * anchors)), dim3(256), 0, s, F(pR), (long long)n * anchors, F(pS));
-    hipLaunchKernelGGL(det_topk_kernel<DET_PRE_NMS>, dim3(n), dim3(1024), 0, s, F(pS), (int)anchors, I(pI1), F(pS1));
-    hipLaunchKernelGGL(det_rpn_decode_kernel, dim3(nblk((long long)n * K1)), dim3(256), 0, s, F(pR), I(pI1), n, hf, wf, K1, Hf, Wf, F(pB1));
-    hipLaunchKernelGGL(det_nms_mask_kernel, dim3(K1 / 64, K1 / 64, n), dim3(64), 0, s, F(pB1), F(pS1), K1, d.rpn_iou, 0.0f,
-                       reinterpret_cast<unsigned long long *>(base + pM.off));
-    hipLaunchKernelGGL(det_nms_scan_kernel, dim3(n), dim3(256), (size_t)K1 * (K1 / 64) * 8, s, reinterpret_cast<unsigned long long *>(base + pM.off), F(pS1), K1, 0.0f,
-                       P, I(pK1), I(pN1));
-    hipLaunchKernelGGL(det_gather_proposals_kernel, dim3(nblk((long long)n * P)), dim3(256), 0, s, F(pB1), I(pK1), n, K1, Hf, Wf, F(pP),
-                       F(pPn), I(pBi));
+    DET_TRY(conv(d, pl, L_RPN, F(pl.F), F(pl.A), s));
+    DET_TRY(conv(d, pl, L_RPN_HEAD, F(pl.A), F(pl.R), s));
+    hipLaunchKernelGGL(det_objectness_kernel, dim3(nblk((long long)n * anchors)), dim3(256), 0, s, F(pl.R), (long long)n * anchors, F(pl.S));
+    hipLaunchKernelGGL(det_topk_kernel<DET_PRE_NMS>, dim3(n), dim3(1024), 0, s, F(pl.S), (int)anchors, I(pl.I1), F(pl.S1));
+    hipLaunchKernelGGL(det_rpn_decode_kernel, dim3(nblk((long long)n * K1)), dim3(256), 0, s, F(pl.R), I(pl.I1), n, hf, wf, K1, Hf, Wf, F(pl.B1));
+    hipLaunchKernelGGL(det_nms_mask_kernel, dim3(K1 / 64, K1 / 64, n), dim3(64), 0, s, F(pl.B1), F(pl.S1), K1, d.rpn_iou, 0.0f,
+                       reinterpret_cast<unsigned long long *>(base + pl.M.off));
+    hipLaunchKernelGGL(det_nms_scan_kernel, dim3(n), dim3(256), (size_t)K1 * (K1 / 64) * 8, s, reinterpret_cast<unsigned long long *>(base + pl.M.off), F(pl.S1), K1, 0.0f,
+                       P, I(pl.K1), I(pl.N1));
+    hipLaunchKernelGGL(det_gather_proposals_kernel, dim3(nblk((long long)n * P)), dim3(256), 0, s, F(pl.B1), I(pl.K1), n, K1, Hf, Wf, F(pl.P),
+                       F(pl.Pn), I(pl.Bi));
     // ---- box head on crop_and_resize'd features
-    hipLaunchKernelGGL(det_crop_pool_kernel, dim3(nblk((long long)n * P * 49 * (DET_CF / 4))), dim3(256), 0, s, F(pF), n, hf, wf, DET_CF, F(pPn),
-                       I(pBi), n * P, DET_CROP, F(pC2));
-    DET_TRY(conv(d, d.h1, F(pC2), n * P, 7, 7, 1, F(pC), s));             // [nP,7,7,128]
-    DET_TRY(conv(d, d.h2, F(pC), n * P, 7, 7, 1, F(pC2), s));             // [nP,4,4,128]
-    hipLaunchKernelGGL(det_avgpool_kernel, dim3(nblk((long long)n * P * DET_CH)), dim3(256), 0, s, F(pC2), (long long)n * P, 16, DET_CH, F(pC));
-    DET_TRY(conv(d, d.fc, F(pC), n * P, 1, 1, 0, F(pH), s));              // [nP,6]
-    hipLaunchKernelGGL(det_head_decode_kernel, dim3(nblk((long long)n * P)), dim3(256), 0, s, F(pH), F(pP), I(pK1), n * P, Hf, Wf, F(pS2),
-                       F(pB2));
+    hipLaunchKernelGGL(det_crop_pool_kernel, dim3(nblk((long long)n * P * 49 * (DET_CF / 4))), dim3(256), 0, s, F(pl.F), n, hf, wf, DET_CF, F(pl.Pn),
+                       I(pl.Bi), n * P, DET_CROP, F(pl.C2));
+    DET_TRY(conv(d, pl, L_H1, F(pl.C2), F(pl.C), s));             // [nP,7,7,128]
+    DET_TRY(conv(d, pl, L_H2, F(pl.C), F(pl.C2), s));             // [nP,4,4,128]
+    hipLaunchKernelGGL(det_avgpool_kernel, dim3(nblk((long long)n * P * DET_CH)), dim3(256), 0, s, F(pl.C2), (long long)n * P, 16, DET_CH, F(pl.C));
+    DET_TRY(conv(d, pl, L_FC, F(pl.C), F(pl.H), s));              // [nP,6]
+    hipLaunchKernelGGL(det_head_decode_kernel, dim3(nblk((long long)n * P)), dim3(256), 0, s, F(pl.H), F(pl.P), I(pl.K1), n * P, Hf, Wf, F(pl.S2),
+                       F(pl.B2));
     // ---- per-class (one foreground class) NMS, score-sorted, padded outputs
-    hipLaunchKernelGGL(det_topk_kernel<512>, dim3(n), dim3(1024), 0, s, F(pS2), P, I(pI2), F(pS2s));
-    hipLaunchKernelGGL(det_gather_kernel, dim3(nblk((long long)n * K2)), dim3(256), 0, s, F(pB2), I(pI2), n, P, K2, F(pB2s));
-    hipLaunchKernelGGL(det_nms_mask_kernel, dim3(K2 / 64, K2 / 64, n), dim3(64), 0, s, F(pB2s), F(pS2s), K2, d.det_iou, d.det_score,
-                       reinterpret_cast<unsigned long long *>(base + pM.off));
-    hipLaunchKernelGGL(det_nms_scan_kernel, dim3(n), dim3(256), (size_t)K2 * (K2 / 64) * 8, s, reinterpret_cast<unsigned long long *>(base + pM.off), F(pS2s), K2,
-                       d.det_score, DET_MAX_DET, I(pK2), I(pN2));
-    hipLaunchKernelGGL(det_output_kernel, dim3(nblk((long long)n * DET_MAX_DET)), dim3(256), 0, s, F(pB2s), F(pS2s), I(pK2), I(pN2), n, K2, Hf,
+    hipLaunchKernelGGL(det_topk_kernel<512>, dim3(n), dim3(1024), 0, s, F(pl.S2), P, I(pl.I2), F(pl.S2s));
+    hipLaunchKernelGGL(det_gather_kernel, dim3(nblk((long long)n * K2)), dim3(256), 0, s, F(pl.B2), I(pl.I2), n, P, K2, F(pl.B2s));
+    hipLaunchKernelGGL(det_nms_mask_kernel, dim3(K2 / 64, K2 / 64, n), dim3(64), 0, s, F(pl.B2s), F(pl.S2s), K2, d.det_iou, d.det_score,
+                       reinterpret_cast<unsigned long long *>(base + pl.M.off));
+    hipLaunchKernelGGL(det_nms_scan_kernel, dim3(n), dim3(256), (size_t)K2 * (K2 / 64) * 8, s, reinterpret_cast<unsigned long long *>(base + pl.M.off), F(pl.S2s), K2,
+                       d.det_score, DET_MAX_DET, I(pl.K2), I(pl.N2));
+    hipLaunchKernelGGL(det_output_kernel, dim3(nblk((long long)n * DET_MAX_DET)), dim3(256), 0, s, F(pl.B2s), F(pl.S2s), I(pl.K2), I(pl.N2), n, K2, Hf,
                        Wf, boxes, scores, classes, num);
     GS_HIP(hipGetLastError());
-    if (dbg_features) GS_HIP(hipMemcpyAsync(dbg_features, F(pF), (size_t)n * cells * DET_CF * 4, hipMemcpyDeviceToDevice, s));
-    if (dbg_rpn) GS_HIP(hipMemcpyAsync(dbg_rpn, F(pR), (size_t)n * cells * 6 * DET_A * 4, hipMemcpyDeviceToDevice, s));
-    if (dbg_proposals) GS_HIP(hipMemcpyAsync(dbg_proposals, F(pP), (size_t)n * P * 16, hipMemcpyDeviceToDevice, s));
-    if (dbg_head) GS_HIP(hipMemcpyAsync(dbg_head, F(pH), (size_t)n * P * 6 * 4, hipMemcpyDeviceToDevice, s));
+    if (dbg_features) GS_HIP(hipMemcpyAsync(dbg_features, F(pl.F), (size_t)n * cells * DET_CF * 4, hipMemcpyDeviceToDevice, s));
+    if (dbg_rpn) GS_HIP(hipMemcpyAsync(dbg_rpn, F(pl.R), (size_t)n * cells * 6 * DET_A * 4, hipMemcpyDeviceToDevice, s));
+    if (dbg_proposals) GS_HIP(hipMemcpyAsync(dbg_proposals, F(pl.P), (size_t)n * P * 16, hipMemcpyDeviceToDevice, s));
+    if (dbg_head) GS_HIP(hipMemcpyAsync(dbg_head, F(pl.H), (size_t)n * P * 6 * 4, hipMemcpyDeviceToDevice, s));
 #undef DET_TRY
     return GS_OK;
 }

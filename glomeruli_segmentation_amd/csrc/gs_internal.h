@@ -77,8 +77,10 @@ struct ConvNhwcArgs {
 };
 void conv2d_nhwc_pack4(const float *w, int kh, int kw, int cin, int cout, float *dst);
 // packed: a.w went through conv2d_nhwc_pack4 (handles that own their weights); a shape the packed-weight kernels cannot take
-// is GS_ERR_UNSUPPORTED
-gs_status launch_conv2d_nhwc(ConvNhwcArgs a, bool packed, hipStream_t stream);
+// is GS_ERR_UNSUPPORTED.  The kernel is conv_nhwc_form's choice (detect_plan.h); a caller that has planned already passes it.
+struct ConvPlan;
+gs_status launch_conv2d_nhwc(const ConvNhwcArgs &a, bool packed, hipStream_t stream);
+gs_status launch_conv2d_nhwc(ConvNhwcArgs a, const ConvPlan &plan, bool packed, hipStream_t stream);
 
 // ---- espnet.hip internals that the crop pipeline (crops.hip) builds on
 struct CropPipe;                                   // staging state of gs_espnet_segment_crops*, owned by the handle

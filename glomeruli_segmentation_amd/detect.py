@@ -206,7 +206,7 @@ def scan_png(path, detector, meta, window_um, overlap, conf_threshold, site_name
 def load_detector(model, model_name, synthetic_seed=None):
     """--model / --model_name -> a detector callable.  The reference joins model/model/model_name and parses a TensorFlow
     frozen graph (:413-427); that graph is an external download and TensorFlow is absent here, so this build takes the
-    weights of its own assembled detector (detector.FrcnnDetector) as an .npz of the tensors detector.LAYERS names."""
+    weights of its own assembled detector (detector.FrcnnDetector) as an .npz of the tensors detector.layers() names."""
     from .detector import FrcnnDetector, synthetic_weights
     if synthetic_seed is not None:
         return FrcnnDetector(synthetic_weights(synthetic_seed))
@@ -219,7 +219,7 @@ def load_detector(model, model_name, synthetic_seed=None):
     if not path.endswith(".npz"):
         raise ValueError("%s: this build cannot load a TensorFlow frozen graph (the reference's detector network is an external "
                          "download, and TensorFlow is not part of this stack); pass an .npz with the tensors of "
-                         "glomeruli_segmentation_amd.detector.LAYERS" % path)
+                         "glomeruli_segmentation_amd.detector.layers()" % path)
     z = np.load(path)
     return FrcnnDetector({k: z[k] for k in z.files})
 

@@ -11,6 +11,7 @@ unpinned; the graph itself is checked against oracle/detector_oracle
     boxes, scores, classes, num = det(window_rgb_u8[None])        # the sess.run of :350-352
 """
 import ctypes
+from functools import lru_cache
 
 import numpy as np
 import torch
@@ -18,15 +19,25 @@ import torch
 from . import _lib
 from .engine import pack_state_dict
 
-# name -> (kernel, cin, cout); weights are [k,k,cin,cout] (TF layout), biases [cout]
-LAYERS = {
-    "backbone.c1": (3, 16, 64), "backbone.c2": (3, 64, 64), "backbone.c3": (3, 64, 128), "backbone.c4": (3, 128, 128),
-    "backbone.c5": (3, 128, 256), "backbone.c6": (3, 256, 256), "rpn.conv": (3, 256, 256), "rpn.head": (1, 256, 72),
-    "head.h1": (1, 256, 128), "head.h2": (3, 128, 128), "head.fc": (1, 128, 6),
-}
-ANCHORS_PER_CELL = 12
-PROPOSALS = 300
-MAX_DETECTIONS = 100
+
+@lru_cache(maxsize=None)
+def layers():
+    """name -> (kernel, cin, cout) of the graph's convolutions, in launch order, read from the library's own table
+    (gs_detector_layer_info; csrc/detect_plan.h); weights are [k,k,cin,cout] (TF layout), biases [cout].  Loads the library on
+    first use (no device needed), not on import."""
+    lib = _lib.load()
+    name, v = ctypes.c_char_p(), [ctypes.c_int() for _ in range(6)]
+    rows = {}
+    while lib.gs_detector_layer_info(len(rows), ctypes.byref(name), *[ctypes.byref(x) for x in v]):
+        rows[name.value.decode()] = (v[0].value, v[1].value, v[2].value)
+    return rows
+
+
+def plan(n, h, w):
+    """gs_detector_plan: what a forward of n windows of h x w runs (feature size, workspace bytes, per-layer shapes and kernels)"""
+    p = _lib.DetectorPlan()
+    _lib.check(_lib.load().gs_detector_plan(n, h, w, ctypes.byref(p)))
+    return p
 
 
 def synthetic_weights(seed=0):
@@ -34,7 +45,7 @@ def synthetic_weights(seed=0):
     initialised), so activations stay O(1) through the stack and box deltas stay moderate."""
     rng = np.random.default_rng(seed)
     sd = {}
-    for name, (k, cin, cout) in LAYERS.items():
+    for name, (k, cin, cout) in layers().items():
         head = name in ("rpn.head", "head.fc")
         std = 0.05 if head else float(np.sqrt(2.0 / (k * k * cin)))
         w = rng.standard_normal((k, k, cin, cout)).astype(np.float32) * np.float32(std)
@@ -86,14 +97,11 @@ class FrcnnDetector:
                "classes": torch.empty((n, d), dtype=torch.float32, device=dev), "num": torch.empty((n,), dtype=torch.float32, device=dev)}
         dbg = [None, None, None, None]
         if taps:
-            def down(x, k, s, p):
-                return (x + 2 * p - k) // s + 1
-            h2, w2 = (h + 1) // 2, (w + 1) // 2
-            hf, wf = down(down(down(h2, 3, 2, 1), 3, 2, 1), 3, 2, 1), down(down(down(w2, 3, 2, 1), 3, 2, 1), 3, 2, 1)
-            out["features"] = torch.empty((n, hf, wf, 256), dtype=torch.float32, device=dev)
-            out["rpn"] = torch.empty((n, hf, wf, 72), dtype=torch.float32, device=dev)
-            out["proposals"] = torch.empty((n, PROPOSALS, 4), dtype=torch.float32, device=dev)
-            out["head"] = torch.empty((n * PROPOSALS, 6), dtype=torch.float32, device=dev)
+            p, rows, props = plan(n, h, w), layers(), self.lib.gs_detector_num_proposals()
+            out["features"] = torch.empty((n, p.hf, p.wf, rows["backbone.c6"][2]), dtype=torch.float32, device=dev)
+            out["rpn"] = torch.empty((n, p.hf, p.wf, rows["rpn.head"][2]), dtype=torch.float32, device=dev)
+            out["proposals"] = torch.empty((n, props, 4), dtype=torch.float32, device=dev)
+            out["head"] = torch.empty((n * props, rows["head.fc"][2]), dtype=torch.float32, device=dev)
             dbg = [out[k].data_ptr() for k in ("features", "rpn", "proposals", "head")]
         with torch.cuda.device(dev):
             _lib.check(self.lib.gs_detector_forward(

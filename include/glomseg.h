@@ -38,7 +38,8 @@ typedef enum gs_status {
 } gs_status;
 
 const char *gs_last_error(void);
-/* ABI version, bumped on any change of a signature or of what an entry accepts (8: the forward-plan entries;
+/* ABI version, bumped on any change of a signature or of what an entry accepts (9: the detector-plan entries
+ * gs_conv2d_nhwc_form, gs_detector_layer_info, gs_detector_plan; 8: the forward-plan entries;
  * 7: ESPNet-C handles give masks and counts).  ABI 8 libraries from the commit that added csrc/enc_head_ens.h on also accept
  * ensembles whose members are all ESPNet-C handles (below); the number was not bumped for that: no signature changed, and a
  * caller finds out by the call itself (an older ABI 8 library answers GS_ERR_INVALID).  Likewise not bumped for the two entries
@@ -373,6 +374,15 @@ gs_status gs_espnet_profile_read(gs_espnet *h, gs_kernel_time *out, int cap, int
 gs_status gs_conv2d_nhwc(const float *in, int n, int h, int w, int cin, const float *weight, int kh, int kw,
                          int cout, const float *bias_or_null, int stride, int pad, int relu, float *out,
                          void *hip_stream);
+/* Test hook, host-only (no device work; csrc/detect_plan.h): which of its kernels gs_conv2d_nhwc runs for a shape -- the
+ * function its launcher itself calls.  *form_name receives a static string, one of "generic" (one 32 x 32 MFMA tile per wave,
+ * any shape), "smallcin" (cin < 8, flattened K up to 512), "tiled" (cin % 8 == 0, 8-channel chunks), "wide" (cin % 32 == 0 and
+ * at least 64 output pixels per image: a whole 128-byte line per pixel); the codes of gs_conv_form index that list.
+ * packed != 0 asks for a handle that keeps its weights in the packed [K/4][cout][4] layout (gs_detector): only "tiled" and
+ * "wide" read it, any other shape is GS_ERR_UNSUPPORTED.  An empty output is GS_ERR_INVALID, as in gs_conv2d_nhwc.  ABI 9. */
+typedef enum gs_conv_form { GS_CONV_GENERIC = 0, GS_CONV_SMALLCIN = 1, GS_CONV_TILED = 2, GS_CONV_WIDE = 3 } gs_conv_form;
+gs_status gs_conv2d_nhwc_form(int n, int h, int w, int cin, int kh, int kw, int cout, int stride, int pad, int packed,
+                              const char **form_name);
 /* tf.image.crop_and_resize (the ROI pooling of TF-OD Faster R-CNN): boxes normalised [y1,x1,y2,x2],
  * bilinear, extrapolation value 0.  feat NHWC fp32 -> out [n_boxes, crop, crop, c]. */
 gs_status gs_roialign(const float *feat, int n, int h, int w, int c, const float *boxes, const int *box_image,
@@ -397,6 +407,27 @@ gs_status gs_detector_create(const float *blob, const gs_layer_desc *table, int 
 void gs_detector_destroy(gs_detector *h);
 int gs_detector_max_detections(void); /* D = 100 */
 int gs_detector_num_proposals(void);  /* 300 */
+/* The graph's convolutions in launch order, host-only: row i's tensor name (static; + ".weight" [k,k,cin,cout] / ".bias"
+ * [cout]), kernel size, channels, stride, padding and whether a ReLU follows.  Any pointer may be NULL.  Returns 1 while i is
+ * a row, 0 past the last: the table gs_detector_create checks the weights against and gs_detector_forward runs.  ABI 9. */
+int gs_detector_layer_info(int i, const char **name, int *k, int *cin, int *cout, int *stride, int *pad, int *relu);
+/* What gs_detector_forward does for n windows of height x width, host-only (the function the forward itself calls): the
+ * feature map's size, the bytes of workspace the handle will hold, and per convolution (rows of gs_detector_layer_info) the
+ * number of maps it runs on (n, or n * 300 in the box head), their size, the output's and the gs_conv_form of the kernel
+ * (weights packed).  Refuses what the forward refuses, with its status and message: windows under 32 x 32, and batches
+ * beyond the kernels' 32-bit offsets ("split it").  ABI 9. */
+#define GS_DETECTOR_MAX_LAYERS 16
+typedef struct gs_detector_layer_plan {
+    int64_t images;
+    int32_t in_h, in_w, out_h, out_w, form;
+} gs_detector_layer_plan;
+typedef struct gs_detector_plan_info {
+    int32_t hf, wf;
+    int64_t workspace_bytes;
+    int32_t n_layers;
+    gs_detector_layer_plan layers[GS_DETECTOR_MAX_LAYERS];
+} gs_detector_plan_info;
+gs_status gs_detector_plan(int n, int height, int width, gs_detector_plan_info *out);
 gs_status gs_detector_set_thresholds(gs_detector *h, float rpn_nms_iou, float det_nms_iou, float det_score_threshold);
 /* images_rgb: device uint8 [n,height,width,3].  boxes [n,D,4] normalised [ymin,xmin,ymax,xmax], scores [n,D] descending,
  * classes [n,D] (1.0 = glomerulus, 0 = padding), num [n]: device fp32.  dbg_*: optional device taps (NULL to skip):

@@ -1,8 +1,10 @@
 """The detector's kernels (csrc/detect_ops.hip, csrc/detector.hip) at the shapes and inputs where they can go wrong.
 
-1. the four convolution kernels behind launch_conv2d_nhwc: CONV_CASES holds known answers for its choice (conv_form, written
-   by hand from the dispatch code), one float64 reference, one bound for the family, and a CPU test showing that the bound
-   rejects a dropped K-tail, a zeroed tap column and a one-pixel shift;
+1. the four convolution kernels behind launch_conv2d_nhwc: CONV_CASES holds hand-written known answers for its choice, which
+   a CPU test asks of the product itself (gs_conv2d_nhwc_form: conv_nhwc_form of csrc/detect_plan.h, the function the
+   launcher switches over), one float64 reference, one bound for the family, and a CPU test showing that the bound rejects a
+   dropped K-tail, a zeroed tap column and a one-pixel shift; likewise known answers for the detector's host plan
+   (gs_detector_plan, gs_detector_layer_info): size chain, workspace bytes, batch limits, per-layer kernels;
 2. gs_roialign against the float32 oracle, on the border, beyond it, at crop 1 and on degenerate maps;
 3. gs_nms against a float32 restatement, exactly, on inputs whose arithmetic is exact;
 4. the selection stages of the assembled detector (top-k, NMS, decode, gather, output) stage by stage against
@@ -13,6 +15,7 @@ NOT reference parity: the reference's detector is an external frozen graph (DESI
 numpy or oracle/detector_oracle.py.
 """
 import ctypes
+import os
 from collections import namedtuple
 from functools import lru_cache
 
@@ -22,6 +25,7 @@ import pytest
 from oracle import detector_oracle as do
 
 F32 = np.float32
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -36,17 +40,13 @@ def conv_out_hw(h, w, kh, kw, stride, pad):
     return (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
 
 
-def conv_form(n, h, w, cin, kh, kw, cout, stride, pad):
-    """launch_conv2d_nhwc's choice (csrc/detect_ops.hip) for the public entry, whose weights are not packed"""
-    ho, wo = conv_out_hw(h, w, kh, kw, stride, pad)
-    assert ho > 0 and wo > 0
-    in32 = n * h * w * cin * 4 < 0x7fffffff          # the 64 x 64 kernels use 32-bit byte offsets
-    w32 = kh * kw * cin * cout * 4 < 0x7fffffff
-    if cin % 8 == 0 and in32 and w32:                # 8-channel chunks ...
-        return "wide" if cin % 32 == 0 and ho * wo >= 64 else "tiled"   # ... or a whole 128-byte line per pixel
-    if cin < 8 and kh * kw * cin <= 512 and kh < 1024 and kw < 1024 and in32:
-        return "smallcin"                            # flattened K through a 512-entry table
-    return "generic"
+def conv_form(n, h, w, cin, kh, kw, cout, stride, pad, packed=False):
+    """the library's answer (gs_conv2d_nhwc_form; no device): the kernel launch_conv2d_nhwc runs for the shape; packed=False is
+    the public entry, whose weights are not packed"""
+    from glomeruli_segmentation_amd import _lib
+    name = ctypes.c_char_p()
+    _lib.check(_lib.load().gs_conv2d_nhwc_form(n, h, w, cin, kh, kw, cout, stride, pad, int(packed), ctypes.byref(name)))
+    return name.value.decode()
 
 
 ConvCase = namedtuple("ConvCase", "name form n h w cin kh kw cout stride pad bias relu edges")
@@ -200,6 +200,122 @@ def test_conv_bounds_discriminate():
           "worst error / bound = %.3f" % (worst[top], top, 4 * worst[top], CONV_TAU, worst[top] / CONV_TAU))
     # no looser than the 2e-4 * max(1, max|ref|) the detector's convolutions were held to before
     assert CONV_TAU <= 2e-4
+
+
+def test_conv_form_refusals():
+    """an empty output is GS_ERR_INVALID; packed weights with a shape the tiled / wide kernels cannot take (or an empty output)
+    is GS_ERR_UNSUPPORTED, both with the launcher's messages; packed is a flag beside the form, not a form"""
+    from glomeruli_segmentation_amd import _lib
+    with pytest.raises(_lib.GlomsegError, match="gs_conv2d_nhwc: empty output") as e:
+        conv_form(1, 2, 2, 8, 3, 3, 8, 1, 0)
+    assert e.value.status == 1
+    for shape in ((1, 12, 13, 7, 3, 3, 20, 1, 1), (1, 12, 13, 12, 3, 3, 20, 1, 1), (1, 2, 2, 8, 3, 3, 8, 1, 0)):
+        with pytest.raises(_lib.GlomsegError, match="conv2d_nhwc_packed4: shape not supported by the packed-weight kernel") as e:
+            conv_form(*shape, packed=True)
+        assert e.value.status == 4
+    assert conv_form(1, 9, 7, 32, 3, 3, 64, 1, 1, packed=True) == "tiled" and conv_form(1, 8, 8, 32, 3, 3, 64, 1, 1, packed=True) == "wide"
+
+
+# ---- the detector's host plan (csrc/detect_plan.h through gs_detector_layer_info / gs_detector_plan; no device)
+# the rows synthetic_weights was written against: name -> (k, cin, cout), in launch order
+DET_LAYER_ROWS = [("backbone.c1", 3, 16, 64, 1, 1, 1), ("backbone.c2", 3, 64, 64, 1, 1, 1), ("backbone.c3", 3, 64, 128, 2, 1, 1),
+                  ("backbone.c4", 3, 128, 128, 1, 1, 1), ("backbone.c5", 3, 128, 256, 2, 1, 1), ("backbone.c6", 3, 256, 256, 1, 1, 1),
+                  ("rpn.conv", 3, 256, 256, 1, 1, 1), ("rpn.head", 1, 256, 72, 1, 0, 0), ("head.h1", 1, 256, 128, 1, 0, 1),
+                  ("head.h2", 3, 128, 128, 2, 1, 1), ("head.fc", 1, 128, 6, 1, 0, 0)]
+# (n, H, W) -> h2 x w2, h4 x w4, h8 x w8, hf x wf, workspace bytes: worked out from the forward's arithmetic before the plan existed
+DET_PLAN_KNOWN = {
+    (16, 1000, 1000): ((500, 500), (250, 250), (125, 125), (63, 63), 1730729728),
+    (1, 32, 32): ((16, 16), (8, 8), (4, 4), (2, 2), 22861568),
+    (2, 33, 47): ((17, 24), (9, 12), (5, 6), (3, 3), 45836288),
+    (3, 50, 37): ((25, 19), (13, 10), (7, 5), (4, 3), 68834048),
+}
+# per-layer kernels with packed weights.  1000 x 1000: c1 (cin 16), head.h1 (49 pixels), head.h2 (16 pixels) and head.fc (1 pixel)
+# are tiled, the other seven wide; 32 x 32: only c2 (8 x 8 = 64 pixels) is wide
+DET_PLAN_FORMS = {
+    (16, 1000, 1000): ["tiled", "wide", "wide", "wide", "wide", "wide", "wide", "wide", "tiled", "tiled", "tiled"],
+    (1, 32, 32): ["tiled", "wide", "tiled", "tiled", "tiled", "tiled", "tiled", "tiled", "tiled", "tiled", "tiled"],
+}
+
+
+# synthetic_weights(0): sha256 over name + bytes of every tensor in order, taken at the commit before detector.LAYERS became layers()
+SYNTHETIC_WEIGHTS_SEED0_SHA256 = "018db6e5b8aec9de50a02373fb6ceda8b5c780af473520bb6c5f65dde87bc970"
+
+
+def detector_layer_rows():
+    from glomeruli_segmentation_amd import _lib
+    lib = _lib.load()
+    name, v = ctypes.c_char_p(), [ctypes.c_int() for _ in range(6)]
+    rows = []
+    while lib.gs_detector_layer_info(len(rows), ctypes.byref(name), *[ctypes.byref(x) for x in v]):
+        rows.append((name.value.decode(),) + tuple(x.value for x in v))
+        assert len(rows) <= 16
+    return rows
+
+
+def test_detector_layer_table_and_lazy_import():
+    """gs_detector_layer_info enumerates the 11 rows synthetic_weights produced its tensors for (and 0 outside them); detector.py
+    reads them lazily: importing it does not load the library; the seeded arrays are what they were"""
+    import hashlib
+    import subprocess
+    import sys
+    from glomeruli_segmentation_amd import _lib
+    from glomeruli_segmentation_amd import detector
+    rows = detector_layer_rows()
+    assert rows == DET_LAYER_ROWS and len(rows) == 11
+    lib = _lib.load()
+    assert lib.gs_detector_layer_info(-1, None, None, None, None, None, None, None) == 0
+    assert lib.gs_detector_layer_info(0, None, None, None, None, None, None, None) == 1
+    assert list(detector.layers().items()) == [(r[0], r[1:4]) for r in DET_LAYER_ROWS]
+    assert lib.gs_detector_num_proposals() == do.PROPOSALS == 300 and lib.gs_detector_max_detections() == do.MAX_DET == 100
+    sd = detector.synthetic_weights(0)
+    assert [(k, v.shape) for k, v in sd.items()] == [
+        (r[0] + s, shape) for r in DET_LAYER_ROWS for s, shape in ((".weight", (r[1], r[1], r[2], r[3])), (".bias", (r[3],)))]
+    h = hashlib.sha256()
+    for k, v in sd.items():
+        h.update(k.encode() + v.tobytes())
+    assert h.hexdigest() == SYNTHETIC_WEIGHTS_SEED0_SHA256
+    code = ("import sys; import glomeruli_segmentation_amd.detector as d, glomeruli_segmentation_amd._lib as l; "
+            "assert l._lib is None, 'importing detector loaded the library'; d.layers(); assert l._lib is not None")
+    subprocess.run([sys.executable, "-c", code], check=True, cwd=REPO, timeout=120)
+
+
+def detector_plan(n, H, W):
+    from glomeruli_segmentation_amd import detector
+    return detector.plan(n, H, W)
+
+
+@pytest.mark.parametrize("shape", sorted(DET_PLAN_KNOWN))
+def test_detector_plan_known_answers(shape):
+    n, H, W = shape
+    (h2, w2), (h4, w4), (h8, w8), (hf, wf), ws_bytes = DET_PLAN_KNOWN[shape]
+    p = detector_plan(n, H, W)
+    L = p.layers
+    assert p.n_layers == 11 and (p.hf, p.wf) == (hf, wf) and p.workspace_bytes == ws_bytes
+    P = 300
+    want = [(n, h2, w2, h2, w2), (n, h4, w4, h4, w4), (n, h4, w4, h8, w8), (n, h8, w8, h8, w8), (n, h8, w8, hf, wf), (n, hf, wf, hf, wf),
+            (n, hf, wf, hf, wf), (n, hf, wf, hf, wf), (n * P, 7, 7, 7, 7), (n * P, 7, 7, 4, 4), (n * P, 1, 1, 1, 1)]
+    assert [(L[i].images, L[i].in_h, L[i].in_w, L[i].out_h, L[i].out_w) for i in range(11)] == want
+    forms = [CONV_FORMS[L[i].form] for i in range(11)]
+    # the plan's form codes are the single-shape entry's answers with packed weights
+    for i, (name, k, cin, cout, stride, pad, relu) in enumerate(DET_LAYER_ROWS):
+        assert conv_form(L[i].images, L[i].in_h, L[i].in_w, cin, k, k, cout, stride, pad, packed=True) == forms[i], name
+    if shape in DET_PLAN_FORMS:
+        assert forms == DET_PLAN_FORMS[shape]
+
+
+def test_detector_plan_limits():
+    """the forward's three limit checks (anchors < 2^24, the 32-bit byte offsets of c1's input and of the pooled crops): the last
+    batch accepted and the first refused at two window sizes; windows under 32 x 32 are refused as the forward refuses them"""
+    from glomeruli_segmentation_amd import _lib
+    for (H, W, last) in ((1000, 1000, 134), (32, 32, 142)):
+        assert detector_plan(last, H, W).workspace_bytes > 0
+        with pytest.raises(_lib.GlomsegError, match=r"batch too large \(n=%d windows of %dx%d\): split it" % (last + 1, H, W)) as e:
+            detector_plan(last + 1, H, W)
+        assert e.value.status == 1          # GS_ERR_INVALID
+    for bad in ((0, 64, 64), (1, 31, 64), (1, 64, 31)):
+        with pytest.raises(_lib.GlomsegError, match="windows must be at least 32x32") as e:
+            detector_plan(*bad)
+        assert e.value.status == 1
 
 
 @pytest.mark.gpu

@@ -93,13 +93,13 @@ def main():
     out["cfg3_nms_300"] = {"us": round(t * 1e6, 1), "pair_ious_per_s": round(k * k / t / 1e9, 3), "unit": "G pairs/s"}
 
     # ---- cfg 3: the assembled detector (gs_detector_forward), sixteen 1000x1000 windows per call ----------------
-    from glomeruli_segmentation_amd.detector import LAYERS, FrcnnDetector, synthetic_weights
+    from glomeruli_segmentation_amd.detector import FrcnnDetector, layers, plan, synthetic_weights
     det = FrcnnDetector(synthetic_weights(0))
     wins = torch.from_numpy(np.stack([synth_tile(200 + i, 1000, 1000, blobs=8)[:, :, ::-1].copy() for i in range(4)] * 4)).to(dev)
     t = timeit(lambda: det.forward_device(wins), reps=5, warm=2)
-    sizes = {"backbone.c1": 500 * 500, "backbone.c2": 250 * 250, "backbone.c3": 125 * 125, "backbone.c4": 125 * 125, "backbone.c5": 63 * 63,
-             "backbone.c6": 63 * 63, "rpn.conv": 63 * 63, "rpn.head": 63 * 63, "head.h1": 300 * 49, "head.h2": 300 * 16, "head.fc": 300}
-    gflop = sum(2.0 * sizes[k] * kk * kk * ci * co for k, (kk, ci, co) in LAYERS.items()) / 1e9
+    per_window = plan(1, 1000, 1000).layers                      # output pixels of every layer, per window
+    gflop = sum(2.0 * per_window[i].images * per_window[i].out_h * per_window[i].out_w * kk * kk * ci * co
+                for i, (kk, ci, co) in enumerate(layers().values())) / 1e9
     out["cfg3_detector_forward_batch16_1000x1000"] = {
         "ms_per_batch": round(t * 1e3, 2), "windows/s": round(16 / t, 1), "GFLOP_per_window": round(gflop, 2),
         "TFLOP/s": round(16 * gflop / t / 1e3, 1), "frac_of_fp32_mfma_peak": round(16 * gflop / t / 1e3 / 157.3, 3),

@@ -43,7 +43,7 @@ def main():
     print(os.environ.get("GLOMSEG_LIB", "shipped"), "ensemble", ensemble_digest(torch))
 
 
-# (n, h, w, cin, cout, k, stride, pad): generic, small-cin, tiled and wide kernels, 3x3 / 7x7 / 1x1, ragged tiles
+# (n, h, w, cin, cout, k, stride, pad)
 CONV_SHAPES = [(2, 19, 23, 7, 37, 3, 2, 1), (2, 33, 41, 3, 64, 3, 2, 1), (1, 40, 37, 3, 70, 7, 2, 3), (2, 9, 11, 1, 5, 3, 1, 1),
                (1, 12, 13, 12, 20, 3, 1, 1), (2, 21, 37, 16, 70, 3, 1, 1), (3, 30, 19, 24, 64, 3, 2, 1), (1, 9, 300, 8, 130, 3, 1, 1),
                (2, 21, 37, 32, 70, 3, 1, 1), (1, 30, 19, 64, 64, 3, 2, 1), (3, 11, 13, 96, 40, 3, 1, 1), (1, 7, 9, 32, 33, 3, 1, 1),
