@@ -147,6 +147,12 @@ SCORING_PROTOTYPES = {
     "gs_espnet_segment_crops_host_scored": (_I, PROTOTYPES["gs_espnet_segment_crops_host"][1] + [ctypes.POINTER(CropScoring)]),
 }
 
+# every symbol include/glomseg_plan.h declares (an addition to ABI 9 with a header of its own)
+PLAN_PROTOTYPES = {
+    "gs_espnet_plan_flags": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]),
+}
+GS_PLAN_LAZY_B2, GS_PLAN_L3C_IN_REDUCE = 1, 2
+
 _lib = None
 
 
@@ -161,7 +167,9 @@ def load():
             "%s is missing: build it with `python -m glomeruli_segmentation_amd.build` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in list(PROTOTYPES.items()) + list(SCORING_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(SCORING_PROTOTYPES.items()) + list(PLAN_PROTOTYPES.items()):
+        if name in PLAN_PROTOTYPES and not hasattr(lib, name):
+            continue   # (an ABI 9 library from before glomseg_plan.h, loaded for an A/B: engine.plan_flags then raises)
         fn = getattr(lib, name)   # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

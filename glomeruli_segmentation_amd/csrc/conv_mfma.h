@@ -107,6 +107,12 @@ struct ConvArgs {
     // for channels that arrive normalised, and a last all-zero slot.  k-groups [bnl_s0, bnl_s1) hold the raw channels: BN of
     // their zero halo would not be zero, so a tap row above the image takes the zero slot and column -1 is re-zeroed.
     int bnl_s0, bnl_s1;
+    // F_SIDE1X1 (stride-2 reduce): the raw output of a 1x1 convolution of the INPUT map (level3_C, Model.py:372), `classes` planes
+    // at the input's resolution, no halo
+    float *side;
+    long long side_sn;
+    int side_sc, side_pitch, side_off;
+    unsigned side_img_bytes;
     // GS_DIAG builds only:
     int stagger;   // units of 1024 cycles by which waves WAVES/2.. start late (0 = off)
     int prio_mode; // wave priority of the two halves of a workgroup: 0 alternates per dilation, 1 per task (shipped), 2 off, 3 fixed
@@ -223,6 +229,27 @@ constexpr int F_S2_FLIP = 1048576;
 // (G == NSTEP) such a chunk is skipped (wave-uniform), and the operand ring is refilled with the next LIVE chunk instead.
 constexpr int F_SKIP_PAD = 4194304;
 constexpr int F_BNLOAD = 8388608;  // see ConvArgs::bnl_s0
+// A 1x1 convolution of the stride-2 reduce's INPUT, computed on the vector ALU beside the matrix instructions (level3_C, the
+// decoder's 131 -> classes projection of output1_cat, Model.py:372).  Output pixel (y, x) loads input pixels (2y-1..2y+1,
+// 2x-1..2x+1); its taps (ty, tx) in {1, 2}^2 are the input pixels (2y + ty - 1, 2x + tx - 1), so every input pixel is one of
+// those four taps of exactly one output pixel: the B operands of tx = 1, 2 in tap rows 1 and 2 -- after F_BNLOAD's BN + PReLU
+// -- are every value the 1x1 needs, each exactly once and already in a register.  A lane (pixel run p, k-group kq = lane / 32)
+// adds w[k][ch] * value into side[p][k][tx - 1] for the channels ch = 2 * step + kq of its k-group; the class weights of a
+// channel are one LDS read per channel step from the table [CINP + SIDE_ZROWS][SIDE_REC] behind the (rounded) F_BNLOAD table, the
+// last SIDE_ZROWS rows zero.  A tap row is finished before the next one starts and reuses its 2 * classes * P accumulators.
+// SUMMATION ORDER of one pixel's sum, the same in every form (P = 4, P = 1, with and without F_BNLOAD), so batch size and task
+// shape never change a bit: fmaf chain over the channels of k-group 0 (even channels) ascending from 0.0f, fmaf chain over the
+// channels of k-group 1 (odd channels) ascending from 0.0f, then (g0 + g1).  Tap row 0 runs the same instructions on the zero
+// row of the table (a wave-uniform branch after every matrix instruction measured slower for F_BNLOAD's identity channels).
+// The class count sits in bits 27..30 of FLAGS; needs F_S2PAIR, TAPS == 9, STRIDE == 2, MT == 32.
+constexpr int F_SIDE_SHIFT = 27;
+constexpr int F_SIDE1X1(int classes) { return classes << F_SIDE_SHIFT; }
+constexpr int SIDE_REC = 8;   // floats per channel record of the table (dec2_record of up to eight classes)
+constexpr int SIDE_ZROWS = 16;   // zero rows behind the channels' (a chunk's row groups read rows CINP + g * KL of them for tap row 0)
+constexpr int side_table_floats(int CINP) { return (CINP + SIDE_ZROWS) * SIDE_REC; }
+// float offset of the side table behind a configuration's image: the F_BNLOAD table is part of the blob of such a reduce
+// whether the form applies it or not
+constexpr int side_table_offset(int image_total, int CINP, int KL) { return image_total + (3 * (CINP + KL) + 3) / 4 * 4; }
 constexpr int F_X_NOLOAD = 16;  // GS_DIAG timing experiments only (results are garbage): no activation loads in the loop
 constexpr int F_X_NOLDS = 32;   // GS_DIAG: no LDS weight reads in the loop
 constexpr int F_X_NOEPI = 64;   // GS_DIAG: no epilogue at all
@@ -289,6 +316,11 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
     constexpr bool S2FLIP = FLAGS & F_S2_FLIP;
     constexpr bool SKIP = FLAGS & F_SKIP_PAD;
     constexpr bool BNL = FLAGS & F_BNLOAD;
+    constexpr int SCLS = (FLAGS >> F_SIDE_SHIFT) & 15;   // F_SIDE1X1: classes of the side 1x1 (0: none)
+    constexpr bool SIDE = SCLS > 0;
+    static_assert(!SIDE || ((FLAGS & F_S2PAIR) && TAPS == 9 && STRIDE == 2 && MT == 32 && NDIL == 1 && SCLS <= SIDE_REC &&
+                            (CINP / M_KL_OF(MT)) % G == 0 && G * M_KL_OF(MT) <= SIDE_ZROWS && !(FLAGS & (F_A_GLOBAL | F_VEC | F_X_ALL))),
+                  "F_SIDE1X1 is for the stride-2 3x3 reduce on 32-pixel runs, a tap row in whole chunks");
     static_assert(!BNL || ((FLAGS & F_S2PAIR) && !(FLAGS & (F_BNACT | F_A_GLOBAL | F_VEC))), "F_BNLOAD is for the plain stride-2 reduce");
     static_assert(!SKIP || (TAPS == 9 && STRIDE == 1 && !(FLAGS & F_S2PAIR) && G * M_KL_OF(MT) == CINP),
                   "F_SKIP_PAD: unit-stride 3x3 with one tap row per chunk");
@@ -340,6 +372,8 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
     // F_BNLOAD: [scale | shift | alpha][BNL_C] right after the (rounded) image
     constexpr int BNL_C = CINP + M::KL;
     const float *bnl = lds + (conv_image(CINP, TAPS, NDIL, NOUT1, NOUT, BNACT, DUAL, FUSE ? M::NACC : 0).total - LDS_SRC0);
+    // F_SIDE1X1: [CINP + SIDE_ZROWS][SIDE_REC] class weights per input channel, the last rows zero
+    const float *sidew = lds + side_table_offset(conv_image(CINP, TAPS, NDIL, NOUT1, NOUT, BNACT, DUAL, FUSE ? M::NACC : 0).total, CINP, M::KL);
     const __amdgpu_buffer_rsrc_t rsrc_w =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.wpack), 0, AGL ? WFL * 4 : 0, 0x00020000);
 
@@ -598,6 +632,12 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
             dst = zero ? 0.0f : v;
         };
 
+        // F_SIDE1X1: the running sums of the tap row at hand, [pixel run][class][tx - 1], and the class weights of the lane's
+        // channel in the row group at hand
+        float side[SIDE ? P : 1][SIDE ? SCLS : 1][2], sw[SIDE ? SCLS : 1];
+        const __amdgpu_buffer_rsrc_t rside = __builtin_amdgcn_make_buffer_rsrc(
+            SIDE ? a.side + (long long)n * a.side_sn : a.out, 0, SIDE ? a.side_img_bytes : 0u, 0x00020000);
+
         // prologue: the first chunk's activations are requested before the weights are staged, so
         // their latency overlaps the LDS fill
         if (task == t0) {
@@ -796,6 +836,24 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
                 for (int p = 0; p < P; ++p)
                     acc[p] = (typename M::acc_t)(0.0f);
             }
+            // F_SIDE1X1: the tap row of this chunk (a tap row is whole chunks); rows 1 and 2 feed the side sums
+            constexpr int CPR = SIDE ? NSTEP / G : 1;   // chunks per tap row
+            int side_ty = 0;
+            if (SIDE) {
+                int ty0c, sidxc;
+                decode_rg(c, 0, ty0c, sidxc);
+                side_ty = flip ? TYN - 1 - ty0c : ty0c;
+                if (c % CPR == 0) {
+#pragma unroll
+                    for (int p = 0; p < P; ++p)
+#pragma unroll
+                        for (int k = 0; k < SCLS; ++k)
+                            side[p][k][0] = side[p][k][1] = 0.0f;
+                }
+            }
+            const bool side_row = SIDE && side_ty >= 1;   // (wave-uniform)
+            // the lane's row of the table in the chunk's first row group; the zero rows for tap row 0
+            const float *side_wrow = sidew + (side_row ? (c % CPR) * G * KL + kq : CINP) * SIDE_REC;
             // the ring is refilled with the next (live) chunk of this task, or with the first one of the next task
             int nxl = c + 1;
             if (SKIP)
@@ -842,6 +900,12 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
                         else if (!last)
                             bnl_fetch(nx, g + 2 - G, y, flip, nsc, nsh, nal, nraw);
                     }
+                    if (SIDE && tx == 0) {   // the class weights of this group's channel: first used four matrix instructions on
+                        const float *wr = side_wrow + g * KL * SIDE_REC;   // (one address per chunk + a constant)
+#pragma unroll
+                        for (int k = 0; k < SCLS; ++k)
+                            sw[k] = wr[k];
+                    }
 #pragma unroll
                     for (int p = 0; p < P; ++p) {
                         acc[p] = M::run(aq[u % RA], BNL ? bt[BNL ? g & 1 : 0][p][S2P ? tx : 0]
@@ -852,12 +916,44 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
                                 bnl_apply(bt[BNL ? (g + 1) & 1 : 0][e / 3][e % 3], bl[S2P ? (g + 1) % G : 0][e / 3][e % 3], tsc, tsh, tal, tpin,
                                           e == 0 && x0 == 0 && px == 0);
                         }
+                        if (SIDE && tx == 2) {   // the operands of this pixel run's tx = 1 and tx = 2: input pixels 2x and 2x + 1
+                            const float *v = BNL ? bt[BNL ? g & 1 : 0][p] : bl[S2P ? g : 0][p];
+#pragma unroll
+                            for (int k = 0; k < SCLS; ++k) {
+                                side[p][k][0] = fmaf(sw[k], v[S2P ? 1 : 0], side[p][k][0]);
+                                side[p][k][1] = fmaf(sw[k], v[S2P ? 2 : 0], side[p][k][1]);
+                                // (pinned here, in the shadow of the matrix instruction above: left alone hipcc sinks the side sums
+                                // of a whole chunk to its end and keeps every group's weights live until then -- 40 registers)
+                                asm volatile("" : "+v"(side[p][k][0]), "+v"(side[p][k][1]));
+                            }
+                        }
                     }
                     // the slot just consumed is refilled with the step R later: of this chunk, or of the next one
                     refill(u);
                     // pin the ring order: left alone, hipcc sinks the refill loads to the end of the
                     // chunk, which shrinks the prefetch distance from D steps to a few
                     __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            if (SIDE && side_row && (c + 1) % CPR == 0) {
+                // the tap row is complete: g0 + g1 across the halves of the wave, then lanes 0..31 store pixels 2x, 2x + 1 of every
+                // class plane (8 bytes per lane); lanes past the end of a partial strip store nothing
+                const int sside = (a.side_off + (y * STRIDE + side_ty - 1) * a.side_pitch + x0 * STRIDE) * 4;
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    const bool sok = kq == 0 && x0 + p * MT + px < a.W;
+#pragma unroll
+                    for (int k = 0; k < SCLS; ++k) {
+                        float o[2];
+#pragma unroll
+                        for (int dx = 0; dx < 2; ++dx) {
+                            const float own = side[p][k][dx];
+                            const float oth = __builtin_bit_cast(
+                                float, __builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, __builtin_bit_cast(int, own)));
+                            o[dx] = kq == 0 ? own + oth : oth + own;   // (g0 + g1 in both halves)
+                        }
+                        buf_store_vec<2>(rside, sok ? sside + (k * a.side_sc + (p * MT + px) * STRIDE) * 4 : OOB, o);
+                    }
                 }
             }
             if (stamp2)
@@ -937,7 +1033,11 @@ gs_status launch_conv_mfma(ConvArgs a, int num_cus, hipStream_t stream)
     if (const char *e = std::getenv("GS_STAGGER"))
         a.stagger = std::atoi(e);
 #endif
-    constexpr int EXTRA = (FLAGS & F_BNLOAD) ? 3 * (CINP + Mfma<MT>::KL) : 0;   // the on-load BN / PReLU table follows the image
+    // the on-load BN / PReLU table follows the image, the F_SIDE1X1 table follows that
+    constexpr bool SIDE = (FLAGS >> F_SIDE_SHIFT) & 15;
+    constexpr int EXTRA = SIDE                 ? side_table_offset(im.total, CINP, Mfma<MT>::KL) - im.total + side_table_floats(CINP)
+                          : (FLAGS & F_BNLOAD) ? 3 * (CINP + Mfma<MT>::KL)
+                                               : 0;
     a.wfloats = im.total + EXTRA;
     const int lds_floats = im.total + EXTRA - ((FLAGS & F_A_GLOBAL) ? im.w : 0);
     const size_t lds_bytes = (size_t)((lds_floats + 255) / 256 * 256) * sizeof(float);   // whole 1-KiB DMA pieces

@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/glomseg_plan.h"
 #include "conv_mfma.h"
 #include "dec_tail_args.h"
 #include "enc_head.h"
@@ -86,7 +87,7 @@ struct Model {
     void *ws = nullptr;
     size_t ws_bytes = 0;
     int ws_n = 0, ws_h = 0, ws_w = 0;
-    Act a0c, a0, inp1, inp2, r2[2], bb[3], a1, r3[2], cc[3], o2c, tt, t3, ee, ff;
+    Act a0c, a0, inp1, inp2, r2[2], bb[3], a1, r3[2], cc[3], o2c, l3c, tt, t3, ee, ff;
     float *prob = nullptr;   // ensemble scratch of this lane (ensemble_scratch: the first member's handle owns it)
     size_t prob_bytes = 0;
     std::map<std::string, std::pair<Act, int>> stages;   // name -> (activation, channels) of the last forward
@@ -185,7 +186,8 @@ static void pack_conv(const float *w, int cout, int cin, int k, float *dst, int 
 // (F_FUSE1X1); empty = no fusion.
 static bool pack_block(WeightTable &t, BlobBuilder &bb, const std::string &pre, bool down, int level, PackedConv &pc,
                        const float *dual = nullptr, int dual_coff = 0, int dual_c = 0, const std::string &next = "",
-                       const float *in2_bn = nullptr, int in2_c0 = 0, int in2_cn = 0, int in2_c = 0)
+                       const float *in2_bn = nullptr, int in2_c0 = 0, int in2_cn = 0, int in2_c = 0,
+                       const float *side_w = nullptr, int side_n = 0)
 {
     // level 2: cin 19 (down) / 64, n = 12, n1 = 16;  level 3: cin 131 (down) / 128, n = 25, n1 = 28
     const int n = level == 2 ? 12 : 25, n1 = level == 2 ? 16 : 28, nOut = n1 + 4 * n;
@@ -198,7 +200,13 @@ static bool pack_block(WeightTable &t, BlobBuilder &bb, const std::string &pre, 
         return false;
     const int c1_floats = conv_wfloats(cinp, taps, 1, n, n, false);
     const int bnl_c = cinp + kl;   // F_BNLOAD table: one entry per (padded) input channel + an all-zero slot of one k-group
-    pc.c1 = bb.reserve(c1_floats + (in2_bn ? 3 * bnl_c : 0));
+    // F_SIDE1X1: the class weights [side_n][cin] of a 1x1 over this reduce's input, as [cinp + SIDE_ZROWS][SIDE_REC] behind the table above
+    const int side_at = side_table_offset(c1_floats, cinp, kl);
+    pc.c1 = bb.reserve(side_w ? side_at + side_table_floats(cinp) : c1_floats + (in2_bn ? 3 * bnl_c : 0));
+    if (side_w)
+        for (int ch = 0; ch < cin; ++ch)
+            for (int k = 0; k < side_n; ++k)
+                bb.data[pc.c1 + side_at + (size_t)ch * SIDE_REC + k] = side_w[(size_t)k * cin + ch];
     pack_conv(wc1, n, cin, down ? 3 : 1, bb.data.data() + pc.c1, 0, taps, cinp, n);
     if (in2_bn) {   // [scale | shift | alpha][bnl_c]: identity, except the cat's BR for the channels that are stored raw
         float *x = bb.data.data() + pc.c1 + c1_floats;
@@ -295,6 +303,8 @@ static gs_status layout_workspace(Model *m, int n, int H, int W)
     for (int i = 0; i < 3; ++i)
         m->cc[i] = make_act(128, 128, H3, W3, 0, 0, 0, 0);
     m->o2c = make_act(cls, cls, H2, W2, 0, 0, 0, 0);
+    // level3_C's raw output, written by the stride-2 reduce (F_SIDE1X1) when the plan says so; else a token buffer
+    m->l3c = !m->encoder_only && l3c_side_sums(cls) ? make_act(cls, cls, H2, W2, 0, 0, 0, 0) : make_act(1, 1, 8, 8, 0, 0, 0, 0);
     // (twelve classes and more: combine_l2_l3.1's 3x3 runs on the matrix cores and reads its input with a zero halo; t3 is its output)
     const bool dec3_mfma = dec3_on_mfma(cls);
     m->tt = dec3_mfma ? make_act(2 * cls, 2 * cls, H2, W2, 1, 1, 32, 1) : make_act(2 * cls, 2 * cls, H2, W2, 0, 0, 0, 0);
@@ -306,7 +316,7 @@ static gs_status layout_workspace(Model *m, int n, int H, int W)
     if (lazy_b2)
         m->bb[0] = Act();   // no storage of its own
     Act *all[] = {&m->a0c, &m->inp1, &m->inp2, &m->r2[0], &m->r2[1], &m->bb[0], &m->bb[1], &m->bb[2], &m->a1, &m->r3[0], &m->r3[1],
-                  &m->cc[0], &m->cc[1], &m->cc[2], &m->o2c, &m->tt, &m->t3, &m->ff};
+                  &m->cc[0], &m->cc[1], &m->cc[2], &m->o2c, &m->l3c, &m->tt, &m->t3, &m->ff};
     for (Act *a : all) {   // kernels address one image with 32-bit byte offsets (buffer soffset / voffset)
         if ((unsigned long long)a->sn * sizeof(float) >= (1ull << 31)) {
             set_error("tile %dx%d is too large: an activation of one image exceeds 2 GiB", H, W);
@@ -505,8 +515,17 @@ static gs_status launch_l2_esp_last(const Model *m, form::l2_esp_last f, const C
 }
 
 // (the F_BNLOAD forms: planes 64..127 of output1_cat hold output1_0 RAW, b2 is applied to the B operands on load)
-static gs_status launch_l3_reduce(const Model *m, form::l3_reduce f, const ConvArgs &ca, hipStream_t s)
+// side5: the plan's l3c_in_reduce -- every form also computes the five-class level3_C into ca.side (F_SIDE1X1)
+static gs_status launch_l3_reduce(const Model *m, form::l3_reduce f, bool side5, const ConvArgs &ca, hipStream_t s)
 {
+    constexpr int SIDE5 = F_SIDE1X1(5);
+    if (side5)
+        switch (f) {
+        case form::l3_reduce::BNL_P1: return launch_conv_mfma<CFG_L3_C1S_BNL_P1, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD | SIDE5>(ca, m->num_cus, s);
+        case form::l3_reduce::BNL: return launch_conv_mfma<CFG_L3_C1S_BNL, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD | SIDE5>(ca, m->num_cus, s);
+        case form::l3_reduce::C1S: return launch_conv_mfma<CFG_L3_C1S, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | SIDE5>(ca, m->num_cus, s);
+        case form::l3_reduce::none: return not_planned("l3_reduce");
+        }
     switch (f) {
     case form::l3_reduce::BNL_P1: return launch_conv_mfma<CFG_L3_C1S_BNL_P1, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD>(ca, m->num_cus, s);
     case form::l3_reduce::BNL:
@@ -710,15 +729,25 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
 
     // ---- level 3 (Model.py:361-366)
     int rd3 = 0;
-    L.run(K_L3_C1S, px3 * (131 * 9 * 25 * 2), [&] {
+    L.run(K_L3_C1S, px3 * (131 * 9 * 25 * 2) + (plan.l3c_in_reduce ? px2 * (131 * m->classes * 2) : 0), [&] {
         GS_DIAG_TRY(diag_reduce_s2(m, 3, conv_args(m->a1, wb + m->l3_0.c1, m->r3[0], nullptr, n), s, dst_));
         ConvArgs ca = conv_args(m->a1, wb + m->l3_0.c1, m->r3[0], nullptr, n);
         if (lazy_b2) {   // planes 64..127 of output1_cat hold output1_0 RAW: b2 is applied to the B operands on load
             ca.bnl_s0 = 64 / 2;      // k-groups of two channels
             ca.bnl_s1 = 128 / 2;
         }
-        return launch_l3_reduce(m, plan.l3_reduce, ca, s);
+        if (plan.l3c_in_reduce) {
+            ca.side = m->l3c.base;
+            ca.side_sn = m->l3c.sn;
+            ca.side_sc = m->l3c.sc;
+            ca.side_pitch = m->l3c.pitch;
+            ca.side_off = m->l3c.off;
+            ca.side_img_bytes = (unsigned)(m->l3c.sn * sizeof(float));
+        }
+        return launch_l3_reduce(m, plan.l3_reduce, plan.l3c_in_reduce, ca, s);
     });
+    if (plan.l3c_in_reduce)
+        m->set_stage("level3_C", m->l3c, m->classes);
     L.run(K_L3_DOWN, px3 * (25 * 9 * 128 * 2) + (m->l3_0.fused_next ? px3 * (128 * 25 * 2) : 0), [&] {
         const ConvArgs ca = conv_args(m->r3[rd3], wb + m->l3_0.br, m->cc[0], nullptr, n);
         return launch_l3_down(m, plan.l3_down, m->l3_0.fused_next ? with_fused(ca, m->r3[rd3 ^ 1], 25) : ca, s);
@@ -798,19 +827,26 @@ static gs_status decode(Model *m, Launcher &L, const ForwardPlan &plan, const Fo
     m->set_stage("up_l3", m->o2c, ncls);
 
     // ---- level3_C + cat + BR (Model.py:372-373)
-    L.run(K_DEC2, px2 * (131 * ncls * 2), [&] {
+    L.run(K_DEC2, plan.l3c_in_reduce ? 0 : px2 * (131 * ncls * 2), [&] {
         Dec2Args a{};
+        a.o2c = view(m->o2c);
+        a.br = wb + m->cbr0;
+        a.t = view(m->tt);
+        a.N = n;
+        a.classes = ncls;
+        if constexpr (l3c_side_sums(CLS)) {
+            if (plan.l3c_in_reduce) {   // level3_C came out of the stride-2 reduce: what is left is the cat's BR over 2 * CLS small planes
+                a.a1 = view(m->l3c);
+                hipLaunchKernelGGL(dec2_br_kernel<CLS>, dim3(blocks_for((long long)n * H2 * W2)), dim3(256), 0, s, a);
+                return GS_OK;
+            }
+        }
         a.a1 = view(m->a1);
         a.raw = view(m->bb[0]);
         a.b2 = wb + m->b2;
         a.raw_c0 = 64;
         a.raw_cn = enc.lazy_b2 ? 64 : 0;
-        a.o2c = view(m->o2c);
         a.w3c = wb + m->w3c;
-        a.br = wb + m->cbr0;
-        a.t = view(m->tt);
-        a.N = n;
-        a.classes = ncls;
         hipLaunchKernelGGL(dec2_kernel<CLS>, dim3((unsigned)(((long long)n * H2 * W2 + 63) / 64)), dim3(256), 0, s, a);   // 64 pixels x 4 channel quarters
         return GS_OK;
     });
@@ -913,7 +949,7 @@ static gs_status decode(Model *m, Launcher &L, const ForwardPlan &plan, const Fo
 static gs_status forward_any(Model *m, const ForwardReq &r)
 {
     Launcher L{m, r.s, GS_OK, r.n};
-    const ForwardPlan plan = plan_forward(r.n, r.H, r.W, m->p, m->q, m->cp, m->num_cus, no_vec());   // every choice of a kernel form
+    const ForwardPlan plan = plan_forward(r.n, r.H, r.W, m->p, m->q, m->cp, m->num_cus, no_vec(), m->encoder_only);   // every choice of a kernel form
     const Encoded e = encode(m, L, plan, r);
     switch (m->cp) {
     case 5: return decode<5>(m, L, plan, r, e);
@@ -1152,7 +1188,11 @@ gs_status gs_espnet_create(const float *blob, const gs_layer_desc *table, int n_
     for (int i = 0; i < p; ++i)
         if (!pack_block(t, bb, e + "level2." + std::to_string(i), false, 2, m.l2[i], i == p - 1 ? b2f.data() : nullptr, 0, 131, next2(i + 1)))
             return GS_ERR_INVALID;
-    if (!pack_block(t, bb, e + "level3_0", true, 3, m.l3_0, nullptr, 0, 0, next3(0), b2f.data(), 64, 64, 131)) return GS_ERR_INVALID;
+    // (the reduce of a five-class decoder model also computes level3_C: forward_plan.h, l3c_side_sums)
+    const float *w3c_side = nullptr;
+    if (!m.encoder_only && l3c_side_sums(m.cp) && !(w3c_side = t.get("level3_C.conv.weight", {classes, 131, 1, 1}))) return GS_ERR_INVALID;
+    if (!pack_block(t, bb, e + "level3_0", true, 3, m.l3_0, nullptr, 0, 0, next3(0), b2f.data(), 64, 64, 131, w3c_side, classes))
+        return GS_ERR_INVALID;
     m.l3.resize(q);
     for (int i = 0; i < q; ++i)
         if (!pack_block(t, bb, e + "level3." + std::to_string(i), false, 3, m.l3[i], nullptr, 0, 0, next3(i + 1))) return GS_ERR_INVALID;
@@ -1472,7 +1512,7 @@ gs_status gs_espnet_block_forward(gs_espnet *h, int kind, int level, int index, 
             r = kind == 1 ? launch_l2_down(&m, unfused_l2_down(dst.W, no_vec()), bca, s)
                           : launch_l2_esp_fused(&m, unfused_l2_esp(dst.W, no_vec()), bca, s);
         } else {
-            r = kind == 1 ? launch_l3_reduce(&m, form::l3_reduce::C1S, rca, s) : launch_l3_c1(&m, rca, s);
+            r = kind == 1 ? launch_l3_reduce(&m, form::l3_reduce::C1S, false, rca, s) : launch_l3_c1(&m, rca, s);
             if (r != GS_OK) return r;
             r = kind == 1 ? launch_l3_down(&m, unfused_l3_down(dst.W, no_vec()), bca, s)
                           : launch_l3_esp_last(&m, whole_row_l3_esp(dst.W, no_vec()), bca, s);
@@ -1505,6 +1545,17 @@ gs_status gs_espnet_plan_forward(int n, int height, int width, int p, int q, int
         return GS_OK;
     GS_REQUIRE(cap >= kLaunchClassCount, "gs_espnet_plan_forward: %d entries needed, room for %d", kLaunchClassCount, cap);
     plan_forward(n, height, width, p, q, padded_classes(classes), num_cus, no_vec()).codes(out_forms);
+    return GS_OK;
+}
+
+gs_status gs_espnet_plan_flags(int n, int height, int width, int p, int q, int classes, int encoder_only, int num_cus, int *flags)
+{
+    GS_REQUIRE(flags, "gs_espnet_plan_flags: null argument");
+    int count = 0;
+    gs_status st = gs_espnet_plan_forward(n, height, width, p, q, classes, num_cus, nullptr, 0, &count);   // (the same refusals)
+    if (st != GS_OK) return st;
+    const ForwardPlan pl = plan_forward(n, height, width, p, q, padded_classes(classes), num_cus, no_vec(), encoder_only != 0);
+    *flags = (pl.lazy_b2 ? GS_PLAN_LAZY_B2 : 0) | (pl.l3c_in_reduce ? GS_PLAN_L3C_IN_REDUCE : 0);
     return GS_OK;
 }
 

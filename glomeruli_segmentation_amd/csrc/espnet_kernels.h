@@ -520,16 +520,6 @@ __global__ void __launch_bounds__(256) dec2_kernel(const Dec2Args a)
     for (int k = 0; k < CLS; ++k)
         s[k] = 0.0f;
     const int cb = 32 * w;
-#if defined(GS_DIAG) && defined(DEC2_X_NOCAT)
-    // gain ceiling for "level3_C computed elsewhere" (profiles/r05_ab_level3c_fusion.txt; results wrong by construction): dec2
-    // without its read of the 131 planes of output1_cat -- five planes of a precomputed level3_C output stand in
-    if (w == 0) {
-#pragma unroll
-        for (int k = 0; k < CLS; ++k)
-            s[k] = ld_stream<NT_DEC2_LD>(at(a.a1, n, k, y, x));
-    }
-    if (false)
-#endif
     if (cb >= a.raw_c0 && cb < a.raw_c0 + a.raw_cn) {   // (uniform) lazy b2: these planes are raw; BN + PReLU of the cat's BR here
 #pragma unroll 16
         for (int c = cb; c < cb + 32; ++c) {
@@ -549,9 +539,6 @@ __global__ void __launch_bounds__(256) dec2_kernel(const Dec2Args a)
                 s[k] = fmaf(pc[k], v, s[k]);
         }
     }
-#if defined(GS_DIAG) && defined(DEC2_X_NOCAT)
-    if (false)
-#endif
     if (w == 3) {
 #pragma unroll
         for (int c = 128; c < 131; ++c) {
@@ -584,6 +571,27 @@ __global__ void __launch_bounds__(256) dec2_kernel(const Dec2Args a)
     for (int k = 0; k < 2 * CLS; ++k)
         if (k % CLS < ncls)
             *at(a.t, n, k, y, x) = tv[k];
+}
+
+// dec2 when level3_C's raw output already exists (the stride-2 reduce computed it: F_SIDE1X1, conv_mfma.h; a.a1 = those CLS
+// planes): cat with output2_c, BR(2*classes).  One thread per 1/4-scale pixel.
+template <int CLS>
+__global__ void __launch_bounds__(256) dec2_br_kernel(const Dec2Args a)
+{
+    const int H2 = a.t.H, W2 = a.t.W;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)a.N * H2 * W2)
+        return;
+    const int x = (int)(idx % W2);
+    const int y = (int)((idx / W2) % H2);
+    const int n = (int)(idx / ((long long)W2 * H2));
+    const int ncls = real_classes<CLS>(a.classes);
+#pragma unroll
+    for (int k = 0; k < CLS; ++k)
+        if (k < ncls) {
+            *at(a.t, n, k, y, x) = bn_prelu(*at(a.a1, n, k, y, x), a.br, 2 * CLS, k);
+            *at(a.t, n, CLS + k, y, x) = bn_prelu(*at(a.o2c, n, k, y, x), a.br, 2 * CLS, CLS + k);
+        }
 }
 
 // combine_l2_l3[1] CBR(2*classes,classes,3) -> up_l2 deconv -> BR(classes).  One thread per

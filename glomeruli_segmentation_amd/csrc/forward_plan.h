@@ -24,6 +24,10 @@ constexpr bool l3_c1_fused(int i, int q) { return (CFG_FUSE_L3 == 2 || (CFG_FUSE
 // the decoder by padded class count: combine_l2_l3.1's 3x3 on the matrix cores from twelve planes on (else dec3_kernel),
 // the fused tail for the five-class networks (else a conv_mfma launch + dec4_kernel); MFMA rows 16 up to sixteen planes
 constexpr bool dec3_on_mfma(int cp) { return cp >= 12; }
+// level3_C (the decoder's 1x1 over output1_cat) is computed by the level-3 stride-2 reduce, which has every value of that map
+// in a register (F_SIDE1X1), and dec2 reads its `cp` planes instead of the 131.  Five class planes only: at four pixel runs
+// per lane the side sums take 2 * cp * 4 registers, and eight planes do not fit beside the reduce's 196-207 without spilling.
+constexpr bool l3c_side_sums(int cp) { return cp == 5; }
 constexpr bool dec_tail_fused(int cp) { return cp == 5; }
 constexpr int dec_mt(int cp) { return cp <= 16 ? 16 : 32; }
 constexpr int dec_pixels(int cp) { return cp <= 16 ? 8 : 4; }
@@ -125,6 +129,7 @@ constexpr int kLaunchClassCount = (int)(sizeof kLaunchClasses / sizeof kLaunchCl
 struct ForwardPlan {
     GS_LAUNCH_CLASSES(GS_PLAN_MEMBER)
     bool lazy_b2 = false;
+    bool l3c_in_reduce = false;   // the stride-2 reduce also writes level3_C's raw output (F_SIDE1X1); dec2 reads that
     // one form code per launch class, in table order (the ABI's view of a plan)
     void codes(int *out) const { GS_LAUNCH_CLASSES(GS_PLAN_CODE) }
 };
@@ -166,14 +171,16 @@ constexpr form::l3_esp_last whole_row_l3_esp(int W3, bool no_vec)
 
 // What a forward of n tiles of H x W runs on a device with num_cus CUs, for ESPNet(classes, p, q) with cp = padded_classes(classes).
 // no_vec (GS_NO_VEC of -DGS_DIAG builds; false in the product) keeps every launch off the vector mappings and the small-batch forms.
-// (An ESPNet-C handle stops before the decoder: its dec3 / dec_conv entries are not launched.)
-inline ForwardPlan plan_forward(int n, int H, int W, int p, int q, int cp, int num_cus, bool no_vec)
+// (An ESPNet-C handle -- encoder_only -- stops before the decoder: its dec3 / dec_conv entries are not launched, and nothing of
+// it asks for level3_C.)
+inline ForwardPlan plan_forward(int n, int H, int W, int p, int q, int cp, int num_cus, bool no_vec, bool encoder_only = false)
 {
     namespace f = form;
     const int W1 = W / 2, H2 = H / 4, W2 = W / 4, H3 = H / 8, W3 = W / 8;
     const long long cus = num_cus;
     ForwardPlan pl;
     pl.lazy_b2 = b2_is_lazy(p);
+    pl.l3c_in_reduce = !encoder_only && l3c_side_sums(cp);   // in every form of the reduce: lazy or not, any task shape
 
     // ---- level 2.  Small batches: 32-pixel tasks (two pixels per lane) while there are at most CFG_SMALL2_WAVES of them per CU
     const bool small2 = CFG_SMALL2_WAVES > 0 && (long long)n * H2 * cdiv(W2, 64) * 2 <= cus * CFG_SMALL2_WAVES &&

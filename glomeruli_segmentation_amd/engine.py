@@ -322,6 +322,14 @@ def plan_forward(n, height, width, p, q, classes, num_cus):
     return {cls: forms[codes[k]][0] for k, (cls, forms) in enumerate(table) if codes[k] != _lib.GS_FORM_NONE}
 
 
+def plan_flags(n, height, width, p, q, classes, num_cus, encoder_only=False):
+    """{"lazy_b2": bool, "l3c_in_reduce": bool}: the decisions of the same plan that are no form of a launch class
+    (gs_espnet_plan_flags, include/glomseg_plan.h).  Host-only: needs no GPU."""
+    flags = ctypes.c_int()
+    _lib.check(_lib.load().gs_espnet_plan_flags(n, height, width, p, q, classes, int(bool(encoder_only)), num_cus, ctypes.byref(flags)))
+    return {"lazy_b2": bool(flags.value & _lib.GS_PLAN_LAZY_B2), "l3c_in_reduce": bool(flags.value & _lib.GS_PLAN_L3C_IN_REDUCE)}
+
+
 def crop_preprocess(crop_u8, mean, std, out_h, out_w, out=None):
     """uint8 BGR crop [h,w,3] on the GPU -> normalised, bilinearly resized fp32 [3,out_h,out_w]
     (VisualizeResults_iou.py:107-116 for a crop that is not network-sized)."""
