@@ -77,6 +77,10 @@ class DetectorPlan(ctypes.Structure):
                 ("layers", DetectorLayerPlan * 16)]
 
 
+class WeightPiece(ctypes.Structure):
+    _fields_ = [("name", ctypes.c_char * 32), ("offset", ctypes.c_longlong), ("floats", ctypes.c_longlong)]
+
+
 class KernelTime(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 64), ("total_ms", ctypes.c_double), ("launches", ctypes.c_int64),
                 ("flops_per_tile", ctypes.c_double)]
@@ -150,6 +154,9 @@ SCORING_PROTOTYPES = {
 # every symbol include/glomseg_plan.h declares (an addition to ABI 9 with a header of its own)
 PLAN_PROTOTYPES = {
     "gs_espnet_plan_flags": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]),
+    "gs_espnet_pack_weights": (_I, [_P, ctypes.POINTER(LayerDesc), _I, _I, _I, _I, _I, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                                ctypes.POINTER(WeightPiece), _I, ctypes.POINTER(_I)]),
+    "gs_espnet_workspace_plan": (_I, [_I] * 7 + [ctypes.POINTER(ctypes.c_size_t)]),
 }
 GS_PLAN_LAZY_B2, GS_PLAN_L3C_IN_REDUCE = 1, 2
 

@@ -244,12 +244,7 @@ constexpr int F_BNLOAD = 8388608;  // see ConvArgs::bnl_s0
 // The class count sits in bits 27..30 of FLAGS; needs F_S2PAIR, TAPS == 9, STRIDE == 2, MT == 32.
 constexpr int F_SIDE_SHIFT = 27;
 constexpr int F_SIDE1X1(int classes) { return classes << F_SIDE_SHIFT; }
-constexpr int SIDE_REC = 8;   // floats per channel record of the table (dec2_record of up to eight classes)
-constexpr int SIDE_ZROWS = 16;   // zero rows behind the channels' (a chunk's row groups read rows CINP + g * KL of them for tap row 0)
-constexpr int side_table_floats(int CINP) { return (CINP + SIDE_ZROWS) * SIDE_REC; }
-// float offset of the side table behind a configuration's image: the F_BNLOAD table is part of the blob of such a reduce
-// whether the form applies it or not
-constexpr int side_table_offset(int image_total, int CINP, int KL) { return image_total + (3 * (CINP + KL) + 3) / 4 * 4; }
+// (SIDE_REC, SIDE_ZROWS, side_table_floats, side_table_offset: espnet_facts.h, shared with the weight packer)
 constexpr int F_X_NOLOAD = 16;  // GS_DIAG timing experiments only (results are garbage): no activation loads in the loop
 constexpr int F_X_NOLDS = 32;   // GS_DIAG: no LDS weight reads in the loop
 constexpr int F_X_NOEPI = 64;   // GS_DIAG: no epilogue at all
@@ -263,22 +258,7 @@ constexpr int F_X_RESL2 = 33554432;     // GS_DIAG: the residual loads fall into
 constexpr int F_X_STL2 = 67108864;      // GS_DIAG: likewise the result stores
 constexpr int F_X_ALL = F_X_NOLOAD | F_X_NOLDS | F_X_NOEPI | F_X_STAMP | F_X_STAMP2 | F_X_NOEPIMEM | F_X_RESL2 | F_X_STL2;
 
-// Float layout of a configuration's packed image in the weight blob: [weights NDIL*TAPS*CINP*NROW | BN scale, shift,
-// alpha (3*COUT, twice with F_DUAL) | F_FUSE1X1 table NDIL*NACC*64], rounded up to whole float4s.
-struct ConvImage {
-    int nrow, cout, w, bn, tab, total;
-};
-constexpr ConvImage conv_image(int CINP, int TAPS, int NDIL, int NOUT1, int NOUT, bool bn, bool dual = false, int fuse_nacc = 0)
-{
-    ConvImage im{};
-    im.nrow = NOUT1 > NOUT ? NOUT1 : NOUT;
-    im.cout = NOUT1 + (NDIL - 1) * NOUT;
-    im.w = NDIL * TAPS * CINP * im.nrow;
-    im.bn = (bn ? 3 * im.cout : 0) + (dual ? 3 * im.cout : 0);
-    im.tab = NDIL * fuse_nacc * 64;
-    im.total = (im.w + im.bn + im.tab + 3) / 4 * 4;
-    return im;
-}
+// (the float layout of a configuration's packed image in the weight blob -- ConvImage, conv_image, conv_wfloats: espnet_facts.h)
 
 #ifndef CFG_STAGE_ROT
 #define CFG_STAGE_ROT 17   // 0 = every workgroup stages the weight image in the same order
@@ -1003,12 +983,6 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
                 a.stamp[sbase2 + 2 * c + 1] = __builtin_amdgcn_s_memrealtime();
         }
     }
-}
-
-// number of floats of a configuration's image in the weight blob (see conv_image)
-constexpr int conv_wfloats(int CINP, int TAPS, int NDIL, int NOUT1, int NOUT, bool bn, bool dual = false, int fuse_nacc = 0)
-{
-    return conv_image(CINP, TAPS, NDIL, NOUT1, NOUT, bn, dual, fuse_nacc).total;
 }
 
 // Per (kernel instantiation, device): the dynamic-LDS attribute and the occupancy figure.  One process normally drives one

@@ -31,8 +31,7 @@ struct DecTailArgs {
     int team;             // exchanging form (dec_tail.h, EXCH): waves per team = strips per row rounded up to a power of two
 };
 
-constexpr int DT_A_FLOATS = 18 * 64;
-constexpr int DT_PACK_FLOATS = DT_A_FLOATS + 16 + 100;
+// (DT_A_FLOATS, DT_PACK_FLOATS, the sizes of wpack: espnet_facts.h)
 
 // conv CBR(19+classes, classes, 3) + classifier deconvolution + argmax + counts in one or two launches (dec_tail.h)
 gs_status launch_dec_tail(DecTailArgs a, int num_cus, hipStream_t stream);

@@ -20,8 +20,10 @@
 #include "espnet_config.h"
 #include "forward_plan.h"
 #include "espnet_kernels.h"
+#include "espnet_weights.h"
 #include "host_copy.h"
 #include "host_pipe.h"
+#include "workspace_plan.h"
 
 namespace gs {
 
@@ -57,12 +59,7 @@ static const char *kKernelNames[K_COUNT] = {
     "conv_l3_esp_branches", "dec1_kernel", "dec2_kernel", "dec3_kernel", "conv_dec_cbr", "dec4_kernel", "dec_tail_kernel",
     "enc_head_kernel", "enc_head_ens_kernel"};
 
-struct PackedConv {   // float offsets into the device weight blob
-    long long c1 = -1, br = -1;
-    bool fused_next = false;   // br carries the F_FUSE1X1 table of the following block's c1
-};
-
-struct Model {
+struct Model : Workspace {   // (the activations: workspace_plan.h)
     int classes = 0, p = 0, q = 0;
     int cp = 0;   // the padded class count the decoder kernels are instantiated for: 5 for the five-class networks (the fast path),
                   // else `classes` rounded up to a multiple of four (espnet_kernels.h, "CLASS COUNTS")
@@ -74,20 +71,12 @@ struct Model {
     static constexpr int variant = 0;
 #endif
     float *dblob = nullptr;
-    // offsets (floats) into dblob
-    float stem_params[537] = {0};   // host copy of level1 weights + folded bn1 + folded b1: they travel as kernel arguments
-    long long w1, bn1, b1, b2, b3, wcls, br, wup3, w3c, cbr0, wcc, bncc, wup2, bnu2, wclassifier, wtail;
-    long long wconv = -1;   // the generic decoder tail's conv_mfma image (class counts other than five)
-    long long wcc_mfma = -1;   // twelve classes and more: combine_l2_l3.1 as a conv_mfma image (see decode)
-    PackedConv l2_0;
-    std::vector<PackedConv> l2, l3;
-    PackedConv l3_0;
+    EspnetOffsets w;   // float offsets into dblob, and the stem's parameters: they travel as kernel arguments (espnet_weights.h)
 
     // workspace
     void *ws = nullptr;
     size_t ws_bytes = 0;
     int ws_n = 0, ws_h = 0, ws_w = 0;
-    Act a0c, a0, inp1, inp2, r2[2], bb[3], a1, r3[2], cc[3], o2c, l3c, tt, t3, ee, ff;
     float *prob = nullptr;   // ensemble scratch of this lane (ensemble_scratch: the first member's handle owns it)
     size_t prob_bytes = 0;
     std::map<std::string, std::pair<Act, int>> stages;   // name -> (activation, channels) of the last forward
@@ -111,169 +100,6 @@ struct Model {
 };
 
 // ------------------------------------------------------------------------------------------
-struct WeightTable {
-    const float *blob;
-    std::map<std::string, const gs_layer_desc *> by_name;
-    std::string prefix;   // "encoder." for the full net, "" for ESPNet_Encoder tables
-    bool ok = true;
-    const float *get(const std::string &name, std::initializer_list<int> shape)
-    {
-        auto it = by_name.find(name);
-        if (it == by_name.end()) {
-            set_error("weight tensor '%s' missing from the table", name.c_str());
-            ok = false;
-            return nullptr;
-        }
-        const gs_layer_desc *d = it->second;
-        int i = 0;
-        bool match = d->ndim == (int)shape.size();
-        for (int s : shape)
-            match = match && d->shape[i++] == s;
-        if (!match) {
-            set_error("weight tensor '%s' has the wrong shape", name.c_str());
-            ok = false;
-            return nullptr;
-        }
-        return blob + d->offset;
-    }
-};
-
-struct BlobBuilder {
-    std::vector<float> data;
-    long long reserve(size_t n)
-    {
-        const size_t at = (data.size() + 3) / 4 * 4;   // 16-byte aligned pieces (float4 LDS staging)
-        data.resize(at + (n + 3) / 4 * 4, 0.0f);
-        return (long long)at;
-    }
-    long long push(const float *src, size_t n)
-    {
-        const long long at = reserve(n);
-        std::memcpy(data.data() + at, src, n * sizeof(float));
-        return at;
-    }
-};
-
-// BatchNorm2d(eps=1e-3).eval() folded to y = x*scale + shift, plus the PReLU slope (1 when absent):
-// layout [scale | shift | alpha][C].  reference: Model.py:21-22,44-45,141-142
-static bool fold_bn(WeightTable &t, const std::string &bn, const std::string &act, int C, float *dst, bool with_alpha = true)
-{
-    const float *g = t.get(bn + ".weight", {C}), *b = t.get(bn + ".bias", {C});
-    const float *m = t.get(bn + ".running_mean", {C}), *v = t.get(bn + ".running_var", {C});
-    const float *al = act.empty() ? nullptr : t.get(act + ".weight", {C});
-    if (!t.ok)
-        return false;
-    for (int c = 0; c < C; ++c) {
-        const double inv = 1.0 / std::sqrt((double)v[c] + 1e-3);
-        dst[c] = (float)((double)g[c] * inv);
-        dst[C + c] = (float)((double)b[c] - (double)m[c] * (double)g[c] * inv);
-        if (with_alpha)
-            dst[2 * C + c] = al ? al[c] : 1.0f;
-    }
-    return true;
-}
-
-// conv weight [cout][cin][k][k] -> LDS image rows [tap][cin_padded][nrow] of dilation slot `slot`
-static void pack_conv(const float *w, int cout, int cin, int k, float *dst, int slot, int taps, int cinp, int nrow)
-{
-    for (int tap = 0; tap < taps; ++tap)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int co = 0; co < cout; ++co)
-                dst[(((size_t)slot * taps + tap) * cinp + ci) * nrow + co] = w[((size_t)co * cin + ci) * k * k + tap];
-}
-
-// `next` names the block whose c1 (1x1 reduce of THIS block's output, Model.py:193) is computed in this block's epilogue
-// (F_FUSE1X1); empty = no fusion.
-static bool pack_block(WeightTable &t, BlobBuilder &bb, const std::string &pre, bool down, int level, PackedConv &pc,
-                       const float *dual = nullptr, int dual_coff = 0, int dual_c = 0, const std::string &next = "",
-                       const float *in2_bn = nullptr, int in2_c0 = 0, int in2_cn = 0, int in2_c = 0,
-                       const float *side_w = nullptr, int side_n = 0)
-{
-    // level 2: cin 19 (down) / 64, n = 12, n1 = 16;  level 3: cin 131 (down) / 128, n = 25, n1 = 28
-    const int n = level == 2 ? 12 : 25, n1 = level == 2 ? 16 : 28, nOut = n1 + 4 * n;
-    const int cin = level == 2 ? (down ? 19 : 64) : (down ? 131 : 128);
-    const int kl = level == 2 ? 4 : 2;
-    const int cinp = (cin + kl - 1) / kl * kl;
-    const int taps = down ? 9 : 1;
-    const float *wc1 = t.get(pre + ".c1.conv.weight", {n, cin, down ? 3 : 1, down ? 3 : 1});
-    if (!t.ok)
-        return false;
-    const int c1_floats = conv_wfloats(cinp, taps, 1, n, n, false);
-    const int bnl_c = cinp + kl;   // F_BNLOAD table: one entry per (padded) input channel + an all-zero slot of one k-group
-    // F_SIDE1X1: the class weights [side_n][cin] of a 1x1 over this reduce's input, as [cinp + SIDE_ZROWS][SIDE_REC] behind the table above
-    const int side_at = side_table_offset(c1_floats, cinp, kl);
-    pc.c1 = bb.reserve(side_w ? side_at + side_table_floats(cinp) : c1_floats + (in2_bn ? 3 * bnl_c : 0));
-    if (side_w)
-        for (int ch = 0; ch < cin; ++ch)
-            for (int k = 0; k < side_n; ++k)
-                bb.data[pc.c1 + side_at + (size_t)ch * SIDE_REC + k] = side_w[(size_t)k * cin + ch];
-    pack_conv(wc1, n, cin, down ? 3 : 1, bb.data.data() + pc.c1, 0, taps, cinp, n);
-    if (in2_bn) {   // [scale | shift | alpha][bnl_c]: identity, except the cat's BR for the channels that are stored raw
-        float *x = bb.data.data() + pc.c1 + c1_floats;
-        for (int c = 0; c < bnl_c; ++c) {
-            const bool raw = c >= in2_c0 && c < in2_c0 + in2_cn, zero = c >= cinp;
-            x[c] = zero ? 0.0f : raw ? in2_bn[c] : 1.0f;
-            x[bnl_c + c] = zero ? 0.0f : raw ? in2_bn[in2_c + c] : 0.0f;
-            x[2 * bnl_c + c] = raw ? in2_bn[2 * in2_c + c] : 1.0f;
-        }
-    }
-
-    const int rcinp = (n + kl - 1) / kl * kl;
-    const int mt = level == 2 ? 16 : 32, nacc = level == 2 ? 4 : 16;
-    pc.fused_next = !next.empty();
-    const ConvImage im = conv_image(rcinp, 9, 5, n1, n, true, dual != nullptr, pc.fused_next ? nacc : 0);
-    pc.br = bb.reserve(im.total);
-    static const char *dn[5] = {".d1", ".d2", ".d4", ".d8", ".d16"};
-    for (int di = 0; di < 5; ++di) {
-        const int co = di == 0 ? n1 : n;
-        const float *w = t.get(pre + dn[di] + ".conv.weight", {co, n, 3, 3});
-        if (!t.ok)
-            return false;
-        pack_conv(w, co, n, 3, bb.data.data() + pc.br, di, 9, rcinp, n1);
-    }
-    if (pc.fused_next) {
-        // table[di][r][lane]: the A operand of the k-step "accumulator register r of slot di": lane = (k-group, c1 output
-        // row i); k-group kq of register r holds this block's channel cb + row(r, kq)
-        const float *w2 = t.get(next + ".c1.conv.weight", {n, nOut, 1, 1});
-        if (!t.ok)
-            return false;
-        float *tab = bb.data.data() + pc.br + im.w + im.bn;
-        for (int di = 0; di < 5; ++di) {
-            const int nout = di == 0 ? n1 : n, cb = di == 0 ? 0 : n1 + (di - 1) * n;
-            for (int r = 0; r < nacc; ++r)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int i = lane % mt, kq = lane / mt;
-                    const int row = mt == 32 ? (r & 3) + 8 * (r >> 2) + 4 * kq : kq * 4 + r;
-                    tab[(di * nacc + r) * 64 + lane] = (row < nout && i < n) ? w2[(size_t)i * nOut + cb + row] : 0.0f;
-                }
-        }
-    }
-    float *bnp = bb.data.data() + pc.br + im.w;
-    // DownSamplerB: self.bn / self.act (Model.py:141-142); ESP block: self.bn = BR(nOut) (Model.py:184)
-    if (dual)   // slice of the following concat's BR parameters, same [scale | shift | alpha][nOut] layout
-        for (int j = 0; j < 3; ++j)
-            for (int c = 0; c < nOut; ++c)
-                bnp[(3 + j) * nOut + c] = dual[j * dual_c + dual_coff + c];
-    return down ? fold_bn(t, pre + ".bn", pre + ".act", nOut, bnp) : fold_bn(t, pre + ".bn.bn", pre + ".bn.act", nOut, bnp);
-}
-
-// ------------------------------------------------------------------------------------------
-static Act make_act(int C, int Cp, int H, int W, int pad_t, int pad_b, int pad_l, int pad_r)
-{
-    Act a;
-    a.C = C;
-    a.Cp = Cp;
-    a.H = H;
-    a.W = W;
-    a.pitch = (int)round_up(pad_l + W + pad_r, 32);   // 128-byte rows: interior stores stay line-aligned
-    // + 96 floats: a plane stride that is a power of two (8192 floats at 1/8 scale) lands every channel of a
-    // pixel on the same HBM channel / L2 slice when a kernel walks the channels (dec1, the 1x1 reduces)
-    a.sc = (pad_t + H + pad_b) * a.pitch + 96;
-    a.off = pad_t * a.pitch + pad_l;
-    a.sn = (long long)Cp * a.sc;
-    return a;
-}
-
 static gs_status layout_workspace(Model *m, int n, int H, int W)
 {
     if (m->ws && n <= m->ws_n && H == m->ws_h && W == m->ws_w)
@@ -283,77 +109,25 @@ static gs_status layout_workspace(Model *m, int n, int H, int W)
         GS_HIP(hipFree(m->ws));
         m->ws = nullptr;
     }
-    const int cls = m->cp;   // padded class planes (the planes beyond m->classes stay zero)
-    const int H1 = H / 2, W1 = W / 2, H2 = H / 4, W2 = W / 4, H3 = H / 8, W3 = W / 8;
-    // comb_l2_l3 (planes 0..cls-1, written by dec3) and output0_cat (planes cls..cls+18, written by the stem) share one
-    // buffer in the order of the decoder's torch.cat (Model.py:375), so conv CBR(19+classes, classes, 3) reads its input as
-    // ONE 24-plane activation with zero pad on all four sides.  Plane cls+19 is never written: the level-2 strided reduce
-    // reads output0_cat padded to 20 channels (a multiple of the k-step) and its padding plane must be zeros, not a
-    // plane some other stage writes (a non-finite value there would survive the zero weight).
-    m->a0c = make_act(cls + 19, cls + 20, H1, W1, 1, 1, 32, 1);
-    m->inp1 = make_act(3, 3, H1, W1, 0, 0, 0, 0);
-    m->inp2 = make_act(3, 3, H2, W2, 0, 0, 0, 0);
-    for (int i = 0; i < 2; ++i)   // two reduced maps: a block reads one while its epilogue writes the next block's
-        m->r2[i] = make_act(12, 12, H2, W2, 16, 16, 32, 16);  // dilation up to 16
-    for (int i = 0; i < 3; ++i)
-        m->bb[i] = make_act(64, 64, H2, W2, 0, 0, 0, 0);
-    m->a1 = make_act(131, 132, H2, W2, 1, 0, 32, 1);
-    for (int i = 0; i < 2; ++i)
-        m->r3[i] = make_act(25, 26, H3, W3, 16, 16, 32, 16);
-    for (int i = 0; i < 3; ++i)
-        m->cc[i] = make_act(128, 128, H3, W3, 0, 0, 0, 0);
-    m->o2c = make_act(cls, cls, H2, W2, 0, 0, 0, 0);
-    // level3_C's raw output, written by the stride-2 reduce (F_SIDE1X1) when the plan says so; else a token buffer
-    m->l3c = !m->encoder_only && l3c_side_sums(cls) ? make_act(cls, cls, H2, W2, 0, 0, 0, 0) : make_act(1, 1, 8, 8, 0, 0, 0, 0);
-    // (twelve classes and more: combine_l2_l3.1's 3x3 runs on the matrix cores and reads its input with a zero halo; t3 is its output)
-    const bool dec3_mfma = dec3_on_mfma(cls);
-    m->tt = dec3_mfma ? make_act(2 * cls, 2 * cls, H2, W2, 1, 1, 32, 1) : make_act(2 * cls, 2 * cls, H2, W2, 0, 0, 0, 0);
-    m->t3 = dec3_mfma ? make_act(cls, cls, H2, W2, 0, 0, 0, 0) : make_act(1, 1, 8, 8, 0, 0, 0, 0);
-    m->ff = make_act(cls, cls, H1, W1, 0, 0, 0, 0);
-    // Lazy b2 (p > 0): output1_0 is stored RAW, once, straight into planes 64..127 of output1_cat -- bb[0] becomes a view of
-    // them -- and the consumers of output1_cat apply b2 to those planes on load (espnet_config.h, "Lazy b2").
-    const bool lazy_b2 = b2_is_lazy(m->p);
-    if (lazy_b2)
-        m->bb[0] = Act();   // no storage of its own
-    Act *all[] = {&m->a0c, &m->inp1, &m->inp2, &m->r2[0], &m->r2[1], &m->bb[0], &m->bb[1], &m->bb[2], &m->a1, &m->r3[0], &m->r3[1],
-                  &m->cc[0], &m->cc[1], &m->cc[2], &m->o2c, &m->l3c, &m->tt, &m->t3, &m->ff};
-    for (Act *a : all) {   // kernels address one image with 32-bit byte offsets (buffer soffset / voffset)
-        if ((unsigned long long)a->sn * sizeof(float) >= (1ull << 31)) {
-            set_error("tile %dx%d is too large: an activation of one image exceeds 2 GiB", H, W);
-            return GS_ERR_UNSUPPORTED;
-        }
-    }
-    const size_t slack = 64 * 1024;   // strips may over-read past a buffer's last row (masked lanes only)
-    size_t total = 0;
-    for (Act *a : all)
-        total += round_up(a->bytes(n) + slack, 256);
+    WorkspacePlan plan;   // every activation, its place in the allocation and the total: workspace_plan.h
+    const gs_status st = plan_workspace(n, H, W, m->cp, m->p, m->encoder_only, plan);
+    if (st != GS_OK)
+        return st;
     void *ws = nullptr;
-    if (hipMalloc(&ws, total) != hipSuccess) {
-        set_error("workspace allocation of %zu bytes failed (n=%d, %dx%d)", total, n, H, W);
+    if (hipMalloc(&ws, plan.bytes) != hipSuccess) {
+        set_error("workspace allocation of %zu bytes failed (n=%d, %dx%d)", plan.bytes, n, H, W);
         return GS_ERR_NOMEM;
     }
-    GS_HIP(hipMemset(ws, 0, total));   // halos and padded channel planes are zero from here on
+    GS_HIP(hipMemset(ws, 0, plan.bytes));   // halos and padded channel planes are zero from here on
     // (the fill runs on the NULL stream, which non-blocking streams -- the host pipelines' own, torch's side streams -- do not
     // wait for: a forward launched on one of them right after this call must not meet the fill still in flight)
     GS_HIP(hipDeviceSynchronize());
-    size_t at = 0;
-    for (Act *a : all) {
-        a->base = reinterpret_cast<float *>(static_cast<char *>(ws) + at);
-        at += round_up(a->bytes(n) + slack, 256);
-    }
-    if (lazy_b2) {
-        m->bb[0] = m->a1;
-        m->bb[0].base = m->a1.base + (long long)64 * m->a1.sc;
-        m->bb[0].C = 64;
-        m->bb[0].Cp = 64;
-    }
-    m->ee = m->a0c;   // comb_l2_l3 = the first planes of the concat buffer
-    m->ee.C = cls;
-    m->a0 = m->a0c;   // output0_cat = the planes after it (+ the zero plane)
-    m->a0.base = m->a0c.base + (long long)cls * m->a0c.sc;
-    m->a0.C = 19;
+    static_cast<Workspace &>(*m) = plan.acts;
+    int i = 0;
+    for (Act *a : acts_of(*m))
+        a->base = reinterpret_cast<float *>(static_cast<char *>(ws) + plan.at[i++]);
     m->ws = ws;
-    m->ws_bytes = total;
+    m->ws_bytes = plan.bytes;
     m->ws_n = n;
     m->ws_h = H;
     m->ws_w = W;
@@ -633,9 +407,9 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
             a.mean[i] = r.mean ? r.mean[i] : 0.0f;
             a.std[i] = r.stdv ? r.stdv[i] : 1.0f;
         }
-        std::memcpy(a.w1, m->stem_params, sizeof(float) * 432);
-        std::memcpy(a.bn1, m->stem_params + 432, sizeof(float) * 48);
-        std::memcpy(a.b1, m->stem_params + 480, sizeof(float) * 57);
+        std::memcpy(a.w1, m->w.stem_params, sizeof(float) * 432);
+        std::memcpy(a.bn1, m->w.stem_params + 432, sizeof(float) * 48);
+        std::memcpy(a.b1, m->w.stem_params + 480, sizeof(float) * 57);
         a.a0 = view(m->a0);
         a.inp1 = view(m->inp1);
         a.N = n;
@@ -651,7 +425,7 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
     });
     L.run(K_POOL, 0, [&] {
         hipLaunchKernelGGL(pool_kernel, dim3(blocks_for((long long)n * 3 * H2 * W2)), dim3(256), 0, s, view(m->inp1),
-                           view(m->inp2), n, 3, m->p > 0 ? wb + m->b2 : nullptr, view(m->a1), 128, 131);
+                           view(m->inp2), n, 3, m->p > 0 ? wb + m->w.b2 : nullptr, view(m->a1), 128, 131);
         return GS_OK;
     });
     m->set_stage("b1", m->a0, 19);
@@ -659,8 +433,8 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
 
     // ---- level 2 (Model.py:351-357): DownSamplerB(19,64) then p ESP blocks
     L.run(K_L2_C1S, px2 * (19 * 9 * 12 * 2), [&] {
-        GS_DIAG_TRY(diag_reduce_s2(m, 2, conv_args(m->a0, wb + m->l2_0.c1, m->r2[0], nullptr, n), s, dst_));
-        return launch_l2_reduce(m, conv_args(m->a0, wb + m->l2_0.c1, m->r2[0], nullptr, n), s);
+        GS_DIAG_TRY(diag_reduce_s2(m, 2, conv_args(m->a0, wb + m->w.l2_0.c1, m->r2[0], nullptr, n), s, dst_));
+        return launch_l2_reduce(m, conv_args(m->a0, wb + m->w.l2_0.c1, m->r2[0], nullptr, n), s);
     });
     // b2 = BR(131) over cat([output1, output1_0, inp2]) (Model.py:359) never runs as a kernel: the last ESP block stores
     // only its b2-normalised form (planes 0..63 of output1_cat), the pool kernel writes planes 128..130 normalised, and
@@ -690,24 +464,24 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
     const bool lazy_b2 = plan.lazy_b2;
     m->b2_lazy = lazy_b2;
     int rd2 = 0;   // index of the reduced map the next level-2 branch kernel reads
-    L.run(K_L2_DOWN, px2 * (12 * 9 * 64 * 2) + (m->l2_0.fused_next ? px2 * (64 * 12 * 2) : 0), [&] {
-        const ConvArgs ca = conv_args(m->r2[rd2], wb + m->l2_0.br, m->bb[0], nullptr, n);
-        return launch_l2_down(m, plan.l2_down, m->l2_0.fused_next ? with_fused(ca, m->r2[rd2 ^ 1], 12) : ca, s);
+    L.run(K_L2_DOWN, px2 * (12 * 9 * 64 * 2) + (m->w.l2_0.fused_next ? px2 * (64 * 12 * 2) : 0), [&] {
+        const ConvArgs ca = conv_args(m->r2[rd2], wb + m->w.l2_0.br, m->bb[0], nullptr, n);
+        return launch_l2_down(m, plan.l2_down, m->w.l2_0.fused_next ? with_fused(ca, m->r2[rd2 ^ 1], 12) : ca, s);
     });
-    bool have_r2 = m->l2_0.fused_next;   // the reduced map of the next block already exists
+    bool have_r2 = m->w.l2_0.fused_next;   // the reduced map of the next block already exists
     rd2 ^= have_r2 ? 1 : 0;
     m->set_stage("level2_0", m->bb[0], 64);
     int cur2 = 0;
     for (int i = 0; i < m->p; ++i) {
         const int nxt = cur2 == 1 ? 2 : 1;
         const bool last = i == m->p - 1;
-        const bool fuse_next = m->l2[i].fused_next;
+        const bool fuse_next = m->w.l2[i].fused_next;
         if (!have_r2)
             L.run(K_L2_C1, px2 * (64 * 12 * 2), [&] {
-                return launch_l2_c1(m, conv_args(m->bb[cur2], wb + m->l2[i].c1, m->r2[rd2], nullptr, n), s);
+                return launch_l2_c1(m, conv_args(m->bb[cur2], wb + m->w.l2[i].c1, m->r2[rd2], nullptr, n), s);
             });
         L.run(K_L2_ESP, px2 * (12 * 9 * 64 * 2) + (fuse_next ? px2 * (64 * 12 * 2) : 0), [&] {
-            const ConvArgs ca = conv_args(m->r2[rd2], wb + m->l2[i].br, m->bb[nxt], &m->bb[cur2], n);
+            const ConvArgs ca = conv_args(m->r2[rd2], wb + m->w.l2[i].br, m->bb[nxt], &m->bb[cur2], n);
             if (last)
                 return launch_l2_esp_last(m, plan.l2_esp_last, with_dual(ca, 0), s);
             return launch_l2_esp_fused(m, plan.l2_esp_fused, fuse_next ? with_fused(ca, m->r2[rd2 ^ 1], 12) : ca, s);
@@ -721,7 +495,7 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
     if (plan.cat_b2 == form::cat_b2::KERNEL) {
         L.run(K_CAT_B2, 0, [&] {
             hipLaunchKernelGGL(cat_b2_kernel, dim3(blocks_for((long long)n * 131 * H2 * W2)), dim3(256), 0, s, view(m->bb[cur2]),
-                               view(m->bb[0]), view(m->inp2), wb + m->b2, view(m->a1), n);
+                               view(m->bb[0]), view(m->inp2), wb + m->w.b2, view(m->a1), n);
             return GS_OK;
         });
     }
@@ -730,8 +504,8 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
     // ---- level 3 (Model.py:361-366)
     int rd3 = 0;
     L.run(K_L3_C1S, px3 * (131 * 9 * 25 * 2) + (plan.l3c_in_reduce ? px2 * (131 * m->classes * 2) : 0), [&] {
-        GS_DIAG_TRY(diag_reduce_s2(m, 3, conv_args(m->a1, wb + m->l3_0.c1, m->r3[0], nullptr, n), s, dst_));
-        ConvArgs ca = conv_args(m->a1, wb + m->l3_0.c1, m->r3[0], nullptr, n);
+        GS_DIAG_TRY(diag_reduce_s2(m, 3, conv_args(m->a1, wb + m->w.l3_0.c1, m->r3[0], nullptr, n), s, dst_));
+        ConvArgs ca = conv_args(m->a1, wb + m->w.l3_0.c1, m->r3[0], nullptr, n);
         if (lazy_b2) {   // planes 64..127 of output1_cat hold output1_0 RAW: b2 is applied to the B operands on load
             ca.bnl_s0 = 64 / 2;      // k-groups of two channels
             ca.bnl_s1 = 128 / 2;
@@ -748,24 +522,24 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
     });
     if (plan.l3c_in_reduce)
         m->set_stage("level3_C", m->l3c, m->classes);
-    L.run(K_L3_DOWN, px3 * (25 * 9 * 128 * 2) + (m->l3_0.fused_next ? px3 * (128 * 25 * 2) : 0), [&] {
-        const ConvArgs ca = conv_args(m->r3[rd3], wb + m->l3_0.br, m->cc[0], nullptr, n);
-        return launch_l3_down(m, plan.l3_down, m->l3_0.fused_next ? with_fused(ca, m->r3[rd3 ^ 1], 25) : ca, s);
+    L.run(K_L3_DOWN, px3 * (25 * 9 * 128 * 2) + (m->w.l3_0.fused_next ? px3 * (128 * 25 * 2) : 0), [&] {
+        const ConvArgs ca = conv_args(m->r3[rd3], wb + m->w.l3_0.br, m->cc[0], nullptr, n);
+        return launch_l3_down(m, plan.l3_down, m->w.l3_0.fused_next ? with_fused(ca, m->r3[rd3 ^ 1], 25) : ca, s);
     });
-    bool have_r3 = m->l3_0.fused_next;
+    bool have_r3 = m->w.l3_0.fused_next;
     m->set_stage("level3_reduce", m->r3[rd3], 25);      // (debug: valid until the second ESP block overwrites the map)
     rd3 ^= have_r3 ? 1 : 0;
     m->set_stage("level3_0", m->cc[0], 128);
     int cur3 = 0;
     for (int i = 0; i < m->q; ++i) {
         const int nxt = cur3 == 1 ? 2 : 1;
-        const bool fuse_next = m->l3[i].fused_next;
+        const bool fuse_next = m->w.l3[i].fused_next;
         if (!have_r3)
             L.run(K_L3_C1, px3 * (128 * 25 * 2), [&] {
-                return launch_l3_c1(m, conv_args(m->cc[cur3], wb + m->l3[i].c1, m->r3[rd3], nullptr, n), s);
+                return launch_l3_c1(m, conv_args(m->cc[cur3], wb + m->w.l3[i].c1, m->r3[rd3], nullptr, n), s);
             });
         L.run(K_L3_ESP, px3 * (25 * 9 * 128 * 2) + (fuse_next ? px3 * (128 * 25 * 2) : 0), [&] {
-            const ConvArgs ca = conv_args(m->r3[rd3], wb + m->l3[i].br, m->cc[nxt], &m->cc[cur3], n);
+            const ConvArgs ca = conv_args(m->r3[rd3], wb + m->w.l3[i].br, m->cc[nxt], &m->cc[cur3], n);
             GS_DIAG_TRY(diag_l3_esp(m, ca, i, s, dst_));
             if (fuse_next)
                 return launch_l3_esp_fused(m, plan.l3_esp_fused, with_fused(ca, m->r3[rd3 ^ 1], 25), i, s);
@@ -796,9 +570,9 @@ static gs_status decode(Model *m, Launcher &L, const ForwardPlan &plan, const Fo
         Dec1Args a{};
         a.c0 = view(m->cc[0]);
         a.clast = view(m->cc[enc.last]);
-        a.b3w = wb + m->b3;
-        a.br = m->encoder_only ? nullptr : wb + m->br;
-        a.wup = m->encoder_only ? nullptr : wb + m->wup3;
+        a.b3w = wb + m->w.b3;
+        a.br = m->encoder_only ? nullptr : wb + m->w.br;
+        a.wup = m->encoder_only ? nullptr : wb + m->w.wup3;
         a.out = view(m->o2c);
         a.enc_logits = enc_logits;
         a.N = n;
@@ -830,7 +604,7 @@ static gs_status decode(Model *m, Launcher &L, const ForwardPlan &plan, const Fo
     L.run(K_DEC2, plan.l3c_in_reduce ? 0 : px2 * (131 * ncls * 2), [&] {
         Dec2Args a{};
         a.o2c = view(m->o2c);
-        a.br = wb + m->cbr0;
+        a.br = wb + m->w.cbr0;
         a.t = view(m->tt);
         a.N = n;
         a.classes = ncls;
@@ -843,10 +617,10 @@ static gs_status decode(Model *m, Launcher &L, const ForwardPlan &plan, const Fo
         }
         a.a1 = view(m->a1);
         a.raw = view(m->bb[0]);
-        a.b2 = wb + m->b2;
+        a.b2 = wb + m->w.b2;
         a.raw_c0 = 64;
         a.raw_cn = enc.lazy_b2 ? 64 : 0;
-        a.w3c = wb + m->w3c;
+        a.w3c = wb + m->w.w3c;
         hipLaunchKernelGGL(dec2_kernel<CLS>, dim3((unsigned)(((long long)n * H2 * W2 + 63) / 64)), dim3(256), 0, s, a);   // 64 pixels x 4 channel quarters
         return GS_OK;
     });
@@ -857,13 +631,13 @@ static gs_status decode(Model *m, Launcher &L, const ForwardPlan &plan, const Fo
         // many classes: the 3x3 over 2 * CLS planes is 7 200 FMAs per pixel at twenty classes -- on the matrix cores (a plain
         // conv_mfma launch, BN + PReLU in its epilogue), the deconvolution + BR as a second, small kernel
         L.run(K_DEC3, px2 * (2 * ncls * 9 * ncls * 2), [&] {
-            return launch_dec3<CLS>(m, plan.dec3, conv_args(m->tt, wb + m->wcc_mfma, m->t3, nullptr, n), s);
+            return launch_dec3<CLS>(m, plan.dec3, conv_args(m->tt, wb + m->w.wcc_mfma, m->t3, nullptr, n), s);
         });
         L.run(K_DEC3, px2 * (ncls * ncls * 4 * 2), [&] {
             Dec3Args a{};
             a.t = view(m->t3);
-            a.wup = wb + m->wup2;
-            a.bnu = wb + m->bnu2;
+            a.wup = wb + m->w.wup2;
+            a.bnu = wb + m->w.bnu2;
             a.e = view(m->ee);
             a.N = n;
             a.classes = ncls;
@@ -874,10 +648,10 @@ static gs_status decode(Model *m, Launcher &L, const ForwardPlan &plan, const Fo
         L.run(K_DEC3, px2 * (2 * ncls * 9 * ncls * 2) + px2 * (ncls * ncls * 4 * 2), [&] {
             Dec3Args a{};
             a.t = view(m->tt);
-            a.wc = wb + m->wcc;
-            a.bnc = wb + m->bncc;
-            a.wup = wb + m->wup2;
-            a.bnu = wb + m->bnu2;
+            a.wc = wb + m->w.wcc;
+            a.bnc = wb + m->w.bncc;
+            a.wup = wb + m->w.wup2;
+            a.bnu = wb + m->w.bnu2;
             a.e = view(m->ee);
             a.N = n;
             a.classes = ncls;
@@ -896,7 +670,7 @@ static gs_status decode(Model *m, Launcher &L, const ForwardPlan &plan, const Fo
             a.in_pitch = m->a0c.pitch;
             a.in_off = m->a0c.off;
             a.in_img_bytes = (unsigned)(m->a0c.sn * sizeof(float));
-            a.wpack = wb + m->wtail;
+            a.wpack = wb + m->w.wtail;
             a.logits = r.logits;
             a.mask = r.mask;
             a.hist = ens_finishes((int)r.role) ? r.hist : nullptr;   // only the last member of an ensemble counts
@@ -922,13 +696,13 @@ static gs_status decode(Model *m, Launcher &L, const ForwardPlan &plan, const Fo
         // buffer as a plain conv_mfma launch (MFMA rows = the padded output channels, BN + PReLU in its epilogue), then the
         // classifier deconvolution + argmax + counts (+ the ensemble's softmax accumulation) as a second kernel.
         L.run(K_DEC_CONV, px1 * ((19 + ncls) * 9 * ncls * 2), [&] {
-            return launch_dec_conv<CLS>(m, plan.dec_conv, conv_args(m->a0c, wb + m->wconv, m->ff, nullptr, n), s);
+            return launch_dec_conv<CLS>(m, plan.dec_conv, conv_args(m->a0c, wb + m->w.wconv, m->ff, nullptr, n), s);
         });
         m->set_stage("conv", m->ff, ncls);
         L.run(K_DEC4, px1 * (ncls * ncls * 4 * 2), [&] {
             Dec4Args a{};
             a.f = view(m->ff);
-            a.wcl = wb + m->wclassifier;
+            a.wcl = wb + m->w.wclassifier;
             a.logits = r.logits;
             a.mask = r.mask;
             a.hist = r.hist;
@@ -1122,17 +896,26 @@ gs_status run_ensemble(gs_espnet *const *models, int n_models, int lane, const F
 
 extern "C" {
 
-gs_status gs_espnet_create(const float *blob, const gs_layer_desc *table, int n_layers, int classes, int p, int q,
-                           int encoder_only, gs_espnet **out)
+// what gs_espnet_create and gs_espnet_pack_weights (`fn`) ask of their common arguments
+static gs_status check_model_args(const char *fn, const float *blob, const gs_layer_desc *table, int n_layers, int classes, int p, int q)
 {
-    GS_REQUIRE(blob && table && out && n_layers > 0, "gs_espnet_create: null argument");
-    GS_REQUIRE(p >= 0 && q >= 0, "gs_espnet_create: p and q must be non-negative");
+    GS_REQUIRE(blob && table && n_layers > 0, "%s: null argument", fn);
+    GS_REQUIRE(p >= 0 && q >= 0, "%s: p and q must be non-negative", fn);
     // Model.py:311,246: `classes` is free (20 by default).  The decoder kernels exist for 2..20 (padded to 4, 5, 8, 12, 16, 20
     // planes: Model::cp); class maps are uint8 and a lane's per-class counters are sized for at most 20.
     if (classes < 2 || classes > 20) {
-        set_error("gs_espnet_create: classes must be 2..20 (got %d)", classes);
+        set_error("%s: classes must be 2..20 (got %d)", fn, classes);
         return GS_ERR_UNSUPPORTED;
     }
+    return GS_OK;
+}
+
+gs_status gs_espnet_create(const float *blob, const gs_layer_desc *table, int n_layers, int classes, int p, int q,
+                           int encoder_only, gs_espnet **out)
+{
+    GS_REQUIRE(out, "gs_espnet_create: null argument");
+    gs_status st = check_model_args("gs_espnet_create", blob, table, n_layers, classes, p, q);
+    if (st != GS_OK) return st;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         set_error("gs_espnet_create: no HIP device visible");
@@ -1157,193 +940,36 @@ gs_status gs_espnet_create(const float *blob, const gs_layer_desc *table, int n_
     if (const char *v = std::getenv("GS_VARIANT"))
         m.variant = std::atoi(v);
 #endif
-
-    WeightTable t;
-    t.blob = blob;
-    for (int i = 0; i < n_layers; ++i)
-        t.by_name[std::string(table[i].name)] = &table[i];
-    const std::string e = m.encoder_only ? "" : "encoder.";
-    const int c = classes;
-    BlobBuilder bb;
-    std::vector<float> tmp(3 * 256);
-
-    const float *w;
-    if (!(w = t.get(e + "level1.conv.weight", {16, 3, 3, 3}))) return GS_ERR_INVALID;
-    m.w1 = bb.push(w, 432);
-    if (!fold_bn(t, e + "level1.bn", e + "level1.act", 16, tmp.data())) return GS_ERR_INVALID;
-    m.bn1 = bb.push(tmp.data(), 48);
-    if (!fold_bn(t, e + "b1.bn", e + "b1.act", 19, tmp.data())) return GS_ERR_INVALID;
-    m.b1 = bb.push(tmp.data(), 57);
-    std::memcpy(m.stem_params, bb.data.data() + m.w1, sizeof(float) * 432);
-    std::memcpy(m.stem_params + 432, bb.data.data() + m.bn1, sizeof(float) * 48);
-    std::memcpy(m.stem_params + 480, bb.data.data() + m.b1, sizeof(float) * 57);
-    std::vector<float> b2f(3 * 131);
-    if (!fold_bn(t, e + "b2.bn", e + "b2.act", 131, b2f.data())) return GS_ERR_INVALID;
-    m.b2 = bb.push(b2f.data(), 393);
-    auto next2 = [&](int i) { return l2_c1_fused(i, p) ? e + "level2." + std::to_string(i) : std::string(); };
-    auto next3 = [&](int i) { return l3_c1_fused(i, q) ? e + "level3." + std::to_string(i) : std::string(); };
-    // (lazy b2: the down-sampler has no second store, so its image carries no second BN section)
-    if (!pack_block(t, bb, e + "level2_0", true, 2, m.l2_0, nullptr, 0, 0, next2(0))) return GS_ERR_INVALID;
-    m.l2.resize(p);
-    for (int i = 0; i < p; ++i)
-        if (!pack_block(t, bb, e + "level2." + std::to_string(i), false, 2, m.l2[i], i == p - 1 ? b2f.data() : nullptr, 0, 131, next2(i + 1)))
-            return GS_ERR_INVALID;
-    // (the reduce of a five-class decoder model also computes level3_C: forward_plan.h, l3c_side_sums)
-    const float *w3c_side = nullptr;
-    if (!m.encoder_only && l3c_side_sums(m.cp) && !(w3c_side = t.get("level3_C.conv.weight", {classes, 131, 1, 1}))) return GS_ERR_INVALID;
-    if (!pack_block(t, bb, e + "level3_0", true, 3, m.l3_0, nullptr, 0, 0, next3(0), b2f.data(), 64, 64, 131, w3c_side, classes))
-        return GS_ERR_INVALID;
-    m.l3.resize(q);
-    for (int i = 0; i < q; ++i)
-        if (!pack_block(t, bb, e + "level3." + std::to_string(i), false, 3, m.l3[i], nullptr, 0, 0, next3(i + 1))) return GS_ERR_INVALID;
-    // ---- decoder: every piece is packed for cp class planes, zero beyond the model's c (espnet_kernels.h, "CLASS COUNTS")
-    const int cp = m.cp;
-    // [rows][cols][2][2] deconvolution weights -> [cp][cp][2][2]
-    auto pad_deconv = [&](const float *src) {
-        std::vector<float> o((size_t)cp * cp * 4, 0.0f);
-        for (int i = 0; i < c; ++i)
-            for (int o2 = 0; o2 < c; ++o2)
-                for (int k = 0; k < 4; ++k)
-                    o[((size_t)i * cp + o2) * 4 + k] = src[((size_t)i * c + o2) * 4 + k];
-        return o;
-    };
-    // folded BN (+ PReLU slope) [rows][C] -> [rows][cpn] through `map` (padded index -> source channel or -1): padding planes
-    // get scale 0, shift 0, slope 1, so they stay exact zeros
-    auto pad_bn = [&](const float *src, int C, int rows, int cpn, const std::function<int(int)> &map) {
-        std::vector<float> o((size_t)rows * cpn, 0.0f);
-        for (int k = 0; k < cpn; ++k) {
-            const int sc = map(k);
-            for (int r = 0; r < rows; ++r)
-                o[(size_t)r * cpn + k] = sc >= 0 ? src[(size_t)r * C + sc] : (r == 2 ? 1.0f : 0.0f);
-        }
-        return o;
-    };
-    auto ident = [&](int k) { return k < c ? k : -1; };
-    if (!fold_bn(t, e + "b3.bn", e + "b3.act", 256, tmp.data())) return GS_ERR_INVALID;
-    if (!(w = t.get(e + "classifier.conv.weight", {c, 256, 1, 1}))) return GS_ERR_INVALID;
-    {
-        const int rec = (3 + cp + 3) / 4 * 4;   // dec1_record<cp>
-        std::vector<float> pk((size_t)256 * rec, 0.0f);   // [channel][scale, shift, alpha, w0..]
-        for (int ch = 0; ch < 256; ++ch) {
-            for (int j = 0; j < 3; ++j) pk[(size_t)ch * rec + j] = tmp[j * 256 + ch];
-            for (int k = 0; k < c; ++k) pk[(size_t)ch * rec + 3 + k] = w[k * 256 + ch];
-        }
-        m.b3 = bb.push(pk.data(), pk.size());
-        m.wcls = m.b3;
-    }
-    if (!m.encoder_only) {
-        if (!fold_bn(t, "br", "", c, tmp.data(), false)) return GS_ERR_INVALID;
-        {
-            const std::vector<float> v = pad_bn(tmp.data(), c, 2, cp, ident);
-            m.br = bb.push(v.data(), v.size());
-        }
-        if (!(w = t.get("up_l3.0.weight", {c, c, 2, 2}))) return GS_ERR_INVALID;
-        {
-            const std::vector<float> v = pad_deconv(w);
-            m.wup3 = bb.push(v.data(), v.size());
-        }
-        if (!(w = t.get("level3_C.conv.weight", {c, 131, 1, 1}))) return GS_ERR_INVALID;
-        {
-            const int rec = (cp + 3) / 4 * 4;   // dec2_record<cp>
-            std::vector<float> pk((size_t)131 * rec, 0.0f);
-            for (int ch = 0; ch < 131; ++ch)
-                for (int k = 0; k < c; ++k) pk[(size_t)ch * rec + k] = w[k * 131 + ch];
-            m.w3c = bb.push(pk.data(), pk.size());
-        }
-        // combine_l2_l3: cat([level3_C out, up_l3 out]) (Model.py:373) lives in 2 * cp planes, each half padded on its own
-        auto cat2 = [&](int k) { return k < cp ? (k < c ? k : -1) : (k - cp < c ? c + k - cp : -1); };
-        if (!fold_bn(t, "combine_l2_l3.0.bn", "combine_l2_l3.0.act", 2 * c, tmp.data())) return GS_ERR_INVALID;
-        {
-            const std::vector<float> v = pad_bn(tmp.data(), 2 * c, 3, 2 * cp, cat2);
-            m.cbr0 = bb.push(v.data(), v.size());
-        }
-        if (!(w = t.get("combine_l2_l3.1.conv.weight", {c, 2 * c, 3, 3}))) return GS_ERR_INVALID;
-        {
-            std::vector<float> v((size_t)cp * 2 * cp * 9, 0.0f);
-            for (int k = 0; k < c; ++k)
-                for (int ch = 0; ch < 2 * cp; ++ch) {
-                    const int sc = cat2(ch);
-                    if (sc < 0) continue;
-                    for (int tap = 0; tap < 9; ++tap)   // (five classes: the reference's own order; else [plane][tap][class], see Dec3Args)
-                        v[cp == 5 ? ((size_t)k * 2 * cp + ch) * 9 + tap : ((size_t)ch * 9 + tap) * cp + k] = w[((size_t)k * 2 * c + sc) * 9 + tap];
-                }
-            m.wcc = bb.push(v.data(), v.size());
-        }
-        if (dec3_on_mfma(cp)) {   // the same convolution as a conv_mfma image: [tap][2 * cp planes][cp rows], then its folded BN + PReLU
-            m.wcc_mfma = bb.reserve(conv_wfloats(2 * cp, 9, 1, cp, cp, true));
-            float *dst = bb.data.data() + m.wcc_mfma;
-            for (int tap = 0; tap < 9; ++tap)
-                for (int ch = 0; ch < 2 * cp; ++ch) {
-                    const int sc = cat2(ch);
-                    if (sc < 0) continue;
-                    for (int k = 0; k < c; ++k)
-                        dst[((size_t)tap * 2 * cp + ch) * cp + k] = w[((size_t)k * 2 * c + sc) * 9 + tap];
-                }
-        }
-        if (!fold_bn(t, "combine_l2_l3.1.bn", "combine_l2_l3.1.act", c, tmp.data())) return GS_ERR_INVALID;
-        {
-            const std::vector<float> v = pad_bn(tmp.data(), c, 3, cp, ident);
-            m.bncc = bb.push(v.data(), v.size());
-            if (m.wcc_mfma >= 0)
-                std::memcpy(bb.data.data() + m.wcc_mfma + (size_t)9 * 2 * cp * cp, v.data(), sizeof(float) * 3 * cp);
-        }
-        if (!(w = t.get("up_l2.0.weight", {c, c, 2, 2}))) return GS_ERR_INVALID;
-        {
-            const std::vector<float> v = pad_deconv(w);
-            m.wup2 = bb.push(v.data(), v.size());
-        }
-        if (!fold_bn(t, "up_l2.1.bn", "up_l2.1.act", c, tmp.data())) return GS_ERR_INVALID;
-        {
-            const std::vector<float> v = pad_bn(tmp.data(), c, 3, cp, ident);
-            m.bnu2 = bb.push(v.data(), v.size());
-        }
-        if (!(w = t.get("conv.conv.weight", {c, 19 + c, 3, 3}))) return GS_ERR_INVALID;
-        // plane `pl` of the concat buffer [comb_l2_l3 (cp planes) | output0_cat (19) | zero planes] <-> channel of the reference's
-        // torch.cat([comb_l2_l3, output0_cat]) (Model.py:375)
-        auto cat_ch = [&](int pl) { return pl < cp ? (pl < c ? pl : -1) : (pl - cp < 19 ? c + pl - cp : -1); };
-        if (!fold_bn(t, "conv.bn", "conv.act", c, tmp.data())) return GS_ERR_INVALID;
-        const std::vector<float> bn_conv = pad_bn(tmp.data(), c, 3, cp, ident);
-        if (!dec_tail_fused(cp)) {   // (five classes: dec_tail reads m.wtail, packed below)
-            // the generic tail's conv_mfma image [tap][CINP planes][cp rows] + BN: CINP = 19 + cp rounded up to the k-step
-            const int cinp = (19 + cp + 3) / 4 * 4;
-            m.wconv = bb.reserve(conv_wfloats(cinp, 9, 1, cp, cp, true));
-            float *dst = bb.data.data() + m.wconv;
-            for (int tap = 0; tap < 9; ++tap)
-                for (int pl = 0; pl < cinp; ++pl) {
-                    const int wch = cat_ch(pl);
-                    if (wch < 0) continue;
-                    for (int co = 0; co < c; ++co)
-                        dst[((size_t)tap * cinp + pl) * cp + co] = w[((size_t)co * (19 + c) + wch) * 9 + tap];
-                }
-            std::memcpy(dst + (size_t)9 * cinp * cp, bn_conv.data(), sizeof(float) * 3 * cp);
-        }
-        if (!(w = t.get("classifier.weight", {c, c, 2, 2}))) return GS_ERR_INVALID;
-        {
-            const std::vector<float> v = pad_deconv(w);
-            m.wclassifier = bb.push(v.data(), v.size());
-        }
-        if (dec_tail_fused(cp)) {
-            // dec_tail image: A operands [ty][plane group][lane] (lane = k-group * 16 + MFMA row, row = tx*c + o),
-            // then BN scale / shift / alpha of conv, then classifier.weight
-            const float *wc = t.get("conv.conv.weight", {c, 19 + c, 3, 3});
-            if (!wc) return GS_ERR_INVALID;
-            m.wtail = bb.reserve(DT_PACK_FLOATS);
-            float *dt = bb.data.data() + m.wtail;
-            for (int ty = 0; ty < 3; ++ty)
-                for (int g = 0; g < 6; ++g)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int rho = lane & 15, ch = 4 * g + (lane >> 4);
-                        dt[(ty * 6 + g) * 64 + lane] =
-                            rho < 3 * c ? wc[(((size_t)(rho % c) * (19 + c) + ch) * 3 + ty) * 3 + rho / c] : 0.0f;
-                    }
-            std::memcpy(dt + DT_A_FLOATS, bn_conv.data(), sizeof(float) * 3 * c);
-            std::memcpy(dt + DT_A_FLOATS + 16, w, sizeof(float) * c * c * 4);
-        }
-    }
-    bb.reserve(512);   // tail guard: LDS-DMA staging reads whole 1-KiB pieces
-    GS_HIP(hipMalloc(reinterpret_cast<void **>(&m.dblob), bb.data.size() * sizeof(float)));
-    GS_HIP(hipMemcpy(m.dblob, bb.data.data(), bb.data.size() * sizeof(float), hipMemcpyHostToDevice));
+    EspnetWeights packed;   // every layout of the weights: espnet_weights.h
+    st = pack_espnet_weights(blob, table, n_layers, classes, p, q, m.encoder_only, packed);
+    if (st != GS_OK) return st;
+    m.w = packed;
+    GS_HIP(hipMalloc(reinterpret_cast<void **>(&m.dblob), packed.blob.size() * sizeof(float)));
+    GS_HIP(hipMemcpy(m.dblob, packed.blob.data(), packed.blob.size() * sizeof(float), hipMemcpyHostToDevice));
     *out = h.release();
+    return GS_OK;
+}
+
+gs_status gs_espnet_pack_weights(const float *blob, const gs_layer_desc *table, int n_layers, int classes, int p, int q,
+                                 int encoder_only, float *out, size_t cap, size_t *n_floats, gs_weight_piece *pieces, int piece_cap,
+                                 int *n_pieces)
+{
+    GS_REQUIRE(n_floats, "gs_espnet_pack_weights: null argument");
+    gs_status st = check_model_args("gs_espnet_pack_weights", blob, table, n_layers, classes, p, q);
+    if (st != GS_OK) return st;
+    EspnetWeights packed;
+    st = pack_espnet_weights(blob, table, n_layers, classes, p, q, encoder_only != 0, packed);
+    if (st != GS_OK) return st;
+    *n_floats = packed.blob.size();
+    if (n_pieces) *n_pieces = (int)packed.pieces.size();
+    if (out) {
+        GS_REQUIRE(cap >= packed.blob.size(), "gs_espnet_pack_weights: %zu floats needed, room for %zu", packed.blob.size(), cap);
+        std::memcpy(out, packed.blob.data(), packed.blob.size() * sizeof(float));
+    }
+    if (pieces) {
+        GS_REQUIRE(piece_cap >= (int)packed.pieces.size(), "gs_espnet_pack_weights: %zu pieces, room for %d", packed.pieces.size(), piece_cap);
+        std::memcpy(pieces, packed.pieces.data(), packed.pieces.size() * sizeof(gs_weight_piece));
+    }
     return GS_OK;
 }
 
@@ -1389,6 +1015,22 @@ gs_status gs_espnet_reserve(gs_espnet *h, int n, int height, int width)
         if (st != GS_OK) return st;
     }
     return GS_OK;
+}
+
+gs_status gs_espnet_workspace_plan(int n, int height, int width, int p, int q, int classes, int encoder_only, size_t *bytes)
+{
+    GS_REQUIRE(bytes, "gs_espnet_workspace_plan: null argument");
+    gs_status st = check_shape(n, height, width);
+    if (st != GS_OK) return st;
+    GS_REQUIRE(p >= 0 && q >= 0, "gs_espnet_workspace_plan: p and q must be non-negative");
+    if (classes < 2 || classes > 20) {
+        set_error("gs_espnet_workspace_plan: classes must be 2..20 (got %d)", classes);
+        return GS_ERR_UNSUPPORTED;
+    }
+    WorkspacePlan plan;
+    st = plan_workspace(n, height, width, padded_classes(classes), p, encoder_only != 0, plan);
+    *bytes = plan.bytes;
+    return st;
 }
 
 gs_status gs_espnet_set_lanes(gs_espnet *h, int n_lanes)
@@ -1466,7 +1108,7 @@ gs_status gs_espnet_read_stage(gs_espnet *h, const char *stage, int image, float
     GS_HIP(hipMalloc(reinterpret_cast<void **>(&tmp), count * sizeof(float)));
     hipLaunchKernelGGL(unpad_kernel, dim3(blocks_for((long long)count)), dim3(256), 0, 0, view(a), image, C, tmp);
     if (m.b2_lazy && std::string(stage) == "b2")   // planes 64..127 are kept raw in the workspace: normalise the copy
-        hipLaunchKernelGGL(b2_apply_kernel, dim3(blocks_for((long long)64 * a.H * a.W)), dim3(256), 0, 0, tmp, m.dblob + m.b2, a.H * a.W, 64, 64);
+        hipLaunchKernelGGL(b2_apply_kernel, dim3(blocks_for((long long)64 * a.H * a.W)), dim3(256), 0, 0, tmp, m.dblob + m.w.b2, a.H * a.W, 64, 64);
     hipError_t e = hipMemcpy(dst, tmp, count * sizeof(float), hipMemcpyDeviceToHost);
     hipFree(tmp);
     GS_HIP(e);
@@ -1501,7 +1143,7 @@ gs_status gs_espnet_block_forward(gs_espnet *h, int kind, int level, int index, 
     auto body = [&]() -> gs_status {
         GS_HIP(hipMemcpy(tmp, in, nin * sizeof(float), hipMemcpyHostToDevice));
         hipLaunchKernelGGL(pad_kernel, dim3(blocks_for((long long)nin)), dim3(256), 0, s, view(src), 0, cin, tmp);
-        const PackedConv &pc = kind == 1 ? (level == 2 ? m.l2_0 : m.l3_0) : (level == 2 ? m.l2[index] : m.l3[index]);
+        const PackedConv &pc = kind == 1 ? (level == 2 ? m.w.l2_0 : m.w.l3_0) : (level == 2 ? m.w.l2[index] : m.w.l3[index]);
         // the block's reduce, then its branches in the unfused whole-row form its output width allows (forward_plan.h)
         const ConvArgs rca = conv_args(src, wb + pc.c1, red, nullptr, 1);
         const ConvArgs bca = conv_args(red, wb + pc.br, dst, kind == 1 ? nullptr : &src, 1);

@@ -51,21 +51,8 @@ constexpr int L2SP = 4;   // pixels per lane of the level-2 branch kernels (the 
 #define CFG_L3_C1S_BNL_P1 32, 8,  132, 9,   2,     1,   25,   25,   1, 6
 
 // Build-time choices, each made by measurement (profiles/README.md); the defaults are what ships.
-// F_FUSE1X1 (the next block's 1x1 reduce computed in a block's epilogue), measured at batch 32 (profiles/README.md):
-//   level 2: down-sampler 0.223 -> 0.242 ms, ESP block 0.189 -> 0.21 ms (three waves per SIMD instead of four), against
-//            0.063 ms per separate 1x1 launch: -0.084 ms per step.  On.
-//   level 3: down-sampler (no residual: the second accumulator set fits beside four pixels per lane) 0.159 -> 0.175 ms
-//            against 0.032 ms for the 1x1 launch: on.  ESP blocks: beside the residual registers the second accumulator
-//            set only fits at two pixels per lane, and that form takes 0.1995 ms = exactly branch kernel + 1x1 kernel
-//            (0.167 + 0.032); with the residual through a half-slot register ring it fit at four pixels per lane (24
-//            registers spilled) and took 0.190-0.197 ms.  Shipped since: two pixels per lane (CFG_L3_BR_P2R, no spill):
-//            0.183 ms, because half-row tasks halve the images an XCD has in flight and the reduced maps stay in its L2.
-#ifndef CFG_FUSE_L3
-#define CFG_FUSE_L3 2   // 0 off, 1 down-sampler only, 2 every block
-#endif
-#ifndef CFG_FUSE_L2
-#define CFG_FUSE_L2 1
-#endif
+// F_FUSE1X1 (the next block's 1x1 reduce computed in a block's epilogue): CFG_FUSE_L2 / CFG_FUSE_L3 and what was measured are in
+// espnet_facts.h, because the weight packer lays the fused tables out by them.
 // The last (unfused) level-3 block in the half-row task shape of the fused ones (CFG_L3_BR_P2R + F_SKIP_PAD) instead of the
 // whole-row four-pixel form: beyond-L2 fetch of that launch 528 -> 235 MB, step 2.853 -> 2.835 ms (profiles/README.md, round 3).
 #ifndef CFG_L3_LAST_P2

@@ -13,22 +13,8 @@ namespace gs {
 // pixels per lane of a configuration: the 9th element of a CFG_* tuple
 constexpr int cfg_pixels(int, int, int, int, int, int, int, int, int p, int) { return p; }
 
-// ---- facts of the model that the packing (gs_espnet_create), the workspace and the plan share
-// the padded class count the decoder kernels are instantiated for (Model::cp)
-constexpr int padded_classes(int classes) { return classes == 5 ? 5 : (classes + 3) / 4 * 4; }
-// Lazy b2 (espnet_config.h): output1_0 is stored raw and its consumers apply b2 on load, whenever there is an ESP block
-constexpr bool b2_is_lazy(int p) { return p > 0; }
-// the 1x1 reduce of ESP block i is computed in the epilogue of the block before it (F_FUSE1X1; block 0: of the down-sampler)
-constexpr bool l2_c1_fused(int i, int p) { return CFG_FUSE_L2 && i < p; }
-constexpr bool l3_c1_fused(int i, int q) { return (CFG_FUSE_L3 == 2 || (CFG_FUSE_L3 == 1 && i == 0)) && i < q; }
-// the decoder by padded class count: combine_l2_l3.1's 3x3 on the matrix cores from twelve planes on (else dec3_kernel),
-// the fused tail for the five-class networks (else a conv_mfma launch + dec4_kernel); MFMA rows 16 up to sixteen planes
-constexpr bool dec3_on_mfma(int cp) { return cp >= 12; }
-// level3_C (the decoder's 1x1 over output1_cat) is computed by the level-3 stride-2 reduce, which has every value of that map
-// in a register (F_SIDE1X1), and dec2 reads its `cp` planes instead of the 131.  Five class planes only: at four pixel runs
-// per lane the side sums take 2 * cp * 4 registers, and eight planes do not fit beside the reduce's 196-207 without spilling.
-constexpr bool l3c_side_sums(int cp) { return cp == 5; }
-constexpr bool dec_tail_fused(int cp) { return cp == 5; }
+// ---- the facts of the model that the packing, the workspace and the plan share (padded_classes, b2_is_lazy, l2_c1_fused,
+// l3_c1_fused, dec3_on_mfma, l3c_side_sums, dec_tail_fused) are in espnet_facts.h; the MFMA shape of the decoder's 3x3 launches:
 constexpr int dec_mt(int cp) { return cp <= 16 ? 16 : 32; }
 constexpr int dec_pixels(int cp) { return cp <= 16 ? 8 : 4; }
 

@@ -330,6 +330,28 @@ def plan_flags(n, height, width, p, q, classes, num_cus, encoder_only=False):
     return {"lazy_b2": bool(flags.value & _lib.GS_PLAN_LAZY_B2), "l3c_in_reduce": bool(flags.value & _lib.GS_PLAN_L3C_IN_REDUCE)}
 
 
+def pack_weights(state_dict, classes=5, p=2, q=8, encoder_only=False):
+    """(blob, pieces): the fp32 weight blob gs_espnet_create uploads for this model and {piece name: (float offset, floats)} of
+    its pieces in order (gs_espnet_pack_weights, include/glomseg_plan.h).  Host-only: needs no GPU."""
+    lib = _lib.load()
+    src, table = pack_state_dict(state_dict)
+    head = (src.ctypes.data_as(ctypes.c_void_p), table, len(table), classes, p, q, int(bool(encoder_only)))
+    n, n_pieces = ctypes.c_size_t(), ctypes.c_int()
+    _lib.check(lib.gs_espnet_pack_weights(*head, None, 0, ctypes.byref(n), None, 0, ctypes.byref(n_pieces)))
+    blob, pieces = np.empty(n.value, dtype=np.float32), (_lib.WeightPiece * n_pieces.value)()
+    _lib.check(lib.gs_espnet_pack_weights(*head, blob.ctypes.data_as(ctypes.c_void_p), blob.size, ctypes.byref(n), pieces, len(pieces),
+                                          ctypes.byref(n_pieces)))
+    return blob, {pc.name.decode(): (pc.offset, pc.floats) for pc in pieces}
+
+
+def workspace_bytes(n, height, width, p, q, classes, encoder_only=False):
+    """The bytes of activation workspace EspnetEngine.reserve(n, height, width) allocates per lane for ESPNet(classes, p, q)
+    (gs_espnet_workspace_plan); raises GlomsegError for a shape no forward takes.  Host-only: needs no GPU."""
+    b = ctypes.c_size_t()
+    _lib.check(_lib.load().gs_espnet_workspace_plan(n, height, width, p, q, classes, int(bool(encoder_only)), ctypes.byref(b)))
+    return b.value
+
+
 def crop_preprocess(crop_u8, mean, std, out_h, out_w, out=None):
     """uint8 BGR crop [h,w,3] on the GPU -> normalised, bilinearly resized fp32 [3,out_h,out_w]
     (VisualizeResults_iou.py:107-116 for a crop that is not network-sized)."""

@@ -28,7 +28,7 @@ CSRC = os.path.join(REPO, "glomeruli_segmentation_amd", "csrc")
 RANDOM_MEAN_STD = ((120.0, 130.0, 110.0), (60.0, 55.0, 70.0))
 
 # ---------------------------------------------------------------------------------------------- the plan
-# the shipped defaults of espnet_config.h the planner reads (test_dispatch_tripwire pins each one): CASES and
+# the shipped defaults of espnet_config.h (the two fusion switches: espnet_facts.h) the planner reads (test_dispatch_tripwire pins each one): CASES and
 # UNREACHABLE_AT_DEFAULTS are answers for these values
 CONFIG = {"CFG_SMALL2_WAVES": 4, "CFG_SMALL3_WAVES": 8, "CFG_L3_DOWN_P2": 1, "CFG_L3_LAST_P2": 1,
           "CFG_L2_DOWN_SKIP": 1, "CFG_FUSE_L2": 1, "CFG_FUSE_L3": 2}
@@ -92,7 +92,7 @@ def _read(name):
 def test_dispatch_tripwire():
     """CASES and UNREACHABLE_AT_DEFAULTS are answers for the shipped defaults: a changed default fails here, so that they are
     revisited with it.  Deleted switches stay deleted, and every switch left is documented."""
-    cfg = _read("espnet_config.h")
+    cfg = _read("espnet_config.h") + _read("espnet_facts.h")   # (CFG_FUSE_L2 / CFG_FUSE_L3: the weight packer reads them too)
     for name, value in CONFIG.items():
         m = re.search(r"#ifndef %s\n#define %s (\S+)" % (name, name), cfg)
         assert m and m.group(1) == str(value), name
