@@ -15,7 +15,7 @@ if os.environ.get("GLOMSEG_LIB") and os.environ.get("GLOMSEG_EXPERIMENT") == "1"
 GS_OK = 0
 GS_IN_U8_BGR_NHWC = 0
 GS_IN_F32_NCHW = 1
-ABI_VERSION = 9
+ABI_VERSION = 10
 GS_BUILD_DIAG = 1
 GS_FORM_NONE = -1
 GS_MAX_ENSEMBLE_C = 8      # most ESPNet-C members of an ensemble (include/glomseg.h)
@@ -111,6 +111,8 @@ PROTOTYPES = {
     "gs_espnet_segment_crops_host": (_I, [ctypes.POINTER(_P), _I, ctypes.POINTER(_P), ctypes.POINTER(_I), ctypes.POINTER(_I), _I, _FP, _FP,
                                      _I, _I, _I, ctypes.POINTER(_P), _P, _P, ctypes.POINTER(PasteTarget), ctypes.POINTER(_I),
                                      ctypes.POINTER(_I), ctypes.POINTER(CropOverlay)]),
+    "gs_crops_from_masks": (_I, [_P, ctypes.POINTER(CropDesc), _I, _I, _I, _I, _P, _P, ctypes.POINTER(PasteTarget), _P, _P, _I,
+                            ctypes.c_float, ctypes.c_float, _I, _P, _P]),
     "gs_plan_crop_batches": (_I, [ctypes.POINTER(_I), ctypes.POINTER(_I), _I, _I, ctypes.POINTER(_I), _I, ctypes.POINTER(_I)]),
     "gs_host_block_is_pinned": (_I, [_P, ctypes.c_size_t]),
     "gs_espnet_ensemble_forward": (_I, [ctypes.POINTER(_P), _I, _P, _I, _I, _I, _FP, _FP, _P, _P, _P]),

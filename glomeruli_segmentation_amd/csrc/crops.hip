@@ -153,7 +153,10 @@ crops_back_kernel(const CropTable t, const unsigned char *net, int net_h, int ne
 
 // Palette colouring + cv2.addWeighted of every crop of the batch (VisualizeResults_iou.py:139-146): four pixels per thread -- one
 // dword of the crop-size class map, three dwords of BGR in, three out.  The two products and their sum are rounded separately
-// (__fmul_rn / __fadd_rn: no fused multiply-add), so the bytes are those of numpy's float32 arithmetic.
+// (no fused multiply-add), so the bytes are those of numpy's float32 arithmetic.  `fp contract(off)` over plain operators is
+// what keeps them apart: __fmul_rn / __fadd_rn are inline functions whose own * and + are compiled contractible, and written
+// with them nine of the twelve sums of a thread came out as v_fmac_f32 (tests/test_crop_stage.py: the 0.3 / 0.7 and 1.3 / 0.9
+// weights tell the difference, 0.4 / 0.6 does not).
 struct OverlayArgs {
     const unsigned char *crops;   // packed BGR crops (gs_crop_desc::in_off)
     const unsigned char *maps;    // packed crop-size class maps (out_off)
@@ -166,6 +169,7 @@ struct OverlayArgs {
 
 __global__ void __launch_bounds__(256) crops_overlay_kernel(const CropTable t, const OverlayArgs a)
 {
+#pragma clang fp contract(off)
     const int i = blockIdx.y;
     const long long hw = (long long)t.d[i].h * t.d[i].w;
     const unsigned char *src = a.crops + t.d[i].in_off, *cls = a.maps + t.d[i].out_off;
@@ -195,7 +199,7 @@ __global__ void __launch_bounds__(256) crops_overlay_kernel(const CropTable t, c
                 const float pix = (float)((pw[bi >> 2] >> (8 * (bi & 3))) & 0xffu);
                 // palette rows are RGB, the image is BGR (classMap_numpy_color[...] = [b, g, r], :143)
                 const float col = c < a.n_colours ? (float)a.pal[c * 3 + (2 - ch)] : 0.0f;
-                const float v = __fadd_rn(__fmul_rn(pix, a.wa), __fmul_rn(col, a.wb));
+                const float v = pix * a.wa + col * a.wb;   // (three roundings: contraction is off in this function)
                 ow[bi >> 2] |= (unsigned)fminf(fmaxf(rintf(v), 0.0f), 255.0f) << (8 * (bi & 3));   // saturate_cast<uchar>(cvRound)
             }
         }
@@ -509,6 +513,78 @@ struct BatchScoring {
     int gt_clamp;
 };
 
+// An overlay request of after_masks: crops_overlay_kernel over the crop-size maps (packed_out) into `out`
+struct BatchOverlay {
+    const unsigned char *crops;         // packed BGR crops at in_off
+    const unsigned char *palette_rgb;   // host, n_colours rows
+    int n_colours;
+    float wa, wb;
+    unsigned char *out;                 // packed at in_off, or null (only a ground-truth overlay is wanted)
+    int clamp;                          // of the launch into `out`; the ground-truth launch takes BatchScoring::gt_clamp
+};
+
+// Everything that follows the network-resolution masks of one batch, on stream s: the resize back with the counts, the scoring,
+// the overlays (prediction and ground truth) and the paste, each with its grid.  The table is complete.  hist is added into: the
+// caller has zeroed it on the stream (crops_prep_kernel in run_batch, a fill in gs_crops_from_masks).
+static gs_status after_masks(const CropTable &tab, int n, const unsigned char *net_masks, int net_h, int net_w, int classes,
+                             unsigned char *packed_out, unsigned long long *hist, const gs_paste_target *paste,
+                             const BatchOverlay *overlay, const BatchScoring *score, hipStream_t s)
+{
+    long long max_hw = 1, max_cells = 1;
+    for (int i = 0; i < n; ++i) {
+        max_hw = std::max(max_hw, (long long)tab.d[i].h * tab.d[i].w);
+        if (paste)
+            max_cells = std::max(max_cells, (long long)(tab.d[i].w / paste->ds + 3) * (tab.d[i].h / paste->ds + 3));
+    }
+    if (packed_out || hist) {
+        long long gx = (max_hw + 8 * 1024 - 1) / (8 * 1024);   // about eight iterations per workgroup, never more than 512
+        gx = std::max(gx, (max_hw + 512 * 1024 - 1) / (512 * 1024));
+        gx = std::min(std::max(gx, 1ll), 65535ll);
+        const dim3 grid((unsigned)gx, (unsigned)n);
+        switch ((classes + 4) / 5) {
+        case 1: hipLaunchKernelGGL(crops_back_kernel<1>, grid, dim3(256), 0, s, tab, net_masks, net_h, net_w, packed_out, hist, classes); break;
+        case 2: hipLaunchKernelGGL(crops_back_kernel<2>, grid, dim3(256), 0, s, tab, net_masks, net_h, net_w, packed_out, hist, classes); break;
+        case 3: hipLaunchKernelGGL(crops_back_kernel<3>, grid, dim3(256), 0, s, tab, net_masks, net_h, net_w, packed_out, hist, classes); break;
+        default: hipLaunchKernelGGL(crops_back_kernel<4>, grid, dim3(256), 0, s, tab, net_masks, net_h, net_w, packed_out, hist, classes); break;
+        }
+        GS_HIP(hipGetLastError());
+    }
+    if (score) {   // reads the network-resolution masks only
+        const gs_status st = launch_score(tab, n, net_masks, score->labels, net_h, net_w, classes, score->conf, score->seen, s);
+        if (st != GS_OK) return st;
+    }
+    const bool gt_overlay = score && score->gt_overlay && overlay;
+    if ((overlay && overlay->out) || gt_overlay) {   // needs the crop-size maps: the caller passes packed_out with it
+        OverlayArgs oa{};
+        oa.crops = overlay->crops;
+        oa.wa = overlay->wa;
+        oa.wb = overlay->wb;
+        oa.n_colours = overlay->n_colours;
+        std::memcpy(oa.pal, overlay->palette_rgb, (size_t)overlay->n_colours * 3);
+        const long long gx = std::min(std::max((max_hw + 8 * 1024 - 1) / (8 * 1024), 1ll), 65535ll);
+        if (overlay->out) {
+            oa.maps = packed_out;
+            oa.out = overlay->out;
+            oa.clamp = overlay->clamp ? 1 : 0;
+            hipLaunchKernelGGL(crops_overlay_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, s, tab, oa);
+            GS_HIP(hipGetLastError());
+        }
+        if (gt_overlay) {   // the same kernel over the packed labels (VisualizeResults_iou.py:218-222)
+            oa.maps = score->labels;
+            oa.out = score->gt_overlay;
+            oa.clamp = score->gt_clamp ? 1 : 0;
+            hipLaunchKernelGGL(crops_overlay_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, s, tab, oa);
+            GS_HIP(hipGetLastError());
+        }
+    }
+    if (paste) {
+        const unsigned gx = (unsigned)std::min<long long>((max_cells + 255) / 256, 4096);
+        hipLaunchKernelGGL(crops_paste_kernel, dim3(gx, (unsigned)n), dim3(256), 0, s, tab, net_masks, net_h, net_w, *paste);
+        GS_HIP(hipGetLastError());
+    }
+    return GS_OK;
+}
+
 // One batch, everything on stream s: the table is complete (offsets within packed_in / packed_out).
 static gs_status run_batch(gs_espnet *const *models, int n_models, int lane, const unsigned char *packed_in, const gs_crop_desc *descs,
                            int n, const float *means, const float *stds, int net_h, int net_w, unsigned char *net_masks,
@@ -534,13 +610,7 @@ static gs_status run_batch(gs_espnet *const *models, int n_models, int lane, con
     }
     CropTable tab;
     std::memset(&tab, 0, sizeof tab);
-    long long max_hw = 1, max_cells = 1;
-    for (int i = 0; i < n; ++i) {
-        tab.d[i] = descs[i];
-        max_hw = std::max(max_hw, (long long)descs[i].h * descs[i].w);
-        if (paste)
-            max_cells = std::max(max_cells, (long long)(descs[i].w / paste->ds + 3) * (descs[i].h / paste->ds + 3));
-    }
+    std::copy(descs, descs + n, tab.d);
     const dim3 prep_grid((unsigned)((net_h * (net_w / 4) + 255) / 256), (unsigned)n);
     // member k resamples the crops with its own mean / std into the lane's tensor; the first launch also zeroes the counts
     auto prepare = [&](int k) -> gs_status {
@@ -573,52 +643,16 @@ static gs_status run_batch(gs_espnet *const *models, int n_models, int lane, con
         if (st == GS_OK) st = espnet_forward(models[0], lane, r);
     }
     if (st != GS_OK) return st;
-    if (packed_out || hist) {
-        long long gx = (max_hw + 8 * 1024 - 1) / (8 * 1024);   // about eight iterations per workgroup, never more than 512
-        gx = std::max(gx, (max_hw + 512 * 1024 - 1) / (512 * 1024));
-        gx = std::min(std::max(gx, 1ll), 65535ll);
-        const dim3 grid((unsigned)gx, (unsigned)n);
-        switch ((classes + 4) / 5) {
-        case 1: hipLaunchKernelGGL(crops_back_kernel<1>, grid, dim3(256), 0, s, tab, net_masks, net_h, net_w, packed_out, hist, classes); break;
-        case 2: hipLaunchKernelGGL(crops_back_kernel<2>, grid, dim3(256), 0, s, tab, net_masks, net_h, net_w, packed_out, hist, classes); break;
-        case 3: hipLaunchKernelGGL(crops_back_kernel<3>, grid, dim3(256), 0, s, tab, net_masks, net_h, net_w, packed_out, hist, classes); break;
-        default: hipLaunchKernelGGL(crops_back_kernel<4>, grid, dim3(256), 0, s, tab, net_masks, net_h, net_w, packed_out, hist, classes); break;
-        }
-        GS_HIP(hipGetLastError());
+    BatchOverlay bo{};
+    if (overlay) {
+        bo.crops = packed_in;
+        bo.palette_rgb = overlay->palette_rgb;
+        bo.n_colours = overlay->n_colours;
+        bo.wa = overlay->wa;
+        bo.wb = overlay->wb;
+        bo.out = overlay_out;
     }
-    if (score) {   // reads the network-resolution masks only
-        st = launch_score(tab, n, net_masks, score->labels, net_h, net_w, classes, score->conf, score->seen, s);
-        if (st != GS_OK) return st;
-    }
-    const bool gt_overlay = score && score->gt_overlay && overlay;
-    if ((overlay && overlay_out) || gt_overlay) {   // needs the crop-size maps: the caller passes packed_out with it
-        OverlayArgs oa{};
-        oa.crops = packed_in;
-        oa.wa = overlay->wa;
-        oa.wb = overlay->wb;
-        oa.n_colours = overlay->n_colours;
-        std::memcpy(oa.pal, overlay->palette_rgb, (size_t)overlay->n_colours * 3);
-        const long long gx = std::min(std::max((max_hw + 8 * 1024 - 1) / (8 * 1024), 1ll), 65535ll);
-        if (overlay_out) {
-            oa.maps = packed_out;
-            oa.out = overlay_out;
-            hipLaunchKernelGGL(crops_overlay_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, s, tab, oa);
-            GS_HIP(hipGetLastError());
-        }
-        if (gt_overlay) {   // the same kernel over the packed labels (VisualizeResults_iou.py:218-222)
-            oa.maps = score->labels;
-            oa.out = score->gt_overlay;
-            oa.clamp = score->gt_clamp ? 1 : 0;
-            hipLaunchKernelGGL(crops_overlay_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, s, tab, oa);
-            GS_HIP(hipGetLastError());
-        }
-    }
-    if (paste) {
-        const unsigned gx = (unsigned)std::min<long long>((max_cells + 255) / 256, 4096);
-        hipLaunchKernelGGL(crops_paste_kernel, dim3(gx, (unsigned)n), dim3(256), 0, s, tab, net_masks, net_h, net_w, *paste);
-        GS_HIP(hipGetLastError());
-    }
-    return GS_OK;
+    return after_masks(tab, n, net_masks, net_h, net_w, classes, packed_out, hist, paste, overlay ? &bo : nullptr, score, s);
 }
 
 static gs_status check_descs(const gs_crop_desc *descs, int n, bool need_out)
@@ -701,6 +735,47 @@ gs_status gs_espnet_score_crops(const uint8_t *net_masks, const uint8_t *packed_
     std::memset(&tab, 0, sizeof tab);
     std::copy(descs, descs + n, tab.d);
     return launch_score(tab, n, net_masks, packed_labels, net_h, net_w, classes, conf, seen, static_cast<hipStream_t>(hip_stream));
+}
+
+gs_status gs_crops_from_masks(const uint8_t *net_masks, const gs_crop_desc *descs, int n, int net_h, int net_w, int classes,
+                              uint8_t *packed_out, unsigned long long *hist, const gs_paste_target *paste, const uint8_t *overlay_crops,
+                              const uint8_t *palette_rgb, int n_colours, float wa, float wb, int clamp, uint8_t *overlay_out,
+                              void *hip_stream)
+{
+    GS_REQUIRE(classes >= 2 && classes <= GS_MAX_CLASSES, "crops_from_masks: 2 to %d classes (got %d)", GS_MAX_CLASSES, classes);
+    GS_REQUIRE(net_masks && (reinterpret_cast<uintptr_t>(net_masks) & 3u) == 0, "crops_from_masks: net_masks is null or not 4-byte aligned");
+    GS_REQUIRE(net_h >= 8 && net_w >= 8 && net_h % 8 == 0 && net_w % 8 == 0 && (long long)net_h * net_w < (1ll << 29),
+               "network size must be a positive multiple of 8 in both dimensions (got %dx%d)", net_h, net_w);
+    GS_REQUIRE(packed_out || hist || paste, "nothing to compute: every output is NULL");
+    GS_REQUIRE((reinterpret_cast<uintptr_t>(packed_out) & 3u) == 0, "crops_from_masks: packed_out is not 4-byte aligned");
+    gs_status st = check_descs(descs, n, packed_out != nullptr);
+    if (st != GS_OK) return st;
+    st = check_paste(paste);
+    if (st != GS_OK) return st;
+    BatchOverlay bo{};
+    if (overlay_out) {
+        GS_REQUIRE(packed_out, "crops_from_masks: an overlay needs packed_out (it colours the crop-size maps)");
+        GS_REQUIRE(overlay_crops && palette_rgb && n_colours >= 1 && n_colours <= GS_MAX_PALETTE,
+                   "overlay: null crops / palette or a table of %d colours (1 .. %d)", n_colours, GS_MAX_PALETTE);
+        GS_REQUIRE(((reinterpret_cast<uintptr_t>(overlay_crops) | reinterpret_cast<uintptr_t>(overlay_out)) & 3u) == 0,
+                   "overlay: the packed crops and the output must be 4-byte aligned");
+        for (int i = 0; i < n; ++i)
+            GS_REQUIRE(descs[i].in_off % 4 == 0, "overlay: crop %d: in_off must be a multiple of 4", i);
+        bo.crops = overlay_crops;
+        bo.palette_rgb = palette_rgb;
+        bo.n_colours = n_colours;
+        bo.wa = wa;
+        bo.wb = wb;
+        bo.out = overlay_out;
+        bo.clamp = clamp;
+    }
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    if (hist)   // (in the crop entries the resampling kernel zeroes the counts)
+        GS_HIP(hipMemsetAsync(hist, 0, (size_t)n * classes * sizeof(unsigned long long), s));
+    CropTable tab;
+    std::memset(&tab, 0, sizeof tab);
+    std::copy(descs, descs + n, tab.d);
+    return after_masks(tab, n, net_masks, net_h, net_w, classes, packed_out, hist, paste, overlay_out ? &bo : nullptr, nullptr, s);
 }
 
 gs_status gs_plan_crop_batches(const int *heights, const int *widths, int n_crops, int batch, int *starts, int cap, int *n_batches)

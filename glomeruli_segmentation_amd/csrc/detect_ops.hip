@@ -632,6 +632,7 @@ __global__ void __launch_bounds__(256)
 overlay_kernel(const unsigned char *region, const unsigned char *cls, long long npix, const unsigned char *pal, int ncol, float wa,
                float wb, unsigned char *out)
 {
+#pragma clang fp contract(off)   // (plain operators under it: __fmul_rn / __fadd_rn do not stop the compiler from fusing the sum)
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= npix)
         return;
@@ -640,7 +641,7 @@ overlay_kernel(const unsigned char *region, const unsigned char *cls, long long 
     for (int ch = 0; ch < 3; ++ch) {
         // palette rows are RGB, the image is BGR (classMap_numpy_color[...] = [b, g, r])
         const float col = c < ncol ? (float)pal[c * 3 + (2 - ch)] : 0.0f;
-        const float v = __fadd_rn(__fmul_rn((float)region[idx * 3 + ch], wa), __fmul_rn(col, wb));   // (no fused multiply-add: numpy's roundings)
+        const float v = (float)region[idx * 3 + ch] * wa + col * wb;   // (no fused multiply-add: numpy's roundings)
         out[idx * 3 + ch] = (unsigned char)fminf(fmaxf(rintf(v), 0.0f), 255.0f);   // saturate_cast<uchar>(cvRound)
     }
 }

@@ -752,7 +752,7 @@ using namespace gs;
 extern "C" {
 
 const char *gs_last_error(void) { return g_err.c_str(); }
-int gs_abi_version(void) { return 9; }   // 2: lanes, block hook, detector, compositor LUT; 3: batched crop entries, detector host entry, build flags; 4: any class count 2..20 (hist is [n,classes]), batch planner, pinned-block query, overlays from the crop pipeline; 5: gs_device_fault_check, GS_ERR_DEVICE_FAULT; 6: gs_wsi_eval_windows; 7: ESPNet-C handles give class maps and counts (forward, segment_host, the crop entries with one model); 8: gs_espnet_plan_forward, gs_espnet_form_info; 9: gs_conv2d_nhwc_form, gs_detector_layer_info, gs_detector_plan
+int gs_abi_version(void) { return 10; }   // 2: lanes, block hook, detector, compositor LUT; 3: batched crop entries, detector host entry, build flags; 4: any class count 2..20 (hist is [n,classes]), batch planner, pinned-block query, overlays from the crop pipeline; 5: gs_device_fault_check, GS_ERR_DEVICE_FAULT; 6: gs_wsi_eval_windows; 7: ESPNet-C handles give class maps and counts (forward, segment_host, the crop entries with one model); 8: gs_espnet_plan_forward, gs_espnet_form_info; 9: gs_conv2d_nhwc_form, gs_detector_layer_info, gs_detector_plan; 10: gs_crops_from_masks (the crop stage behind the masks, no handle)
 gs_status gs_device_fault_check(void)
 {
     GS_HIP(hipDeviceSynchronize());

@@ -38,7 +38,8 @@ typedef enum gs_status {
 } gs_status;
 
 const char *gs_last_error(void);
-/* ABI version, bumped on any change of a signature or of what an entry accepts (9: the detector-plan entries
+/* ABI version, bumped on any change of a signature or of what an entry accepts (10: gs_crops_from_masks, the crop stage behind
+ * the masks as an entry of its own; 9: the detector-plan entries
  * gs_conv2d_nhwc_form, gs_detector_layer_info, gs_detector_plan; 8: the forward-plan entries;
  * 7: ESPNet-C handles give masks and counts).  ABI 8 libraries from the commit that added csrc/enc_head_ens.h on also accept
  * ensembles whose members are all ESPNet-C handles (below); the number was not bumped for that: no signature changed, and a
@@ -196,6 +197,30 @@ gs_status gs_espnet_ensemble_segment_crops(gs_espnet *const *models, int n_model
                                            int n, const float *means, const float *stds, int net_h, int net_w, uint8_t *net_masks,
                                            uint8_t *packed_out, unsigned long long *hist, const gs_paste_target *paste,
                                            void *hip_stream);
+
+/* What the crop entries do once the network-resolution masks exist, as a stream-ordered entry of its own (ABI 10): the function
+ * gs_espnet_segment_crops and the host pipeline themselves call behind the forward, so the same launches with the same grids.
+ * It needs no handle and allocates nothing.  For masks the caller chose it is the test hook of these kernels; behind a forward of
+ * the caller's own it is the crop stage's second half.
+ *   net_masks      device uint8 [n,net_h,net_w], 4-byte aligned; net_h, net_w positive multiples of 8; 2 <= classes <= GS_MAX_CLASSES
+ *   descs          HOST memory, n <= GS_MAX_CROPS_PER_CALL
+ *   packed_out     device or NULL: crop i's map, cv2.resize INTER_NEAREST of net_masks[i] to h x w, at out_off (4-byte aligned
+ *                  buffer, out_off multiples of 4).  Exactly h * w bytes per crop are written: bytes between the maps are not touched.
+ *                  A mask byte >= classes (no forward writes one) is copied like any other.
+ *   hist           device uint64 [n,classes] or NULL: counts of the crop-size maps, a byte >= classes counted as class 0.  WRITTEN
+ *                  (zeroed on the stream first), not accumulated into.
+ *   paste          or NULL: as in gs_espnet_segment_crops (accumulated into; x1 / y1 of the descriptors)
+ *   overlay_out    device or NULL: crop i's overlay uint8 [h,w,3] at in_off (multiples of 4), the blend of gs_crop_overlay below of
+ *                  overlay_crops (device, packed BGR crops at in_off) and the palette (HOST, n_colours rows RGB, 1 .. GS_MAX_PALETTE)
+ *                  indexed by the map in packed_out, which must then be given.  clamp: a map byte beyond the table is black (0) or
+ *                  takes the table's last row (non-zero: the ground-truth overlay's rule, gs_crop_scoring::gt_clamp).  Without
+ *                  overlay_out the five overlay arguments are not read.
+ * packed_out, hist and paste may be NULL but not all three; that, an overlay without packed_out and everything the crop entries
+ * refuse about descriptors, paste target and network size is GS_ERR_INVALID before any device work. */
+gs_status gs_crops_from_masks(const uint8_t *net_masks, const gs_crop_desc *descs, int n, int net_h, int net_w, int classes,
+                              uint8_t *packed_out, unsigned long long *hist, const gs_paste_target *paste,
+                              const uint8_t *overlay_crops, const uint8_t *palette_rgb, int n_colours, float wa, float wb, int clamp,
+                              uint8_t *overlay_out, void *hip_stream);
 
 /* Optional overlay output of the host pipeline below (VisualizeResults_iou.py:139-146): every crop's class map coloured with the
  * palette (rows RGB as in the reference's table, written [b, g, r]) and blended over the crop as

@@ -19,7 +19,7 @@ import numpy as np
 
 
 def _linear_taps(dst, src):
-    scale = src / float(dst)
+    scale = 1.0 / (dst / float(src))          # OpenCV's own expression (resize.cpp: 1. / inv_scale_x), as the kernels form it
     f = ((np.arange(dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)   # half-pixel centres, no antialias
     i0 = np.floor(f).astype(np.int64)
     w1 = f - i0.astype(np.float32)

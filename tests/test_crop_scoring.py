@@ -42,7 +42,7 @@ def test_scoring_entries_declared_exported_prototyped():
     assert declared == set(_lib.SCORING_PROTOTYPES) == {"gs_espnet_score_crops", "gs_espnet_segment_crops_host_scored"}
     assert not declared & set(_lib.PROTOTYPES)
     lib = _lib.load()
-    assert _lib.ABI_VERSION == 9 and lib.gs_abi_version() == 9
+    assert _lib.ABI_VERSION == 10 and lib.gs_abi_version() == 10
     out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
     assert declared <= set(re.findall(r" T (gs_[a-z0-9_]+)", out))
     for name in declared:

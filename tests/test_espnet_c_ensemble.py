@@ -167,15 +167,15 @@ def test_fp32_restatement_within_tau(fold_logits):
 
 
 def test_header_and_prototypes():
-    """no new exported function of the ensemble's: 47 symbols (44 + the three detector-plan entries of ABI 9), equal to _lib.PROTOTYPES; the member limit is a header macro; the three refusals
+    """no new exported function of the ensemble's: 48 symbols (44 + the three detector-plan entries of ABI 9 + gs_crops_from_masks of ABI 10), equal to _lib.PROTOTYPES; the member limit is a header macro; the three refusals
     of mixed lists are where they were"""
     from glomeruli_segmentation_amd import _lib
     with open(os.path.join(REPO, "include", "glomseg.h")) as fh:
         header = fh.read()
     declared = set(re.findall(r"\b(gs_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", header, flags=re.S)))
-    assert declared == set(_lib.PROTOTYPES) and len(declared) == 47
+    assert declared == set(_lib.PROTOTYPES) and len(declared) == 48
     assert re.findall(r"^#define GS_MAX_ENSEMBLE_C (\d+)$", header, flags=re.M) == ["8"] and _lib.GS_MAX_ENSEMBLE_C == 8
-    assert _lib.ABI_VERSION == 9 and _lib.load().gs_abi_version() == 9
+    assert _lib.ABI_VERSION == 10 and _lib.load().gs_abi_version() == 10
     csrc = os.path.join(REPO, "glomeruli_segmentation_amd", "csrc")
     espnet = open(os.path.join(csrc, "espnet.hip")).read()
     assert '#include "enc_head_ens.h"' in espnet and "launch_ens_head(" in open(os.path.join(csrc, "enc_head_ens.h")).read()

@@ -203,7 +203,7 @@ def test_header_declares_the_setup_entries():
     with open(os.path.join(REPO, "include", "glomseg_plan.h")) as fh:
         header = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
     assert {"gs_espnet_pack_weights", "gs_espnet_workspace_plan"} <= set(re.findall(r"\b(gs_[a-z0-9_]+)\s*\(", header)) == set(_lib.PLAN_PROTOTYPES)
-    assert ctypes.sizeof(_lib.WeightPiece) == 48 and _lib.load().gs_abi_version() == 9
+    assert ctypes.sizeof(_lib.WeightPiece) == 48 and _lib.load().gs_abi_version() == 10
 
 
 # ---------------------------------------------------------------------------------------------- sanitizers
