@@ -162,6 +162,12 @@ PLAN_PROTOTYPES = {
 }
 GS_PLAN_LAZY_B2, GS_PLAN_L3C_IN_REDUCE = 1, 2
 
+# every symbol include/glomseg_instances.h declares (additions to ABI 10 with a header of their own)
+INSTANCE_PROTOTYPES = {
+    "gs_instances_plan": (_I, [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)]),
+    "gs_slide_instances": (_I, [_P, _I, _I, _I, _I, _P, ctypes.c_size_t, _I, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -176,7 +182,8 @@ def load():
             "%s is missing: build it with `python -m glomeruli_segmentation_amd.build` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in list(PROTOTYPES.items()) + list(SCORING_PROTOTYPES.items()) + list(PLAN_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(SCORING_PROTOTYPES.items()) + list(PLAN_PROTOTYPES.items()) + \
+            list(INSTANCE_PROTOTYPES.items()):
         if name in PLAN_PROTOTYPES and not hasattr(lib, name):
             continue   # (an ABI 9 library from before glomseg_plan.h, loaded for an A/B: engine.plan_flags then raises)
         fn = getattr(lib, name)   # AttributeError if the symbol is not exported

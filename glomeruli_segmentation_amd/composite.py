@@ -118,6 +118,11 @@ class SlideCompositor:
                                                 _sp(self.device)))
         return hist
 
+    def instances(self, classes=5, connectivity=8, **kw):
+        """the map's connected components, one per glomerulus: instances.label_instances on the map where it lies"""
+        from .instances import label_instances
+        return label_instances(self.map, classes=classes, connectivity=connectivity, **kw)
+
 
 # --------------------------------------------------------------------------- command line (prediction WSI)
 def relabel(img):
