@@ -166,14 +166,16 @@ def batch_for(case, num_cus):
 
 SWEEP_DEPTHS = ((0, 0), (0, 1), (0, 2), (1, 0), (1, 1), (2, 2), (2, 8), (3, 0))
 SWEEP_CLASSES = (2, 5, 7, 12, 16, 20)
+SWEEP_BATCHES = (1, 2, 4, 9, 16, 21, 32)
+SWEEP_HEIGHTS = (8, 136, 264, 512)
 
 
 @lru_cache(maxsize=None)
-def sweep(num_cus):
+def sweep(num_cus, heights=SWEEP_HEIGHTS, batches=SWEEP_BATCHES):
     """[(W, plan)] at legal tile sizes (multiples of 8), depths and class counts"""
     out = []
-    for n in (1, 2, 4, 9, 16, 21, 32):
-        for H in (8, 136, 264, 512):
+    for n in batches:
+        for H in heights:
             for W in range(8, 1048, 8):
                 for p, q in SWEEP_DEPTHS:
                     for classes in SWEEP_CLASSES:
@@ -181,10 +183,10 @@ def sweep(num_cus):
     return out
 
 
-def reachable_forms(num_cus):
+def reachable_forms(num_cus, heights=SWEEP_HEIGHTS, batches=SWEEP_BATCHES):
     """every (launch class, form) the planner returns over the sweep"""
     out = set()
-    for _, f in sweep(num_cus):
+    for _, f in sweep(num_cus, heights, batches):
         out.update(f.items())
     return out
 
@@ -266,19 +268,28 @@ def test_plan_refuses_bad_arguments():
     assert lib.gs_espnet_form_info(3, -1, ctypes.byref(name), ctypes.byref(P)) == _lib.GS_OK and name.value == b"cat_b2"
 
 
+def case_key(case):
+    """the number a case's seeds are made of: the letter of a one-letter name; of a name like "S3" (the small-map cases of
+    test_kernel_forms_small.py, whose batches run to thousands of tiles) a number past every letter, 32 apart, so that no
+    two cases share a tile seed either"""
+    if len(case.name) == 1:
+        return ord(case.name)
+    return 256 * ord(case.name[0]) + 32 * int(case.name[1:])
+
+
 def case_weights(case):
     from glomeruli_segmentation_amd.synth import FOLD_MEAN_STD
     if case.weights == "fold1":
         mean, std = FOLD_MEAN_STD[1]
         return load_weights(1), mean, std
     mean, std = RANDOM_MEAN_STD
-    return random_state_dict(case.p, case.q, classes=case.classes, seed=4000 + ord(case.name)), mean, std
+    return random_state_dict(case.p, case.q, classes=case.classes, seed=4000 + case_key(case)), mean, std
 
 
 def case_tile(case, k):
     """tile k of the case's batch: synthetic in even slots, noise in odd ones, no seed used twice"""
     from glomeruli_segmentation_amd.synth import noise_tile, synth_tile
-    return (noise_tile if k % 2 else synth_tile)(100 * ord(case.name) + k, case.H, case.W)
+    return (noise_tile if k % 2 else synth_tile)(100 * case_key(case) + k, case.H, case.W)
 
 
 def checked_images(n):
@@ -339,11 +350,12 @@ def over(errors):
     return {name: eb for name, eb in errors.items() if not eb[0] <= eb[1]}
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: c.name)
-def test_bounds_discriminate(case):
-    """On the case's shape the fp32 C oracle passes the bounds, and they reject (a) a 1e-4 * max|ref| change of one element
-    in the last column of any stage, (b) the reference with the bottom tap row of a level-3 d16 weight zeroed -- what a
-    wrong F_SKIP_PAD decision computes -- and (c) with the last input channel of a level-3 reduce dropped, a K-tail bug."""
+D16_ROW2_AND_K_TAIL = (("d16.conv.weight", (slice(None), slice(None), 2)), ("c1.conv.weight", (slice(None), -1)))
+
+
+def bounds_discriminate(case, planted=D16_ROW2_AND_K_TAIL):
+    """The body of test_bounds_discriminate for one case.  planted: (weight of the first level-3 block, the part to zero) per
+    planted weight error."""
     from oracle import espnet_oracle as orc
     sd, mean, std = case_weights(case)
     tile = case_tile(case, 0)
@@ -361,34 +373,52 @@ def test_bounds_discriminate(case):
         bumped[-1, v.shape[1] // 2, -1] += 1e-4 * float(np.abs(ref[name]).max())
         assert name in over(stage_errors(case, {name: bumped}, {name: ref[name]})), name
     blk = "encoder.level3.0" if case.q else "encoder.level3_0"
-    for key, part in ((blk + ".d16.conv.weight", (slice(None), slice(None), 2)), (blk + ".c1.conv.weight", (slice(None), -1))):
+    for suffix, part in planted:
+        key = blk + "." + suffix
         w = np.array(sd[key])
+        assert np.abs(w[part]).max() > 0
         w[part] = 0
         wrong = reference(case, dict(sd, **{key: w}), mean, std, tile[None])
         assert over(stage_errors(case, {name: v[0] for name, v in wrong.items()}, ref)), key
 
 
-# ---------------------------------------------------------------------------------------------- the GPU cases
-@pytest.mark.gpu
 @pytest.mark.parametrize("case", CASES, ids=lambda c: c.name)
-def test_kernel_form_against_float64(case):
-    """The case's batch on the HIP path, sized from the device's CU count to take its target forms.  Tiles 0, n-1 and a
-    middle one: every stage the engine still holds and the logits within the bounds of float64, the mask the first-max
-    argmax of the returned logits and off the float64 argmax only where its top-2 margin is below the logit bound, the
-    counts its bincount; the mask-only kernels give the same mask and counts."""
-    import torch
-    from glomeruli_segmentation_amd.engine import EspnetEngine
-    assert torch.cuda.is_available(), "the gpu-marked tests need a HIP device"
-    num_cus = torch.cuda.get_device_properties(0).multi_processor_count
-    n = batch_for(case, num_cus)
-    hit = plan(n, case.H, case.W, case.p, case.q, case.classes, num_cus)
-    assert all(hit[k] == v for k, v in case.targets.items()) and case.edges <= edges(case.H, case.W)
-    sd, mean, std = case_weights(case)
-    tiles = np.stack([case_tile(case, k) for k in range(n)])
-    picks = checked_images(n)
-    ref = reference(case, sd, mean, std, tiles[picks])
-    eng = EspnetEngine(sd, classes=case.classes, p=case.p, q=case.q)
-    try:
+def test_bounds_discriminate(case):
+    """On the case's shape the fp32 C oracle passes the bounds, and they reject (a) a 1e-4 * max|ref| change of one element
+    in the last column of any stage, (b) the reference with the bottom tap row of a level-3 d16 weight zeroed -- what a
+    wrong F_SKIP_PAD decision computes -- and (c) with the last input channel of a level-3 reduce dropped, a K-tail bug."""
+    bounds_discriminate(case)
+
+
+# ---------------------------------------------------------------------------------------------- the GPU cases
+class DeviceCase:
+    """A case's engine on the HIP path.  forward(n, picks) runs the case's first n tiles and holds tiles `picks` to float64:
+    every stage the engine still holds and the logits within the bounds, the mask the first-max argmax of the returned
+    logits and off the float64 argmax only where its top-2 margin is below the logit bound, the counts its bincount; the
+    mask-only kernels give the same mask and counts."""
+
+    def __init__(self, case):
+        import torch
+        from glomeruli_segmentation_amd.engine import EspnetEngine
+        assert torch.cuda.is_available(), "the gpu-marked tests need a HIP device"
+        self.torch, self.case = torch, case
+        self.num_cus = torch.cuda.get_device_properties(0).multi_processor_count
+        self.sd, self.mean, self.std = case_weights(case)
+        self.eng = EspnetEngine(self.sd, classes=case.classes, p=case.p, q=case.q)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.eng.close()
+
+    def forward(self, n, picks):
+        """-> (mask, hist, logits) of all n tiles, on the host; prints the worst error / bound per stage over picks"""
+        torch, case, eng, mean, std = self.torch, self.case, self.eng, self.mean, self.std
+        hit = plan(n, case.H, case.W, case.p, case.q, case.classes, self.num_cus)
+        assert all(hit[k] == v for k, v in case.targets.items()) and case.edges <= edges(case.H, case.W)
+        tiles = np.stack([case_tile(case, k) for k in range(n)])
+        ref = reference(case, self.sd, mean, std, tiles[picks])
         t = torch.from_numpy(tiles).cuda()
         mask, hist, logits = eng.segment(t, mean, std, want_logits=True)
         torch.cuda.synchronize()
@@ -411,7 +441,18 @@ def test_kernel_form_against_float64(case):
         m2, h2, _ = eng.segment(t, mean, std)                                    # the mask-only kernels
         assert torch.equal(m2, mask) and torch.equal(h2, hist)
         eng.check_device_faults()
-    finally:
-        eng.close()
-    print("case %s: n %d on %d CUs, forms %s; worst error / bound: %s" % (
-        case.name, n, num_cus, hit, ", ".join("%s %.1e/%.1e" % (k, e, b) for k, (e, b) in worst.items())))
+        print("case %s: n %d on %d CUs, forms %s; worst error / bound: %s" % (
+            case.name, n, self.num_cus, hit, ", ".join("%s %.1e/%.1e" % (k, e, b) for k, (e, b) in worst.items())))
+        return mask.cpu(), hist.cpu(), logits.cpu()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", CASES, ids=lambda c: c.name)
+def test_kernel_form_against_float64(case):
+    """The case's batch on the HIP path, sized from the device's CU count to take its target forms.  Tiles 0, n-1 and a
+    middle one: every stage the engine still holds and the logits within the bounds of float64, the mask the first-max
+    argmax of the returned logits and off the float64 argmax only where its top-2 margin is below the logit bound, the
+    counts its bincount; the mask-only kernels give the same mask and counts."""
+    with DeviceCase(case) as dev:
+        n = batch_for(case, dev.num_cus)
+        dev.forward(n, checked_images(n))
