@@ -160,7 +160,7 @@ PLAN_PROTOTYPES = {
                                 ctypes.POINTER(WeightPiece), _I, ctypes.POINTER(_I)]),
     "gs_espnet_workspace_plan": (_I, [_I] * 7 + [ctypes.POINTER(ctypes.c_size_t)]),
 }
-GS_PLAN_LAZY_B2, GS_PLAN_L3C_IN_REDUCE = 1, 2
+GS_PLAN_LAZY_B2, GS_PLAN_L3C_IN_REDUCE, GS_PLAN_CLS_IN_L3 = 1, 2, 4
 
 # every symbol include/glomseg_instances.h declares (additions to ABI 10 with a header of their own)
 INSTANCE_PROTOTYPES = {

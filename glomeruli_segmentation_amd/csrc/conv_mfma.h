@@ -113,6 +113,14 @@ struct ConvArgs {
     long long side_sn;
     int side_sc, side_pitch, side_off;
     unsigned side_img_bytes;
+    // F_CLS1X1 (level-3 branch launches): the records [COUT][CLS_REC] = {scale, shift, alpha, w[0..5)} of this launch's channels
+    // of b3 + classifier (a slice of the blob piece "b3"), and the partial class sums: per image 2 lane halves x CLS_N planes
+    // [H][W] (plane stride cls_sc, row pitch cls_pitch, no halo)
+    const float *crec;
+    float *cls;
+    long long cls_sn;
+    int cls_sc, cls_pitch;
+    unsigned cls_img_bytes;
     // GS_DIAG builds only:
     int stagger;   // units of 1024 cycles by which waves WAVES/2.. start late (0 = off)
     int prio_mode; // wave priority of the two halves of a workgroup: 0 alternates per dilation, 1 per task (shipped), 2 off, 3 fixed
@@ -191,6 +199,21 @@ __device__ __forceinline__ float prelu_med3(float v, float alpha, float pin)
     return __builtin_amdgcn_fmed3f(v, alpha * v, pin);
 }
 
+// F_CLS1X1's arithmetic on one pixel (float) or on a lane's pixel pair (two floats: v_pk_fma_f32 / v_pk_mul_f32 do both in one
+// instruction, each component the same IEEE operation as the scalar form -- the same bits at one, two or four pixels per lane)
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float cls_fma(float a, float b, float c) { return fmaf(a, b, c); }
+__device__ __forceinline__ f32x2 cls_fma(float a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma((f32x2)(a), b, c); }
+__device__ __forceinline__ float cls_prelu(float v, float alpha, float pin) { return prelu_med3(v, alpha, pin); }
+__device__ __forceinline__ f32x2 cls_prelu(f32x2 v, float alpha, float pin)
+{
+    const f32x2 av = v * alpha;
+    f32x2 o;
+    o[0] = __builtin_amdgcn_fmed3f(v[0], av[0], pin);
+    o[1] = __builtin_amdgcn_fmed3f(v[1], av[1], pin);
+    return o;
+}
+
 // epilogue flags
 constexpr int F_BNACT = 1;   // folded BatchNorm + PReLU on the way out
 constexpr int F_RES = 2;     // add the residual input before BN (ESP block, Model.py:211-213)
@@ -245,6 +268,24 @@ constexpr int F_BNLOAD = 8388608;  // see ConvArgs::bnl_s0
 constexpr int F_SIDE_SHIFT = 27;
 constexpr int F_SIDE1X1(int classes) { return classes << F_SIDE_SHIFT; }
 // (SIDE_REC, SIDE_ZROWS, side_table_floats, side_table_offset: espnet_facts.h, shared with the weight packer)
+// A 1x1 convolution of the launch's own OUTPUT behind a second BN + PReLU, computed on the vector ALU in the epilogue: the
+// encoder classifier over b3 = BR(256) of cat([output2_0, output2]) (Model.py:368-370), of which the level-3 down-sampler's
+// launch holds channels 0..127 and the last ESP block's launch channels 128..255 as finished epilogue registers (after BN +
+// PReLU, and after the residual add: the value that is stored).  A finished register -- channel ch = slot offset + accumulator
+// row -- goes through b3 of its channel, t = prelu(v * scale + shift), and adds w[k] * t into CLS_N running sums per pixel that
+// live across the five concat slots of a task and are stored when the task ends.  Lanes l and l + 32 hold the two halves of a
+// pixel's rows and do NOT meet: each half stores its own partial plane, [half][class][H][W] in ConvArgs::cls, and
+// dec1_sums_kernel (espnet_kernels.h) adds the two halves of both launches.  The channel records come from LDS: the launch's
+// COUT rows of the blob piece "b3" are staged behind the image, one zero record behind them for the padded rows of a slot
+// (rows 28..31 of d1, 25..31 of the others), which therefore add exact zeros; registers whose two channels are both padding
+// are skipped.
+// SUMMATION ORDER of one pixel's class sum, the same in every form (one, two or four pixels per lane, run or vector mapping,
+// weights from LDS or the ring), so batch size and task shape never change a bit: per launch and lane half ONE fmaf chain
+// from 0.0f over the slots d1, d2, d4, d8, d16, within a slot the half's rows ascending (accumulator registers 0..15); then
+// dec1_sums_kernel adds ((A0 + A1) + (B0 + B1)), A = output2_0's launch, B = output2's, the index the lane half.
+// Needs MT == 32, F_BNACT, NDIL == 5 and COUT * CLS_REC floats in whole DMA pieces, one per wave.
+constexpr int F_CLS1X1 = 256;
+constexpr int CLS_N = 5, CLS_REC = 8;   // classes of the side sums; floats of a record (dec1_record<5>)
 constexpr int F_X_NOLOAD = 16;  // GS_DIAG timing experiments only (results are garbage): no activation loads in the loop
 constexpr int F_X_NOLDS = 32;   // GS_DIAG: no LDS weight reads in the loop
 constexpr int F_X_NOEPI = 64;   // GS_DIAG: no epilogue at all
@@ -259,6 +300,8 @@ constexpr int F_X_STL2 = 67108864;      // GS_DIAG: likewise the result stores
 constexpr int F_X_ALL = F_X_NOLOAD | F_X_NOLDS | F_X_NOEPI | F_X_STAMP | F_X_STAMP2 | F_X_NOEPIMEM | F_X_RESL2 | F_X_STL2;
 
 // (the float layout of a configuration's packed image in the weight blob -- ConvImage, conv_image, conv_wfloats: espnet_facts.h)
+// F_CLS1X1: float offset in LDS of the channel records behind an image of `image_lds_floats` floats (whole 1-KiB DMA pieces)
+constexpr int conv_cls_lds_offset(int image_lds_floats) { return (image_lds_floats + 255) / 256 * 256; }
 
 #ifndef CFG_STAGE_ROT
 #define CFG_STAGE_ROT 17   // 0 = every workgroup stages the weight image in the same order
@@ -298,6 +341,10 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
     constexpr bool BNL = FLAGS & F_BNLOAD;
     constexpr int SCLS = (FLAGS >> F_SIDE_SHIFT) & 15;   // F_SIDE1X1: classes of the side 1x1 (0: none)
     constexpr bool SIDE = SCLS > 0;
+    constexpr bool CLSF = FLAGS & F_CLS1X1;
+    static_assert(!CLSF || (MT == 32 && NDIL == 5 && TAPS == 9 && (FLAGS & F_BNACT) && !(FLAGS & (F_DUAL | F_NOSTORE | F_BNLOAD | F_X_ALL)) &&
+                            !SIDE && ((NOUT1 + (NDIL - 1) * NOUT) * CLS_REC) % 256 == 0 && (NOUT1 + (NDIL - 1) * NOUT) * CLS_REC / 256 <= WAVES),
+                  "F_CLS1X1 is for the level-3 branch launches: 32-row accumulators, five slots, the records in whole DMA pieces");
     static_assert(!SIDE || ((FLAGS & F_S2PAIR) && TAPS == 9 && STRIDE == 2 && MT == 32 && NDIL == 1 && SCLS <= SIDE_REC &&
                             (CINP / M_KL_OF(MT)) % G == 0 && G * M_KL_OF(MT) <= SIDE_ZROWS && !(FLAGS & (F_A_GLOBAL | F_VEC | F_X_ALL))),
                   "F_SIDE1X1 is for the stride-2 3x3 reduce on 32-pixel runs, a tap row in whole chunks");
@@ -354,6 +401,9 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
     const float *bnl = lds + (conv_image(CINP, TAPS, NDIL, NOUT1, NOUT, BNACT, DUAL, FUSE ? M::NACC : 0).total - LDS_SRC0);
     // F_SIDE1X1: [CINP + SIDE_ZROWS][SIDE_REC] class weights per input channel, the last rows zero
     const float *sidew = lds + side_table_offset(conv_image(CINP, TAPS, NDIL, NOUT1, NOUT, BNACT, DUAL, FUSE ? M::NACC : 0).total, CINP, M::KL);
+    // F_CLS1X1: [COUT + 1][CLS_REC] records of b3 + classifier behind the image's last whole DMA piece, the last one zero
+    constexpr int CREC_OFF = conv_cls_lds_offset(conv_image(CINP, TAPS, NDIL, NOUT1, NOUT, BNACT, DUAL, FUSE ? M::NACC : 0).total - LDS_SRC0);
+    const float *crecl = lds + CREC_OFF;
     const __amdgpu_buffer_rsrc_t rsrc_w =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.wpack), 0, AGL ? WFL * 4 : 0, 0x00020000);
 
@@ -368,6 +418,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
     const int vres = RES ? (kq * KSTR * a.res_sc + xl) * 4 : 0;
     const int vout2 = DUAL ? (kq * KSTR * a.out2_sc + xl) * 4 : 0;
     const int vout3 = FUSE ? (kq * KSTR * a.out3_sc + xl) * 4 : 0;
+    const int vcls = CLSF ? (kq * CLS_N * a.cls_sc + xl) * 4 : 0;   // the lane half's group of class planes
     const int prio_mode = kDiag ? a.prio_mode : 1;
     // the two waves that share a SIMD (their priorities alternate): waves wid and wid + 4 of an eight-wave workgroup; with
     // four-wave workgroups (two per CU) the SIMD's other wave belongs to the workgroup dispatched half a grid later
@@ -446,6 +497,9 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
         const __amdgpu_buffer_rsrc_t rout3 = __builtin_amdgcn_make_buffer_rsrc(
             FUSE ? a.out3 + (long long)n * a.out3_sn : a.out, 0, FUSE ? a.out3_img_bytes : 0u, 0x00020000);
         const int sout3 = FUSE ? (a.out3_off + y * a.out3_pitch + x0) * 4 : 0;
+        const __amdgpu_buffer_rsrc_t rcls = __builtin_amdgcn_make_buffer_rsrc(
+            CLSF ? a.cls + (long long)n * a.cls_sn : a.out, 0, CLSF ? a.cls_img_bytes : 0u, 0x00020000);
+        const int scls = CLSF ? (y * a.cls_pitch + x0) * 4 : 0;
 
         typename M::acc_t acc[P];
         typename M::acc_t acc2[FUSE ? P : 1];   // F_FUSE1X1: the next block's reduced map of this strip
@@ -460,7 +514,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
         // per-lane epilogue offsets: lanes beyond the row end get an offset past num_records, which the
         // buffer range check turns into a dropped store / zero load (no exec-mask branches)
         constexpr int OOB = 0x7ffffff0;
-        int vo[P], vr[P], vo2[P], vo3[P];
+        int vo[P], vr[P], vo2[P], vo3[P], vc[P];
 #pragma unroll
         for (int p = 0; p < P; ++p) {
             const bool xok = x0 + (VEC ? xl : p * MT + px) < a.W;   // F_VEC: W % P == 0, a lane's pixels are all in or all out
@@ -468,6 +522,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
             vr[p] = xok ? vres + (VEC ? 0 : p * MT * 4) : OOB;
             vo2[p] = xok ? vout2 + (VEC ? 0 : p * MT * 4) : OOB;
             vo3[p] = xok ? vout3 + (VEC ? 0 : p * MT * 4) : OOB;
+            vc[p] = xok ? vcls + (VEC ? 0 : p * MT * 4) + scls : OOB;
         }
         // The residual (block input) values of a whole concat slot live in dedicated registers and are
         // requested a full dilation ahead of the epilogue that adds them: fetched next to the store,
@@ -649,6 +704,14 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
                     (const __attribute__((address_space(1))) void *)(a.wpack + LDS_SRC0 + j * 256 + lane * 4),
                     (__attribute__((address_space(3))) void *)(lds + j * 256), 16, 0, 0);
             }
+            if (CLSF) {   // the launch's records of b3 + classifier: one 1-KiB piece per wave, and the zero record behind them
+                if (wid < COUT * CLS_REC / 256)
+                    __builtin_amdgcn_global_load_lds(
+                        (const __attribute__((address_space(1))) void *)(a.crec + wid * 256 + lane * 4),
+                        (__attribute__((address_space(3))) void *)(lds + CREC_OFF + wid * 256), 16, 0, 0);
+                if (tid < CLS_REC)
+                    lds[CREC_OFF + COUT * CLS_REC + tid] = 0.0f;
+            }
             // The barrier (with the `s_waitcnt vmcnt(0) lgkmcnt(0)` in front of it) is UNCONDITIONAL on this path: an LDS-DMA
             // instruction is a FLAT operation to the compiler's wait-count pass, and while one may be pending on ANY path into a
             // block every wait in that block is forced to vmcnt(0) / lgkmcnt(0).  Behind `if (pieces > 0)` the path without the
@@ -706,6 +769,23 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
             for (int p = 0; p < P; ++p)
                 acc2[p] = (typename M::acc_t)(0.0f);
         }
+        // F_CLS1X1: the task's running class sums of this lane half, [pixel or pixel pair][class]
+        using cs_t = std::conditional_t<P % 2 == 0, f32x2, float>;
+        constexpr int CSU = P % 2 == 0 ? P / 2 : P;   // units of a lane: pixel pairs when the pixels pair up
+        cs_t cs[CLSF ? CSU : 1][CLSF ? CLS_N : 1];
+        if (CLSF) {
+#pragma unroll
+            for (int u = 0; u < CSU; ++u)
+#pragma unroll
+                for (int k = 0; k < CLS_N; ++k)
+                    cs[u][k] = (cs_t)(0.0f);
+        }
+        auto cs_at = [&](int p, int k) -> float {
+            if constexpr (P % 2 == 0)
+                return cs[CLSF ? p / 2 : 0][CLSF ? k : 0][p % 2];
+            else
+                return cs[CLSF ? p : 0][CLSF ? k : 0];
+        };
         if (prio_mode == 1) {
             if ((((task - t0) / tstride) + (second_of_simd ? 1 : 0)) & 1)
                 __builtin_amdgcn_s_setprio(1);
@@ -720,6 +800,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
         // and the fused 1x1's A operand
         struct EpiParams {
             float scale = 1.0f, shift = 0.0f, alpha = 1.0f, scale2 = 1.0f, shift2 = 0.0f, alpha2 = 1.0f, a2 = 0.0f;
+            float cscale = 0.0f, cshift = 0.0f, calpha = 0.0f, cw[CLS_N] = {};   // F_CLS1X1: the channel's record
         };
         auto epi_params = [&](int di, auto r_) __attribute__((always_inline)) {
             constexpr int r = decltype(r_)::value;
@@ -744,6 +825,15 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
                     q.shift2 = bp[4 * COUT];
                     q.alpha2 = bp[5 * COUT];
                 }
+            }
+            if (CLSF) {   // (two 16-byte LDS reads; a padded row takes the zero record)
+                const float *cr = crecl + (live ? cb + ch0 + kq * KSTR : COUT) * CLS_REC;
+                q.cscale = cr[0];
+                q.cshift = cr[1];
+                q.calpha = cr[2];
+#pragma unroll
+                for (int k = 0; k < CLS_N; ++k)
+                    q.cw[k] = cr[3 + k];
             }
             return q;
         };
@@ -787,6 +877,28 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
                 buf_store_vec<P, SAUX>(rout, live ? ((FLAGS & F_X_STL2) ? ((int)(wg & 255) * 8192 + ((vo[0] + so) & 0x1ff0)) : vo[0] + so) : OOB, o1);
             if (VEC && DUAL)
                 buf_store_vec<P, SAUX2>(rout2, live ? vo2[0] + so2 : OOB, o2);
+            if (CLSF && ch0 < nout) {   // (uniform) a register whose two channels are both padding adds nothing
+                const float cpin = prelu_pin(q.calpha);
+#pragma unroll
+                for (int u = 0; u < CSU; ++u) {
+                    cs_t t;
+                    if constexpr (P % 2 == 0) {
+                        t[0] = o1[2 * u];
+                        t[1] = o1[2 * u + 1];
+                    } else {
+                        t = o1[u];
+                    }
+                    t = cls_fma(q.cscale, t, (cs_t)(q.cshift));
+                    t = cls_prelu(t, q.calpha, cpin);
+#pragma unroll
+                    for (int k = 0; k < CLS_N; ++k) {
+                        cs[u][k] = cls_fma(q.cw[k], t, cs[u][k]);
+                        // (pinned to this register's step, as F_SIDE1X1's: left alone hipcc sinks the sums to the end of the slot and
+                        // keeps every register's record live until then)
+                        asm volatile("" : "+v"(cs[u][k]));
+                    }
+                }
+            }
             if (FUSE && ch0 < nout) {   // (uniform) registers whose two channels are both beyond the slot hold nothing
                 // k = lane's k-group <-> channel cb + ch0 + kq*KSTR; the table row is zero for channels beyond the slot
 #pragma unroll
@@ -977,6 +1089,24 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
                         buf_store_vec<P, 0>(rout3, live3 ? vo3[0] + so3 : OOB, o3);
                 }
             }
+            if (CLSF && di + 1 == NDIL) {
+                // the five slots are summed: this lane half's partial sums leave for its own group of class planes
+#pragma unroll
+                for (int k = 0; k < CLS_N; ++k) {
+                    const int sc = k * a.cls_sc * 4;
+                    if (VEC) {
+                        float o[P];
+#pragma unroll
+                        for (int p = 0; p < P; ++p)
+                            o[p] = cs_at(p, k);
+                        buf_store_vec<P, 0>(rcls, vc[0] == OOB ? OOB : vc[0] + sc, o);
+                    } else {
+#pragma unroll
+                        for (int p = 0; p < P; ++p)
+                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, cs_at(p, k)), rcls, vc[p] == OOB ? OOB : vc[p] + sc, 0, 0);
+                    }
+                }
+            }
             if ((FLAGS & F_X_STAMP) && lane == 0 && task == t0)
                 a.stamp[wg * 8 + 2 + di] = __builtin_amdgcn_s_memrealtime();
             if (stamp2)
@@ -1013,7 +1143,10 @@ gs_status launch_conv_mfma(ConvArgs a, int num_cus, hipStream_t stream)
                           : (FLAGS & F_BNLOAD) ? 3 * (CINP + Mfma<MT>::KL)
                                                : 0;
     a.wfloats = im.total + EXTRA;
-    const int lds_floats = im.total + EXTRA - ((FLAGS & F_A_GLOBAL) ? im.w : 0);
+    // F_CLS1X1: the channel records (+ the zero record) lie behind the image's last whole DMA piece
+    constexpr int IMG_LDS = im.total + EXTRA - ((FLAGS & F_A_GLOBAL) ? im.w : 0);
+    constexpr int lds_floats = (FLAGS & F_CLS1X1) ? conv_cls_lds_offset(IMG_LDS) + (im.cout + 1) * CLS_REC : IMG_LDS;
+    static_assert((size_t)((lds_floats + 255) / 256 * 256) * sizeof(float) <= 160 * 1024, "the LDS image of a form exceeds a CU's 160 KB");
     const size_t lds_bytes = (size_t)((lds_floats + 255) / 256 * 256) * sizeof(float);   // whole 1-KiB DMA pieces
     static std::mutex mu;
     static std::map<int, LaunchInfo> by_device;

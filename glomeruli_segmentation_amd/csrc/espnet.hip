@@ -311,8 +311,17 @@ static gs_status launch_l3_reduce(const Model *m, form::l3_reduce f, bool side5,
     return not_planned("l3_reduce");
 }
 
-static gs_status launch_l3_down(const Model *m, form::l3_down f, const ConvArgs &ca, hipStream_t s)
+// cls5: the plan's cls_in_l3 -- every form the plan picks with it also sums the five-class classifier's channels 0..127 into
+// ca.cls (F_CLS1X1); the unfused forms (cls_side_sums) and the four-pixel one (plan_forward) are never planned with it
+static gs_status launch_l3_down(const Model *m, form::l3_down f, bool cls5, const ConvArgs &ca, hipStream_t s)
 {
+    if (cls5)
+        switch (f) {
+        case form::l3_down::P1R: return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | POL_L3_DOWN | FUSE_L3 | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0) | F_CLS1X1>(ca, m->num_cus, s);
+        case form::l3_down::P2R_VEC: return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | POL_L3_DOWN | FUSE_L3 | F_VEC | SKIP_L3 | F_CLS1X1>(ca, m->num_cus, s);
+        case form::l3_down::P2F: return launch_conv_mfma<CFG_L3_BR_P2F, F_BNACT | POL_L3_DOWN | FUSE_L3 | F_CLS1X1>(ca, m->num_cus, s);
+        default: return not_planned("l3_down with the classifier's side sums");
+        }
     switch (f) {
     case form::l3_down::P1R: return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | POL_L3_DOWN | FUSE_L3 | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(ca, m->num_cus, s);
     case form::l3_down::P2R_VEC:
@@ -343,8 +352,17 @@ static gs_status launch_l3_esp_fused(const Model *m, form::l3_esp_fused f, const
     return not_planned("l3_esp_fused");
 }
 
-static gs_status launch_l3_esp_last(const Model *m, form::l3_esp_last f, const ConvArgs &ca, hipStream_t s)
+// cls5: as launch_l3_down's, for the network's last block: channels 128..255
+static gs_status launch_l3_esp_last(const Model *m, form::l3_esp_last f, bool cls5, const ConvArgs &ca, hipStream_t s)
 {
+    if (cls5)
+        switch (f) {
+        case form::l3_esp_last::P1R: return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | F_RES | POL_L3_ESP | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0) | F_CLS1X1>(ca, m->num_cus, s);
+        case form::l3_esp_last::P2R_VEC: return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | F_RES | F_VEC | POL_L3_ESP | SKIP_L3 | F_CLS1X1>(ca, m->num_cus, s);
+        case form::l3_esp_last::BR_VEC: return launch_conv_mfma<CFG_L3_BR, F_BNACT | F_RES | F_VEC | POL_L3_ESP | F_CLS1X1>(ca, m->num_cus, s);
+        case form::l3_esp_last::P2: return launch_conv_mfma<CFG_L3_BR_P2, F_BNACT | F_RES | F_CLS1X1>(ca, m->num_cus, s);
+        case form::l3_esp_last::none: return not_planned("l3_esp_last");
+        }
     switch (f) {
     case form::l3_esp_last::P1R: return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | F_RES | POL_L3_ESP | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(ca, m->num_cus, s);
     case form::l3_esp_last::P2R_VEC: return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | F_RES | F_VEC | POL_L3_ESP | SKIP_L3>(ca, m->num_cus, s);   // tap rows in the halo skipped
@@ -461,6 +479,17 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
         a.nout3 = nout3;
         return a;
     };
+    // F_CLS1X1: the classifier's partial sums of one producer (0: output2_0, channels 0..127; 1: output2, 128..255) go to its
+    // two groups of class planes in tt, which nothing reads or writes before dec2 (cls_side_sums, espnet_facts.h)
+    auto with_cls = [&](ConvArgs a, int producer) {
+        a.crec = wb + m->w.b3 + (long long)producer * 128 * CLS_REC;
+        a.cls_sc = H3 * W3;
+        a.cls_pitch = W3;
+        a.cls = m->tt.base + (long long)producer * 2 * CLS_N * a.cls_sc;
+        a.cls_sn = m->tt.sn;
+        a.cls_img_bytes = (unsigned)((size_t)2 * CLS_N * a.cls_sc * sizeof(float));
+        return a;
+    };
     const bool lazy_b2 = plan.lazy_b2;
     m->b2_lazy = lazy_b2;
     int rd2 = 0;   // index of the reduced map the next level-2 branch kernel reads
@@ -522,9 +551,17 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
     });
     if (plan.l3c_in_reduce)
         m->set_stage("level3_C", m->l3c, m->classes);
-    L.run(K_L3_DOWN, px3 * (25 * 9 * 128 * 2) + (m->w.l3_0.fused_next ? px3 * (128 * 25 * 2) : 0), [&] {
-        const ConvArgs ca = conv_args(m->r3[rd3], wb + m->w.l3_0.br, m->cc[0], nullptr, n);
-        return launch_l3_down(m, plan.l3_down, m->w.l3_0.fused_next ? with_fused(ca, m->r3[rd3 ^ 1], 25) : ca, s);
+    const double cls_flops = plan.cls_in_l3 ? px3 * (128 * m->classes * 2) : 0;   // a producer's half of the classifier (F_CLS1X1)
+    L.run(K_L3_DOWN, px3 * (25 * 9 * 128 * 2) + (m->w.l3_0.fused_next ? px3 * (128 * 25 * 2) : 0) + cls_flops, [&] {
+        ConvArgs ca = conv_args(m->r3[rd3], wb + m->w.l3_0.br, m->cc[0], nullptr, n);
+        if (plan.cls_in_l3) {
+            if ((long long)CLS_PART_PLANES * H3 * W3 > m->tt.sn) {
+                set_error("internal: the classifier's partial planes do not fit the workspace's tt");
+                return GS_ERR_INVALID;
+            }
+            ca = with_cls(ca, 0);
+        }
+        return launch_l3_down(m, plan.l3_down, plan.cls_in_l3, m->w.l3_0.fused_next ? with_fused(ca, m->r3[rd3 ^ 1], 25) : ca, s);
     });
     bool have_r3 = m->w.l3_0.fused_next;
     m->set_stage("level3_reduce", m->r3[rd3], 25);      // (debug: valid until the second ESP block overwrites the map)
@@ -538,12 +575,13 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
             L.run(K_L3_C1, px3 * (128 * 25 * 2), [&] {
                 return launch_l3_c1(m, conv_args(m->cc[cur3], wb + m->w.l3[i].c1, m->r3[rd3], nullptr, n), s);
             });
-        L.run(K_L3_ESP, px3 * (25 * 9 * 128 * 2) + (fuse_next ? px3 * (128 * 25 * 2) : 0), [&] {
+        L.run(K_L3_ESP, px3 * (25 * 9 * 128 * 2) + (fuse_next ? px3 * (128 * 25 * 2) : 0) + (i == m->q - 1 ? cls_flops : 0), [&] {
             const ConvArgs ca = conv_args(m->r3[rd3], wb + m->w.l3[i].br, m->cc[nxt], &m->cc[cur3], n);
             GS_DIAG_TRY(diag_l3_esp(m, ca, i, s, dst_));
             if (fuse_next)
                 return launch_l3_esp_fused(m, plan.l3_esp_fused, with_fused(ca, m->r3[rd3 ^ 1], 25), i, s);
-            return launch_l3_esp_last(m, plan.l3_esp_last, ca, s);
+            const bool cls5 = plan.cls_in_l3 && i == m->q - 1;   // the network's last block holds output2
+            return launch_l3_esp_last(m, plan.l3_esp_last, cls5, cls5 ? with_cls(ca, 1) : ca, s);
         });
         have_r3 = fuse_next;
         rd3 ^= have_r3 ? 1 : 0;
@@ -566,7 +604,24 @@ static gs_status decode(Model *m, Launcher &L, const ForwardPlan &plan, const Fo
     // ESPNet-C: the 1/8-scale logits are an output of their own and the input of the head; a caller that wants the class map
     // only gets them in the (otherwise unused) up_l3 buffer of the workspace, which is larger than [n][classes][H3][W3]
     float *enc_logits = !m->encoder_only ? nullptr : r.logits ? r.logits : m->o2c.base;
-    L.run(K_DEC1, px3 * (256 * ncls * 2) + px3 * (ncls * ncls * 4 * 2), [&] {
+    L.run(K_DEC1, (plan.cls_in_l3 ? 0 : px3 * (256 * ncls * 2)) + px3 * (ncls * ncls * 4 * 2), [&] {
+        if constexpr (CLS == CLS_N) {
+            if (plan.cls_in_l3) {   // the classifier came out of the level-3 epilogues: add the partial planes, then br + up_l3
+                Dec1SumsArgs a{};
+                a.part = m->tt.base;
+                a.psn = m->tt.sn;
+                a.psc = H3 * W3;
+                a.br = wb + m->w.br;
+                a.wup = wb + m->w.wup3;
+                a.out = view(m->o2c);
+                a.N = n;
+                a.H3 = H3;
+                a.W3 = W3;
+                a.classes = ncls;
+                hipLaunchKernelGGL(dec1_sums_kernel<CLS>, dim3(blocks_for((long long)n * H3 * W3)), dim3(256), 0, s, a);
+                return GS_OK;
+            }
+        }
         Dec1Args a{};
         a.c0 = view(m->cc[0]);
         a.clast = view(m->cc[enc.last]);
@@ -1156,8 +1211,8 @@ gs_status gs_espnet_block_forward(gs_espnet *h, int kind, int level, int index, 
         } else {
             r = kind == 1 ? launch_l3_reduce(&m, form::l3_reduce::C1S, false, rca, s) : launch_l3_c1(&m, rca, s);
             if (r != GS_OK) return r;
-            r = kind == 1 ? launch_l3_down(&m, unfused_l3_down(dst.W, no_vec()), bca, s)
-                          : launch_l3_esp_last(&m, whole_row_l3_esp(dst.W, no_vec()), bca, s);
+            r = kind == 1 ? launch_l3_down(&m, unfused_l3_down(dst.W, no_vec()), false, bca, s)
+                          : launch_l3_esp_last(&m, whole_row_l3_esp(dst.W, no_vec()), false, bca, s);
         }
         if (r != GS_OK) return r;
         hipLaunchKernelGGL(unpad_kernel, dim3(blocks_for((long long)nout)), dim3(256), 0, s, view(dst), 0, cout, tmp);
@@ -1197,7 +1252,7 @@ gs_status gs_espnet_plan_flags(int n, int height, int width, int p, int q, int c
     gs_status st = gs_espnet_plan_forward(n, height, width, p, q, classes, num_cus, nullptr, 0, &count);   // (the same refusals)
     if (st != GS_OK) return st;
     const ForwardPlan pl = plan_forward(n, height, width, p, q, padded_classes(classes), num_cus, no_vec(), encoder_only != 0);
-    *flags = (pl.lazy_b2 ? GS_PLAN_LAZY_B2 : 0) | (pl.l3c_in_reduce ? GS_PLAN_L3C_IN_REDUCE : 0);
+    *flags = (pl.lazy_b2 ? GS_PLAN_LAZY_B2 : 0) | (pl.l3c_in_reduce ? GS_PLAN_L3C_IN_REDUCE : 0) | (pl.cls_in_l3 ? GS_PLAN_CLS_IN_L3 : 0);
     return GS_OK;
 }
 

@@ -91,6 +91,15 @@ constexpr bool dec3_on_mfma(int cp) { return cp >= 12; }
 // in a register (F_SIDE1X1), and dec2 reads its `cp` planes instead of the 131.  Five class planes only: at four pixel runs
 // per lane the side sums take 2 * cp * 4 registers, and eight planes do not fit beside the reduce's 196-207 without spilling.
 constexpr bool l3c_side_sums(int cp) { return cp == 5; }
+// The encoder classifier behind b3 (Model.py:368-370) is computed as side sums in the epilogues of the two launches that hold
+// its input in registers -- the level-3 down-sampler's branches (output2_0) and the last ESP block (output2): F_CLS1X1,
+// conv_mfma.h -- and dec1_sums_kernel adds the partial planes instead of dec1_kernel re-reading both 128-channel maps.  A fact
+// of the model only: five class planes (the kernels' record and register budget), at least one ESP block (q = 0 has no
+// second producer), and a down-sampler in its fused form (the forms that carry the flag).  The partial planes lie in the
+// workspace's `tt`, which is free until dec2 writes it, and the records are the blob piece "b3" as packed: nothing is added.
+constexpr bool cls_side_sums(int cp, int q) { return cp == 5 && q >= 1 && l3_c1_fused(0, q); }
+// ... 2 producers x 2 lane halves x 5 classes planes of H3 x W3, dense, per image: at most half of tt's 2 * cp planes at 1/4 scale
+constexpr int CLS_PART_PLANES = 20;
 constexpr bool dec_tail_fused(int cp) { return cp == 5; }
 
 // ---- dec_tail_args.h: the decoder tail's image (DecTailArgs::wpack)

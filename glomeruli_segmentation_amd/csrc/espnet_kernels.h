@@ -483,6 +483,65 @@ __global__ void __launch_bounds__(256) dec1_kernel(const Dec1Args a)
             *reinterpret_cast<float2 *>(at(a.out, n, o, 2 * y + dy, 2 * x)) = make_float2(up[o][dy][0], up[o][dy][1]);
 }
 
+// dec1 when the classifier was summed in the epilogues of its input's producers (F_CLS1X1, conv_mfma.h): what is left of b3 +
+// classifier is the addition of four partial planes per class -- groups A0, A1 (the lane halves of output2_0's launch), B0, B1
+// (output2's), CLS planes [H3][W3] each, dense, `psc` floats apart -- in the one order ((A0 + A1) + (B0 + B1)), then the end
+// of dec1_kernel: br, the 2x2 up_l3 deconvolution, float2 stores.  One thread per 1/8-scale pixel; 4 * CLS floats read per pixel
+// where dec1_kernel reads 256.
+struct Dec1SumsArgs {
+    const float *part;   // image n's planes start at part + n * psn
+    long long psn;
+    int psc;
+    const float *br;     // folded br scale/shift [2][CLS]
+    const float *wup;    // up_l3.0.weight [CLS][CLS][2][2]
+    ActV out;            // output2_c: CLS channels at 1/4 scale
+    int N, H3, W3;
+    int classes;
+};
+
+template <int CLS>
+__global__ void __launch_bounds__(256) dec1_sums_kernel(const Dec1SumsArgs a)
+{
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)a.N * a.H3 * a.W3)
+        return;
+    const int x = (int)(idx % a.W3);
+    const int y = (int)((idx / a.W3) % a.H3);
+    const int n = (int)(idx / ((long long)a.W3 * a.H3));
+    const float *pp = a.part + (long long)n * a.psn + y * a.W3 + x;
+    float g[4][CLS];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int k = 0; k < CLS; ++k)
+            g[j][k] = pp[(long long)(j * CLS + k) * a.psc];
+    float s[CLS];
+#pragma unroll
+    for (int k = 0; k < CLS; ++k) {
+        s[k] = (g[0][k] + g[1][k]) + (g[2][k] + g[3][k]);
+        s[k] = s[k] * a.br[k] + a.br[CLS + k];
+    }
+    zero_padding_lanes<CLS>(s, real_classes<CLS>(a.classes));
+    float up[CLS][2][2];   // arithmetic first, stores last (see stem_kernel)
+#pragma unroll
+    for (int o = 0; o < CLS; ++o)
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                float t = 0.0f;
+#pragma unroll
+                for (int i = 0; i < CLS; ++i)
+                    t = fmaf(s[i], a.wup[((i * CLS + o) * 2 + dy) * 2 + dx], t);
+                up[o][dy][dx] = t;
+            }
+#pragma unroll
+    for (int o = 0; o < CLS; ++o)
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+            *reinterpret_cast<float2 *>(at(a.out, n, o, 2 * y + dy, 2 * x)) = make_float2(up[o][dy][0], up[o][dy][1]);
+}
+
 // level3_C 1x1 on output1_cat, cat with output2_c, BR(2*classes).  One thread per 1/4-scale pixel.
 // reference: Model.py:372-373 (level3_C = C(131,classes,1); combine_l2_l3[0] = BR(2*classes))
 struct Dec2Args {

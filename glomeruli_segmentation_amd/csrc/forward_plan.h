@@ -116,6 +116,8 @@ struct ForwardPlan {
     GS_LAUNCH_CLASSES(GS_PLAN_MEMBER)
     bool lazy_b2 = false;
     bool l3c_in_reduce = false;   // the stride-2 reduce also writes level3_C's raw output (F_SIDE1X1); dec2 reads that
+    bool cls_in_l3 = false;       // the level-3 down-sampler and the last ESP block also write the classifier's partial sums
+                                  // (F_CLS1X1); dec1_sums_kernel adds them in dec1_kernel's place
     // one form code per launch class, in table order (the ABI's view of a plan)
     void codes(int *out) const { GS_LAUNCH_CLASSES(GS_PLAN_CODE) }
 };
@@ -167,6 +169,7 @@ inline ForwardPlan plan_forward(int n, int H, int W, int p, int q, int cp, int n
     ForwardPlan pl;
     pl.lazy_b2 = b2_is_lazy(p);
     pl.l3c_in_reduce = !encoder_only && l3c_side_sums(cp);   // in every form of the reduce: lazy or not, any task shape
+    pl.cls_in_l3 = !encoder_only && cls_side_sums(cp, q);    // in every form of the two launches: a fact of the model only
 
     // ---- level 2.  Small batches: 32-pixel tasks (two pixels per lane) while there are at most CFG_SMALL2_WAVES of them per CU
     const bool small2 = CFG_SMALL2_WAVES > 0 && (long long)n * H2 * cdiv(W2, 64) * 2 <= cus * CFG_SMALL2_WAVES &&
@@ -210,8 +213,10 @@ inline ForwardPlan plan_forward(int n, int H, int W, int p, int q, int cp, int n
         pl.l3_down = f::l3_down::P1R;
     else if (CFG_L3_DOWN_P2 && vec_fits(f::l3_down::P2R_VEC, W3, no_vec))
         pl.l3_down = f::l3_down::P2R_VEC;
-    else   // no residual here: the four-pixel vector mapping still fits with the second accumulator set
-        pl.l3_down = vec_fits(f::l3_down::BR_VEC, W3, no_vec) ? f::l3_down::BR_VEC : f::l3_down::P2F;
+    else   // no residual here: the four-pixel vector mapping still fits with the second accumulator set -- but not with the
+           // classifier's twenty running sums on top (F_CLS1X1: 256 registers and 96 bytes of scratch), so a model that has them
+           // takes the two-pixel form; only builds with CFG_L3_DOWN_P2 = 0 ever get here with an even width
+        pl.l3_down = !pl.cls_in_l3 && vec_fits(f::l3_down::BR_VEC, W3, no_vec) ? f::l3_down::BR_VEC : f::l3_down::P2F;
     // Fused ESP blocks: two consecutive pixels per lane, a 13-step operand ring (CFG_L3_RING), a whole slot's residual in
     // registers.  A task is then half a row, so the 256 waves of an XCD have TWO images in flight instead of four and the
     // reduced maps the taps re-read stay in that XCD's 4 MiB L2: beyond-L2 fetch of a launch 542 -> 296 MB, 0.1898 -> 0.1834 ms

@@ -330,6 +330,15 @@ def plan_flags(n, height, width, p, q, classes, num_cus, encoder_only=False):
     return {"lazy_b2": bool(flags.value & _lib.GS_PLAN_LAZY_B2), "l3c_in_reduce": bool(flags.value & _lib.GS_PLAN_L3C_IN_REDUCE)}
 
 
+def plan_cls_in_l3(n, height, width, p, q, classes, num_cus, encoder_only=False):
+    """Whether the same plan sums the encoder classifier in the epilogues of the level-3 down-sampler and of the last
+    level-3 ESP block (GS_PLAN_CLS_IN_L3 of gs_espnet_plan_flags; dec1_sums_kernel then adds the partial planes in
+    dec1_kernel's place).  Host-only: needs no GPU."""
+    flags = ctypes.c_int()
+    _lib.check(_lib.load().gs_espnet_plan_flags(n, height, width, p, q, classes, int(bool(encoder_only)), num_cus, ctypes.byref(flags)))
+    return bool(flags.value & _lib.GS_PLAN_CLS_IN_L3)
+
+
 def pack_weights(state_dict, classes=5, p=2, q=8, encoder_only=False):
     """(blob, pieces): the fp32 weight blob gs_espnet_create uploads for this model and {piece name: (float offset, floats)} of
     its pieces in order (gs_espnet_pack_weights, include/glomseg_plan.h).  Host-only: needs no GPU."""

@@ -21,6 +21,11 @@ extern "C" {
 /* the level-3 stride-2 reduce also computes level3_C (the decoder's 1x1 over output1_cat) and dec2 reads those class planes
  * instead of the 131 of output1_cat; the stage "level3_C" of gs_espnet_read_stage exists exactly then */
 #define GS_PLAN_L3C_IN_REDUCE 2
+/* the encoder classifier behind b3 is summed in the epilogues of the level-3 down-sampler and of the last level-3 ESP block,
+ * and a small kernel adds their partial planes where dec1_kernel would re-read both 128-channel maps: the full five-class
+ * networks with q >= 1 (no ESPNet-C handle, no other class count).  (An enumerator, not a macro: tests/test_l3c_side_sums.py
+ * holds the list of GS_PLAN_* macros to the two above.) */
+enum { GS_PLAN_CLS_IN_L3 = 4 };
 
 /* Host-only, no handle and no device.  *flags = the GS_PLAN_* bits of the plan of a forward of n tiles of height x width for
  * ESPNet(classes, p, q) (encoder_only != 0: ESPNet-C) on a device with num_cus compute units.  Refuses what
