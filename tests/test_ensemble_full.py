@@ -86,6 +86,9 @@ DEFAULT_CUS = 256
 NET_H, NET_W = 64, 128
 CROP_SIZES = [(64, 128), (150, 99), (33, 21), (301, 420), (40, 56)]
 CROP_MEMBERS = [(5, 3), (7, 2)]
+# members at trained-range PReLU / BatchNorm parameters (helpers/edge_weights.edge_state_dict: negative slopes, slopes above 1, negative and
+# zero BN weights; test_kernel_forms_edge.py): one row of FIVE_CASES and one of CLASS_CASES, under the same margin rule
+EDGE_MEMBER_CASES = [FIVE_CASES[6], CLASS_CASES[1]]
 
 
 def gain(classes):
@@ -97,6 +100,13 @@ def member(classes, k):
     sd = random_state_dict(P_Q[0], P_Q[1], classes=classes, seed=(5300 + k) if classes == 2 else (5000 + 37 * classes + k))
     sd["classifier.weight"] = (sd["classifier.weight"] * np.float32(gain(classes))).astype(np.float32)
     return sd, (120.0 + 5 * k, 130.0 - 3 * k, 110.0 + 2 * k), (60.0 + k, 55.0 + 2 * k, 70.0 - k)
+
+
+def edge_member(classes, k):
+    """member(classes, k) with the edge rewrite of its PReLU slopes and BatchNorm weights"""
+    from helpers.edge_weights import edge_state_dict
+    sd, mean, std = member(classes, k)
+    return edge_state_dict(sd), mean, std
 
 
 def case_tiles(h, w, n, classes, images=None):
@@ -325,6 +335,29 @@ def test_fp32_restatement_within_tau(fold_logits, case_logits):
     assert worst <= TAU / 2
 
 
+@pytest.mark.parametrize("h,w,n,classes,K", EDGE_MEMBER_CASES)
+def test_edge_member_conditions(h, w, n, classes, K):
+    """the edge-weight members' cases meet the conditions of the margin rule, and TAU's measurement holds for their logits too: from
+    the CPU oracle's logits alone"""
+    from oracle import espnet_oracle as orc
+    assert (h, w, n, classes, K) in FIVE_CASES + CLASS_CASES
+    lgs = []
+    for k in range(K):
+        sd, mean, std = edge_member(classes, k)
+        lgs.append(np.stack([orc.segment_tile(t, sd, mean, std, *P_Q)[0] for t in case_tiles(h, w, n, classes)]))
+    seen, excluded, worst = set(), 0, 0.0
+    for i in range(n):
+        li = [lg[i] for lg in lgs]
+        P = ens_ref(li)
+        worst = max(worst, float(np.abs(ens_ref32(li).astype(np.float64) - P).max()))
+        seen |= set(np.unique(P.argmax(0)).tolist())
+        excluded += int(margin_set(P).sum())
+    print("edge members %dx%d n=%d classes=%d K=%d: |P32 - P64| <= %.3g, classes in the truth %s, margin set %d of %d pixels"
+          % (h, w, n, classes, K, worst, sorted(seen), excluded, n * h * w))
+    check_conditions(seen, excluded, n * h * w, classes, "edge members %dx%d c%d K%d" % (h, w, classes, K))
+    assert worst <= MEASURED_WORST
+
+
 def mutated(logits, weight=None, own_last=False, pad_plane=False):
     """P float64 of a WRONG ensemble: weight [K, H, W] multiplies member k's probabilities per pixel (2: added twice, 0: left out);
     own_last: the last member's softmax alone; pad_plane: a zero logit of a padding plane takes part in every softmax"""
@@ -440,6 +473,21 @@ def test_other_class_counts(torch_mod, members, h, w, n, classes, K):
     """dec4_kernel<CLS, true> at every padded class count (4, 8, 12, 16, 20: four, two and one half-resolution pixels per thread),
     with a ragged last workgroup; the padding planes stay out of the softmax; K = 1, 2, 3 and 8"""
     run_case(torch_mod, members, h, w, n, classes, K)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("h,w,n,classes,K", EDGE_MEMBER_CASES)
+def test_edge_weight_members(torch_mod, h, w, n, classes, K):
+    """the exchanging five-class tail and dec4_kernel<8, true> with members whose PReLU slopes run from -1 to 1.7 and whose BatchNorm
+    weights are negative or zero on a third of the channels: the same margin rule against the members' own logits"""
+    from glomeruli_segmentation_amd.engine import EspnetEngine
+    ms = [edge_member(classes, k) for k in range(K)]
+    engs = [EspnetEngine(sd, classes=classes, p=P_Q[0], q=P_Q[1]) for sd, _, _ in ms]
+    try:
+        run_case(torch_mod, lambda c, k: (engs, [(mean, std) for _, mean, std in ms]), h, w, n, classes, K)
+    finally:
+        for e in engs:
+            e.close()
 
 
 def device_cus(torch):

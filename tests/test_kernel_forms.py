@@ -283,7 +283,13 @@ def case_weights(case):
         mean, std = FOLD_MEAN_STD[1]
         return load_weights(1), mean, std
     mean, std = RANDOM_MEAN_STD
-    return random_state_dict(case.p, case.q, classes=case.classes, seed=4000 + case_key(case)), mean, std
+    sd = random_state_dict(case.p, case.q, classes=case.classes, seed=4000 + case_key(case))
+    if case.weights == "edge":      # trained-range and limit PReLU slopes, negative and zero BN weights (helpers/edge_weights.py)
+        from helpers.edge_weights import edge_state_dict
+        sd = edge_state_dict(sd)
+    else:
+        assert case.weights == "random", case.weights
+    return sd, mean, std
 
 
 def case_tile(case, k):
@@ -397,13 +403,14 @@ class DeviceCase:
     logits and off the float64 argmax only where its top-2 margin is below the logit bound, the counts its bincount; the
     mask-only kernels give the same mask and counts."""
 
-    def __init__(self, case):
+    def __init__(self, case, weights=None):
+        """weights: (state dict, mean, std) in place of case_weights(case) (test_kernel_forms_edge.py's tied weights)"""
         import torch
         from glomeruli_segmentation_amd.engine import EspnetEngine
         assert torch.cuda.is_available(), "the gpu-marked tests need a HIP device"
         self.torch, self.case = torch, case
         self.num_cus = torch.cuda.get_device_properties(0).multi_processor_count
-        self.sd, self.mean, self.std = case_weights(case)
+        self.sd, self.mean, self.std = weights or case_weights(case)
         self.eng = EspnetEngine(self.sd, classes=case.classes, p=case.p, q=case.q)
 
     def __enter__(self):
