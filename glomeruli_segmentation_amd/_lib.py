@@ -175,6 +175,12 @@ MATCH_PROTOTYPES = {
     "gs_instance_match": (_I, [_P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
 }
 
+# every symbol include/glomseg_boundary_dist.h declares (additions to ABI 10 with a header of their own)
+BOUNDARY_PROTOTYPES = {
+    "gs_boundary_dist_plan": (_I, [_I, _I, ctypes.POINTER(ctypes.c_size_t)]),
+    "gs_instance_boundary_dist": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -190,7 +196,7 @@ def load():
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     for name, (res, args) in list(PROTOTYPES.items()) + list(SCORING_PROTOTYPES.items()) + list(PLAN_PROTOTYPES.items()) + \
-            list(INSTANCE_PROTOTYPES.items()) + list(MATCH_PROTOTYPES.items()):
+            list(INSTANCE_PROTOTYPES.items()) + list(MATCH_PROTOTYPES.items()) + list(BOUNDARY_PROTOTYPES.items()):
         if name in PLAN_PROTOTYPES and not hasattr(lib, name):
             continue   # (an ABI 9 library from before glomseg_plan.h, loaded for an A/B: engine.plan_flags then raises)
         fn = getattr(lib, name)   # AttributeError if the symbol is not exported

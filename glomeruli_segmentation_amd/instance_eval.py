@@ -10,7 +10,11 @@ so there is no assignment to solve.  All of it is integer arithmetic; the ratios
 integers.
 
     python -m glomeruli_segmentation_amd.instance_eval --eval_dir DIR --output_csv FILE --summary_tsv FILE
-           [--classes 5] [--connectivity 8] [--iou_threshold 0.5] [--gpu_id 0]
+           [--classes 5] [--connectivity 8] [--iou_threshold 0.5] [--gpu_id 0] [--boundary]
+
+--boundary adds, per matched pair, how far the two outlines lie apart (include/glomseg_boundary_dist.h, csrc/boundary_dist.hip:
+exact squared distances between the boundary pixels of the pair, on the GPU): the Hausdorff distance, its 95th percentile, the
+average surface distance and the root mean square, in map pixels.
 """
 import csv
 import ctypes
@@ -28,6 +32,8 @@ from . import instances
 GT_SUFFIX, PRED_SUFFIX = "_gt_classmap.png", "_pred_classmap.png"           # what wsi_eval writes
 IOU_DEN_MAX = 65535
 SUMMARY_KEYS = ["gt", "pred", "tp", "fp", "fn", "precision", "recall", "f1", "mean_iou", "pq", "mean_dice"]
+BOUNDARY_COLUMNS = ["hd", "hd95", "assd", "rmsd"]                            # --boundary: behind a TP row, in map pixels
+BOUNDARY_SUMMARY_KEYS = ["mean_hd", "mean_hd95", "mean_assd"]                # ... and behind the summary
 
 
 def check_threshold(iou):
@@ -64,12 +70,87 @@ def _device_map(m):
     return m.contiguous()
 
 
-def match_instances(gt_map, pred_map, classes=5, connectivity=8, iou=(1, 2), pair_cap=4096):
+def boundary_workspace_bytes(height, width):
+    """gs_boundary_dist_plan: host-only"""
+    need = ctypes.c_size_t(0)
+    _lib.check(_lib.load().gs_boundary_dist_plan(int(height), int(width), ctypes.byref(need)))
+    return need.value
+
+
+def boundary_ratios(stats, samples):
+    """stats: int64 [n_gt,2,3] {boundary pixels, max d2, sum of d2} per direction; samples: per direction (ids, d2), the gt id and
+    the d2 of every boundary pixel that has one, sorted ascending by (id, d2) -> {"hd", "hd95", "assd", "rmsd"}: float64 [n_gt],
+    nan where the instance has no sample in either direction (unmatched).  numpy on the host, from the exact integers:
+    hd = sqrt(max d2 over both directions); hd95 = sqrt of the larger of the two directions' nearest-rank 95th percentiles
+    (element (95 * n + 99) // 100, 1-based, of the direction's sorted d2); assd = sum of sqrt(d2) / (n0 + n1);
+    rmsd = sqrt(sum of d2 / (n0 + n1))."""
+    stats = np.asarray(stats, dtype=np.int64).reshape(-1, 2, 3)
+    n_gt = len(stats)
+    n = stats[:, :, 0]
+    have = (n[:, 0] > 0) & (n[:, 1] > 0)
+    p95 = np.zeros((n_gt, 2), dtype=np.int64)
+    root_sum = np.zeros(n_gt, dtype=np.float64)
+    for d, (ids, d2) in enumerate(samples):
+        ids, d2 = np.asarray(ids, dtype=np.int64), np.asarray(d2, dtype=np.int64)
+        if len(ids) != int(n[:, d].sum()) or np.any(np.bincount(ids - 1, minlength=n_gt)[:n_gt] != n[:, d]):
+            raise ValueError("direction %d: the samples are not the boundary pixels stats counts" % d)
+        start = np.cumsum(n[:, d]) - n[:, d]
+        rank = (95 * n[:, d] + 99) // 100                                      # 1-based, 1..n where n >= 1
+        some = n[:, d] > 0
+        p95[some, d] = d2[(start + rank - 1)[some]]
+        np.add.at(root_sum, ids - 1, np.sqrt(d2.astype(np.float64)))
+    total = np.where(have, n.sum(axis=1), 1).astype(np.float64)
+    nan = np.full(n_gt, np.nan)
+    return {"hd": np.where(have, np.sqrt(stats[:, :, 1].max(axis=1).astype(np.float64)), nan),
+            "hd95": np.where(have, np.sqrt(p95.max(axis=1).astype(np.float64)), nan),
+            "assd": np.where(have, root_sum / total, nan),
+            "rmsd": np.where(have, np.sqrt(stats[:, :, 2].sum(axis=1).astype(np.float64) / total), nan)}
+
+
+def boundary_distances(result):
+    """result: what match_instances returns (labels and match arrays on the device) -> {"stats": int64 [n_gt,2,3] {boundary
+    pixels, max d2, sum of d2} by (gt id - 1, direction), "dist_gt", "dist_pred": int32 [h,w], d2 at the boundary pixels of the
+    matched instances and -1 elsewhere (tensors on the labels' device), "hd", "hd95", "assd", "rmsd": float64 [n_gt] numpy arrays,
+    nan where unmatched (boundary_ratios), in map pixels}.  The integers are gs_instance_boundary_dist's; the per-pair
+    distributions are read off its two maps with torch on the device (mask, sort by (id, d2)) and the ratios taken on the host."""
+    import torch
+    lib = _lib.load()
+    lg, lp = result["gt"]["labels"], result["pred"]["labels"]
+    if lg is None or lp is None or not getattr(lg, "is_cuda", False) or not getattr(lp, "is_cuda", False):
+        raise ValueError("boundary_distances needs match_instances' result with its label maps on the GPU")
+    dev = lg.device
+    h, w = lg.shape
+    n_gt, n_pred = int(result["gt"]["n"]), int(result["pred"]["n"])
+    lg, lp = lg.contiguous(), lp.contiguous()
+    match_gt, match_pred = result["match_gt"].contiguous(), result["match_pred"].contiguous()
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ws = torch.empty(boundary_workspace_bytes(h, w), dtype=torch.uint8, device=dev)
+        dist_gt = torch.empty((h, w), dtype=torch.int32, device=dev)
+        dist_pred = torch.empty((h, w), dtype=torch.int32, device=dev)
+        stats = torch.empty((n_gt, 2, 3), dtype=torch.int64, device=dev)
+        _lib.check(lib.gs_instance_boundary_dist(lg.data_ptr(), lp.data_ptr(), match_gt.data_ptr() if n_gt else None, n_gt,
+                                                 match_pred.data_ptr() if n_pred else None, n_pred, h, w, ws.data_ptr(), ws.numel(),
+                                                 dist_gt.data_ptr(), dist_pred.data_ptr(), stats.data_ptr() if n_gt else None, stream))
+        samples = []
+        for dist, labels, partner in ((dist_gt, lg, None), (dist_pred, lp, match_pred)):
+            mask = dist >= 0
+            ids, d2 = labels[mask].to(torch.int64), dist[mask].to(torch.int64)
+            if partner is not None:
+                ids = partner.to(torch.int64)[ids - 1]                         # a pixel with a d2 belongs to a matched prediction
+            key = torch.sort(ids << 31 | d2).values                            # d2 < 2^31
+            samples.append(((key >> 31).cpu().numpy(), (key & 0x7FFFFFFF).cpu().numpy()))
+        out = {"stats": stats, "dist_gt": dist_gt, "dist_pred": dist_pred}
+        out.update(boundary_ratios(stats.cpu().numpy(), samples))
+    return out
+
+
+def match_instances(gt_map, pred_map, classes=5, connectivity=8, iou=(1, 2), pair_cap=4096, boundary=False):
     """gt_map, pred_map: uint8 [h,w] of one size, CUDA tensors or numpy arrays (uploaded to the current device).
     -> {"gt", "pred": instances.label_instances' tables with labels, "pairs" int32 [n,2] (gt id, pred id; ascending),
         "inter", "agree" int64 [n], "match_gt" int32 [n_gt] (matched pred id or 0), "match_pred" int32 [n_pred], "iou": (num, den)},
     tensors on the maps' device.  On overflow of the pair table it runs again with pair_cap doubled: two maps have no more
-    distinct pairs than pixels, so that ends."""
+    distinct pairs than pixels, so that ends.  boundary=True adds boundary_distances' result under "boundary"."""
     import torch
     lib = _lib.load()
     num, den = check_threshold(iou)
@@ -104,16 +185,19 @@ def match_instances(gt_map, pred_map, classes=5, connectivity=8, iou=(1, 2), pai
                                          counts_gt.data_ptr() if gt["n"] else None, gt["n"],
                                          counts_pred.data_ptr() if pred["n"] else None, pred["n"], int(classes), num, den,
                                          match_gt.data_ptr() if gt["n"] else None, match_pred.data_ptr() if pred["n"] else None, stream))
-    return {"gt": gt, "pred": pred, "pairs": pairs[:n], "inter": inter[:n, 0], "agree": inter[:n, 1], "match_gt": match_gt,
-            "match_pred": match_pred, "iou": (num, den)}
+    result = {"gt": gt, "pred": pred, "pairs": pairs[:n], "inter": inter[:n, 0], "agree": inter[:n, 1], "match_gt": match_gt,
+              "match_pred": match_pred, "iou": (num, den)}
+    if boundary:
+        result["boundary"] = boundary_distances(result)
+    return result
 
 
-def header(classes=5):
-    """the columns of instance_rows: the class names are instances.header's"""
+def header(classes=5, boundary=False):
+    """the columns of instance_rows: the class names are instances.header's; boundary: BOUNDARY_COLUMNS behind them"""
     names = instances.header(classes)[7:]
     return (['slide', 'kind', 'gt_id', 'gt_xmin', 'gt_ymin', 'gt_xmax', 'gt_ymax', 'gt_area', 'pred_id', 'pred_xmin', 'pred_ymin',
              'pred_xmax', 'pred_ymax', 'pred_area', 'inter', 'iou', 'dice', 'class_agreement']
-            + ['gt_' + c for c in names] + ['pred_' + c for c in names])
+            + ['gt_' + c for c in names] + ['pred_' + c for c in names] + (BOUNDARY_COLUMNS if boundary else []))
 
 
 def _host(v):
@@ -124,9 +208,12 @@ def on_host(result):
     """the result as numpy arrays, without the label maps: what instance_rows and summary need of it"""
     def side(t):
         return {"n": t["n"], "boxes": _host(t["boxes"]), "counts": _host(t["counts"]), "labels": None}
-    return {"gt": side(result["gt"]), "pred": side(result["pred"]), "pairs": _host(result["pairs"]), "inter": _host(result["inter"]),
-            "agree": _host(result["agree"]), "match_gt": _host(result["match_gt"]), "match_pred": _host(result["match_pred"]),
-            "iou": result["iou"]}
+    out = {"gt": side(result["gt"]), "pred": side(result["pred"]), "pairs": _host(result["pairs"]), "inter": _host(result["inter"]),
+           "agree": _host(result["agree"]), "match_gt": _host(result["match_gt"]), "match_pred": _host(result["match_pred"]),
+           "iou": result["iou"]}
+    if "boundary" in result:                       # without the two maps: the rows and the summary need the ratios only
+        out["boundary"] = {k: _host(result["boundary"][k]) for k in ["stats"] + BOUNDARY_COLUMNS}
+    return out
 
 
 def _tables(result):
@@ -146,10 +233,14 @@ def _matched(result):
     return [(g, p, sum(gc[g - 1]), sum(pc[p - 1])) + table[(g, p)] for g, p in enumerate(match_gt, 1) if p]
 
 
-def instance_rows(result, key):
+def instance_rows(result, key, boundary=False):
     """header(classes) names the columns.  One row per ground-truth instance, kind TP (matched) or FN, then one per unmatched
     prediction, kind FP.  The columns of the absent side are empty; inter, IoU, Dice and class agreement (agree / inter) belong
-    to a TP row."""
+    to a TP row.  boundary: header(classes, True)'s four columns from result["boundary"] behind a TP row, empty elsewhere."""
+    if boundary:
+        b = result["boundary"]
+        ratios = [[float(b[k][g]) for k in BOUNDARY_COLUMNS] for g in range(len(_host(result["match_gt"])))]
+        return [row + (ratios[row[2] - 1] if row[1] == 'TP' else [''] * len(BOUNDARY_COLUMNS)) for row in instance_rows(result, key)]
     gb, gc, pb, pc, table, match_gt, match_pred = _tables(result)
     width = len(gc[0]) if gc else (len(pc[0]) if pc else 1)
     none_side, none_classes = [''] * 6, [''] * (width - 1)
@@ -198,8 +289,21 @@ def summary(results):
             "mean_iou": mean_iou, "pq": pq, "mean_dice": mean_dice}
 
 
+def boundary_summary(results):
+    """one result with "boundary", or a list of them pooled -> mean_hd, mean_hd95, mean_assd over the matched pairs, float64;
+    nan without a matched pair"""
+    if isinstance(results, dict):
+        results = [results]
+    out = {}
+    for name, k in zip(BOUNDARY_SUMMARY_KEYS, BOUNDARY_COLUMNS):
+        v = np.concatenate([np.asarray(_host(r["boundary"][k]), dtype=np.float64).reshape(-1) for r in results] + [np.zeros(0)])
+        v = v[~np.isnan(v)]
+        out[name] = float(np.sum(v) / len(v)) if len(v) else float('nan')
+    return out
+
+
 def summary_row(key, s):
-    return [key] + [s[k] for k in SUMMARY_KEYS]
+    return [key] + [s[k] for k in SUMMARY_KEYS] + [s[k] for k in BOUNDARY_SUMMARY_KEYS if k in s]
 
 
 def build_parser():
@@ -211,6 +315,8 @@ def build_parser():
     p.add_argument('--connectivity', type=int, default=8, choices=[4, 8])
     p.add_argument('--iou_threshold', default='0.5', help='a decimal or a fraction, at least 1/2; a pair matches strictly above it')
     p.add_argument('--gpu_id', type=int, default=0)
+    p.add_argument('--boundary', action='store_true', help='add the boundary distances of every matched pair, in map pixels: the columns '
+                   'hd, hd95, assd, rmsd behind the TP rows and mean_hd, mean_hd95, mean_assd behind the summary')
     return p
 
 
@@ -247,21 +353,26 @@ def main(argv=None, out=sys.stdout):
             gt, pred = read(gt_path), read(pred_path)
             if gt.shape != pred.shape:
                 raise ValueError("%s is %d x %d but %s is %d x %d" % ((pred_path,) + pred.shape[::-1] + (gt_path,) + gt.shape[::-1]))
-            res = match_instances(gt, pred, classes=args.classes, connectivity=args.connectivity, iou=iou)
+            res = match_instances(gt, pred, classes=args.classes, connectivity=args.connectivity, iou=iou, boundary=args.boundary)
             res = on_host(res)
             results.append(res)
-            rows += instance_rows(res, slide)
+            rows += instance_rows(res, slide, boundary=args.boundary)
             s = summary(res)
+            if args.boundary:
+                s.update(boundary_summary(res))
             lines.append(summary_row(slide, s))
             print("{}: {} annotated, {} predicted, {} matched".format(slide, s["gt"], s["pred"], s["tp"]), file=out)
-    lines.append(summary_row("all", summary(results)))
+    s = summary(results)
+    if args.boundary:
+        s.update(boundary_summary(results))
+    lines.append(summary_row("all", s))
     with open(args.output_csv, 'w') as f:
         writer = csv.writer(f)
-        writer.writerow(header(args.classes))
+        writer.writerow(header(args.classes, args.boundary))
         writer.writerows(rows)
     with open(args.summary_tsv, 'w') as f:
         writer = csv.writer(f, delimiter='\t')
-        writer.writerow(['slide'] + SUMMARY_KEYS)
+        writer.writerow(['slide'] + SUMMARY_KEYS + (BOUNDARY_SUMMARY_KEYS if args.boundary else []))
         writer.writerows(lines)
     return 0
 
