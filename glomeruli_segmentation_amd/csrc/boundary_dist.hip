@@ -32,22 +32,20 @@
 // never inside launch 2; the zeroes of launch 1 are in memory before the first atomic of launch 3.  Inside launches 3 and 4 stats
 // is touched only through agent-scope 64-bit atomics (add, max), which execute at the memory side: no lane reads stats at all.
 //
-// Rules (those of instances.hip and instance_match.hip): no kernel waits on another workgroup (no flags, no tickets, no spin
-// loop); every loop has a monotone bound --
+// Rules: those of wave_block.h, whose grouping loop ends launches 3 and 4.  The loops of this file's own --
 //   the row pass      x0 rises (falls) by 256 per round until it leaves [0, width)
 //   the row walk      k rises by one per round and stops at k*k >= best, at height, or when both rows y-k and y+k lie outside
 //   a hop sequence    the column strictly falls (left) or rises (right) with every hop: a link at c-1 is at most c-1, one at
 //                     c+1 at least c+1; it ends at none, at the row's end, at the partner or at dx*dx + k*k >= best: at most
 //                     width hops
-//   the grouping      every round retires at least one lane of the wave
-// -- counters are written with ordinary vector atomics; the entry allocates nothing and writes every byte of the workspace
-// that it later reads.  A link is a column the row pass itself stored (< width) or 0xFFFF, so no link leads out of its row, and
-// an id is used as an index only after its range test.
+// A link is a column the row pass itself stored (< width) or 0xFFFF, so no link leads out of its row, and an id is used as an
+// index only after its range test.
 //
 // Inconsistent match arrays.  A pair is believed only when both arrays agree and both ids are in range; a partner that owns no
 // boundary pixel makes the search walk every link of the map once (bounded by height * width) and end with no d2: -1, no stats.
 #include "gs_internal.h"
 #include "boundary_dist_plan.h"
+#include "wave_block.h"
 #include "../../include/glomseg_boundary_dist.h"
 
 #include <climits>
@@ -220,15 +218,9 @@ __global__ __launch_bounds__(kThreads) void bdist_query_kernel(const int *__rest
         if (dist)
             dist[i] = d2;
     }
-    // every lane of the wave gets here.  Lanes that share g are retired together, as in match_pixel_kernel; a slide-map wave
-    // holds one or two glomeruli.
-    const bool todo = d2 >= 0;
-    u64 rem = __ballot(todo);
-    while (rem) {                                  // wave-uniform; every round retires at least one lane
-        const int first = __ffsll((long long)rem) - 1;
+    // every lane of the wave gets here.  Lanes that share g are retired together; a slide-map wave holds one or two glomeruli.
+    for_each_wave_group(d2 >= 0, g, [&](int first, u64 grp, bool mine) {
         const int g0 = __shfl(g, first);
-        const bool mine = todo && g == g0;
-        const u64 grp = __ballot(mine);
         u64 sum = mine ? (u64)d2 : 0;
         unsigned mx = mine ? (unsigned)d2 : 0;
 #pragma unroll
@@ -245,11 +237,8 @@ __global__ __launch_bounds__(kThreads) void bdist_query_kernel(const int *__rest
             if (sum)
                 __hip_atomic_fetch_add(row + 2, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        rem &= ~grp;
-    }
+    });
 }
-
-inline bool aligned(const void *p, uintptr_t a) { return p && ((uintptr_t)p & (a - 1)) == 0; }
 
 }  // namespace
 
@@ -275,7 +264,7 @@ extern "C" gs_status gs_instance_boundary_dist(const int32_t *labels_gt, const i
     gs_status st = plan_boundary_dist(height, width, plan);
     if (st != GS_OK)
         return st;
-    st = check_boundary_dist(n_gt, n_pred);
+    st = check_instance_counts("gs_instance_boundary_dist", n_gt, n_pred);
     if (st != GS_OK)
         return st;
     GS_REQUIRE(aligned(labels_gt, 4) && aligned(labels_pred, 4),

@@ -51,6 +51,8 @@ inline gs_status grow(T *&buf, size_t &have, size_t need, const char *what)
 }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// p is not NULL and a multiple of a, a power of two
+static inline bool aligned(const void *p, uintptr_t a) { return p && ((uintptr_t)p & (a - 1)) == 0; }
 
 // NHWC convolution (csrc/detect_ops.hip); ho / wo are filled in by the launcher.
 struct ConvNhwcArgs {

@@ -28,11 +28,9 @@
 // is read with a relaxed agent-scope load only to stop early: an old 0 costs time, never correctness.  Across launches
 // visibility comes from the kernel boundary alone.
 //
-// Rules (those of instances.hip): no kernel waits on another workgroup (no flags, tickets or look-back scan: the scan is
-// two-level, launches 3 to 5); every loop has a monotone bound -- a probe sequence visits at most `slots` slots and then
-// raises the overflow word, a probe sequence in LDS gives up after kLocalProbes slots, the wave's grouping loop retires at
-// least one lane per round, the rank loop walks the dense list once -- so there is no spin loop; counters are written with ordinary vector atomics; the entries allocate nothing and write
-// every byte of workspace and output that they later read.
+// Rules: those of wave_block.h, whose count / scan / rank are launches 3 to 5 and whose grouping loop launch 2 spells out.  The loops
+// of this file's own: a probe sequence visits at most `slots` slots and then raises the overflow word, a probe sequence in LDS
+// gives up after kLocalProbes slots, the rank loop walks the dense list once.
 //
 // Overflow.  A claim takes a ticket from state[0]; the claim that finds `cap` tickets already out raises state[1], and so does a
 // probe sequence that runs out.  Threads that see state[1] set insert nothing more, so the table stays about half empty and
@@ -40,6 +38,7 @@
 // total above cap) into n_pairs = {0, 1}; launches 5 and 6 then store nothing.
 #include "gs_internal.h"
 #include "instance_match_plan.h"
+#include "wave_block.h"
 #include "../../include/glomseg_instance_match.h"
 
 namespace gs {
@@ -49,9 +48,8 @@ namespace {
 typedef unsigned long long u64;
 
 constexpr int kThreads = kMatchThreads;
-constexpr int kScanThreads = 1024;
 constexpr int kLocalSlots = 64, kLocalProbes = 4;   // the pixel pass's table in LDS: a slide-map tile holds one or two pairs
-static_assert(kThreads % 64 == 0 && kThreads == 256 && kMatchTileW == 64 && kLocalSlots <= kThreads, "block indexing below");
+static_assert(kThreads == kFlagThreads && kMatchTileW == 64 && kLocalSlots <= kThreads, "block indexing below; block_flag_count / _rank");
 static_assert((kLocalSlots & (kLocalSlots - 1)) == 0 && (long long)kMatchTileW * kMatchTileH < (1ll << 32), "local table");
 
 // murmur3's 64-bit finaliser: every output bit depends on both halves of the key, so neither pairs that share g with
@@ -126,7 +124,7 @@ __device__ inline bool local_add(u64 *lkey, unsigned *lcnt, u64 key, unsigned n_
 }
 
 // One workgroup per 64 x 64 tile, a wave per row of it at a time: 64 consecutive pixels, on a slide map nearly always all of one
-// pair or of none.  The lanes are retired group by group (one key each) as in inst_reduce_kernel; the group's first lane keeps
+// pair or of none.  The lanes are retired group by group (one key each); the group's first lane keeps
 // the group's two popcounts, and after the loop the first lanes of all groups add them to the workgroup's table side by side.
 // At the end the workgroup adds what its table holds to the global one: a tile inside one glomerulus costs one global update
 // instead of 64 (measured without this stage, tools/instance_match_rate.py: 0.24 ms on the 5000 x 5000 disc pair against
@@ -157,6 +155,9 @@ __global__ __launch_bounds__(kThreads) void match_pixel_kernel(const int *__rest
                 same = mg[i] == mp[i];             // the class bytes are read only where both labels are set
             }
         }
+        // for_each_wave_group (wave_block.h) written out, with the key as its two halves: on the 64-bit key the helper measured
+        // 0.0757 and 0.0781 ms on the disc pair against the limit of 0.0758 (profiles/slide_map_shared_ab.json), so this site
+        // keeps the instructions it had.  The helper's argument holds word for word.
         const bool todo = g != 0;
         unsigned n_inter = 0, n_agree = 0;         // set in the first lane of a group
         u64 rem = __ballot(todo);
@@ -182,48 +183,19 @@ __global__ __launch_bounds__(kThreads) void match_pixel_kernel(const int *__rest
 // 3 ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void match_count_kernel(const u64 *__restrict__ keys, int *__restrict__ block_count)
 {
-    __shared__ int wave_n[kThreads / 64];
     const u64 i = (u64)blockIdx.x * kThreads + threadIdx.x;          // < slots: slots is a multiple of kThreads
-    const u64 m = __ballot(keys[i] != 0);
-    if ((threadIdx.x & 63) == 0)
-        wave_n[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < kThreads / 64; ++w)
-            s += wave_n[w];
-        block_count[blockIdx.x] = s;
-    }
+    block_flag_count(keys[i] != 0, block_count);
 }
 
 // 4 ------------------------------------------------------------------------------------------------------------------------
-// One workgroup, as inst_scan_kernel.  The total is the number of distinct pairs in the table (<= pixels: it fits an int).
+// The total is the number of distinct pairs in the table (<= pixels: it fits an int).
 __global__ __launch_bounds__(kScanThreads) void match_scan_kernel(int *__restrict__ block_count, int n_blocks, const unsigned *__restrict__ state,
                                                                    int cap, int *__restrict__ n_pairs)
 {
-    __shared__ int s[kScanThreads];
-    const int t = (int)threadIdx.x, run = (n_blocks + kScanThreads - 1) / kScanThreads;
-    const long long lo = (long long)t * run, hi = lo + run < n_blocks ? lo + run : n_blocks;
-    int sum = 0;
-    for (long long b = lo; b < hi; ++b)
-        sum += block_count[b];
-    s[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < kScanThreads; d <<= 1) {
-        const int v = t >= d ? s[t - d] : 0;
-        __syncthreads();
-        s[t] += v;
-        __syncthreads();
-    }
-    int base = s[t] - sum;
-    for (long long b = lo; b < hi; ++b) {
-        const int c = block_count[b];
-        block_count[b] = base;
-        base += c;
-    }
-    if (t == kScanThreads - 1) {
-        const bool overflow = state[1] != 0 || s[t] > cap;
-        n_pairs[0] = overflow ? 0 : s[t];
+    const int total = block_scan_exclusive(block_count, n_blocks);
+    if (threadIdx.x == kScanThreads - 1) {
+        const bool overflow = state[1] != 0 || total > cap;
+        n_pairs[0] = overflow ? 0 : total;
         n_pairs[1] = overflow ? 1 : 0;
     }
 }
@@ -233,20 +205,10 @@ __global__ __launch_bounds__(kThreads) void match_compact_kernel(const u64 *__re
                                                                   const int *__restrict__ n_pairs, u64 *__restrict__ dense_key,
                                                                   unsigned *__restrict__ dense_slot)
 {
-    __shared__ int wave_n[kThreads / 64];
     const u64 i = (u64)blockIdx.x * kThreads + threadIdx.x;
     const u64 key = keys[i];
-    const u64 m = __ballot(key != 0);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0)
-        wave_n[wave] = __popcll(m);
-    __syncthreads();
-    if (key == 0)
-        return;
-    int pos = block_base[blockIdx.x] + __popcll(m & ((1ull << lane) - 1));
-    for (int w = 0; w < wave; ++w)
-        pos += wave_n[w];
-    if (pos < n_pairs[0]) {                        // {0, 1} on overflow: nothing is stored
+    const int pos = block_flag_rank(key != 0, block_base);
+    if (key != 0 && pos < n_pairs[0]) {            // {0, 1} on overflow: nothing is stored
         dense_key[pos] = key;
         dense_slot[pos] = (unsigned)i;
     }
@@ -321,8 +283,6 @@ __global__ __launch_bounds__(kThreads) void match_test_kernel(const int *__restr
         match_pred[p - 1] = g;
     }
 }
-
-inline bool aligned(const void *p, uintptr_t a) { return p && ((uintptr_t)p & (a - 1)) == 0; }
 
 }  // namespace
 

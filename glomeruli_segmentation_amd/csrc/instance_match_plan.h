@@ -1,17 +1,13 @@
 // Workspace plan of gs_instance_overlaps (csrc/instance_match.hip): what the entry refuses about sizes, the capacity of the
-// pair table and where its parts lie in the caller's workspace.  Host-only and free of HIP (espnet_facts.h), as instance_plan.h
-// is: gs_instance_match_plan (include/glomseg_instance_match.h) answers without a device, and the launcher lays the workspace
-// out with the same function.
+// pair table and where its parts lie in the caller's workspace.  Host-only and free of HIP (slide_map_plan.h, which has the
+// shared refusals and the layout): gs_instance_match_plan (include/glomseg_instance_match.h) answers without a device, and the
+// launcher lays the workspace out with the same function.
 #pragma once
-#include <climits>
-#include <cstddef>
-
-#include "espnet_facts.h"
+#include "slide_map_plan.h"
 
 namespace gs {
 
 constexpr int kMatchThreads = 256;          // threads of every launch; also the slots / pairs a counting block covers
-constexpr size_t kMatchAlign = 256;
 constexpr size_t kMatchMinSlots = 256;      // one whole counting block at least
 constexpr int kMatchTileW = 64, kMatchTileH = 64;   // the pixel pass's tile: one workgroup, a wave per row of 64 pixels at a time
 
@@ -31,23 +27,22 @@ struct InstanceMatchPlan {
     size_t bytes = 0;
 };
 
-inline size_t match_align(size_t v) { return (v + kMatchAlign - 1) / kMatchAlign * kMatchAlign; }
+inline gs_status check_pair_cap(const char *entry, int pair_cap)
+{
+    if (pair_cap >= 1)
+        return GS_OK;
+    set_error("%s: pair_cap must be at least 1 (got %d)", entry, pair_cap);
+    return GS_ERR_INVALID;
+}
 
 inline gs_status plan_instance_match(int height, int width, int pair_cap, InstanceMatchPlan &out)
 {
     out = InstanceMatchPlan();
-    if (height <= 0 || width <= 0) {
-        set_error("gs_instance_overlaps: height and width must be positive (got %d x %d)", height, width);
-        return GS_ERR_INVALID;
-    }
-    if (pair_cap < 1) {
-        set_error("gs_instance_overlaps: pair_cap must be at least 1 (got %d)", pair_cap);
-        return GS_ERR_INVALID;
-    }
-    if ((long long)height * (long long)width > (long long)INT_MAX) {
-        set_error("gs_instance_overlaps: maps of %d x %d have more than 2^31 - 1 pixels", height, width);
-        return GS_ERR_UNSUPPORTED;
-    }
+    const char *entry = "gs_instance_overlaps";
+    gs_status st;
+    if ((st = check_map_sides(entry, height, width)) != GS_OK || (st = check_pair_cap(entry, pair_cap)) != GS_OK ||
+        (st = check_map_pixels(entry, height, width)) != GS_OK)
+        return st;
     out.n_pixels = height * width;
     out.tiles_x = (width - 1) / kMatchTileW + 1;      // (no width + 63: a width near INT_MAX is allowed)
     out.tiles_y = (height - 1) / kMatchTileH + 1;
@@ -56,38 +51,25 @@ inline gs_status plan_instance_match(int height, int width, int pair_cap, Instan
     while (out.slots < 2 * (size_t)out.cap)          // ends at 2^32 at the latest: 2 * cap < 2^32
         out.slots <<= 1;
     out.n_blocks = (int)(out.slots / kMatchThreads);
-    size_t off = 0;
-    out.state_off = off;
-    off += match_align(4 * sizeof(unsigned));
-    out.key_off = off;
-    off += match_align(out.slots * sizeof(unsigned long long));
-    out.val_off = off;
-    off += match_align(out.slots * 2 * sizeof(unsigned long long));
-    out.block_off = off;
-    off += match_align((size_t)out.n_blocks * sizeof(int));
-    out.dense_key_off = off;
-    off += match_align((size_t)out.cap * sizeof(unsigned long long));
-    out.dense_slot_off = off;
-    off += match_align((size_t)out.cap * sizeof(unsigned));
-    out.bytes = off;
+    PlanCursor ws;
+    out.state_off = ws.take(4 * sizeof(unsigned));
+    out.key_off = ws.take(out.slots * sizeof(unsigned long long));
+    out.val_off = ws.take(out.slots * 2 * sizeof(unsigned long long));
+    out.block_off = ws.take((size_t)out.n_blocks * sizeof(int));
+    out.dense_key_off = ws.take((size_t)out.cap * sizeof(unsigned long long));
+    out.dense_slot_off = ws.take((size_t)out.cap * sizeof(unsigned));
+    out.bytes = ws.off;
     return GS_OK;
 }
 
 // What gs_instance_match refuses about its numbers (the pointers are the entry's business).
 inline gs_status check_instance_match(int pair_cap, int n_gt, int n_pred, int classes, int iou_num, int iou_den)
 {
-    if (pair_cap < 1) {
-        set_error("gs_instance_match: pair_cap must be at least 1 (got %d)", pair_cap);
-        return GS_ERR_INVALID;
-    }
-    if (n_gt < 0 || n_pred < 0) {
-        set_error("gs_instance_match: n_gt and n_pred must not be negative (got %d, %d)", n_gt, n_pred);
-        return GS_ERR_INVALID;
-    }
-    if (classes < 2 || classes > GS_MAX_CLASSES) {
-        set_error("gs_instance_match: classes must be 2..%d (got %d)", GS_MAX_CLASSES, classes);
-        return GS_ERR_INVALID;
-    }
+    const char *entry = "gs_instance_match";
+    gs_status st;
+    if ((st = check_pair_cap(entry, pair_cap)) != GS_OK || (st = check_instance_counts(entry, n_gt, n_pred)) != GS_OK ||
+        (st = check_map_classes(entry, classes)) != GS_OK)
+        return st;
     if (iou_num < 1 || iou_den > 65535 || iou_num > iou_den || 2LL * iou_num < (long long)iou_den) {
         set_error("gs_instance_match: the threshold must be num / den with 1 <= num <= den <= 65535 and 2 * num >= den: below "
                   "1/2 a match is not unique (got %d / %d)", iou_num, iou_den);

@@ -23,12 +23,12 @@
 // candidate, and union re-checks that candidate with the value the atomic min returns -- the read-modify-write is exact where
 // the load need not be.  Across launches visibility comes from the kernel boundary alone.
 //
-// Rules: no kernel waits on another workgroup (no flags, tickets or look-back scan: the scan is two-level, launches 3 to 5); every
-// loop makes monotone progress -- find() follows strictly decreasing indices, and in union the larger of the pair strictly
-// decreases each round -- so there is no spin loop; counters and boxes are written with ordinary vector atomics and stores; the
-// entry allocates nothing and writes every byte of workspace and output that it later reads.
+// Rules: those of wave_block.h, whose count / scan / rank are launches 3 to 5 and whose grouping loop is launch 6's.  The loops
+// of this file's own: find() follows strictly decreasing indices, and in union the larger of the pair strictly decreases each
+// round.
 #include "gs_internal.h"
 #include "instance_plan.h"
+#include "wave_block.h"
 #include "../../include/glomseg_instances.h"
 
 namespace gs {
@@ -37,8 +37,7 @@ namespace {
 
 constexpr int kTW = kInstTileW, kTH = kInstTileH, kThreads = kInstThreads;
 constexpr int kTilePixels = kTW * kTH, kPerThread = kTilePixels / kThreads;
-constexpr int kScanThreads = 1024;
-static_assert(kTW == 64 && kTilePixels % kThreads == 0 && kThreads % 64 == 0, "tile indexing below");
+static_assert(kTW == 64 && kTilePixels % kThreads == 0 && kThreads == kFlagThreads, "tile indexing below; block_flag_count / _rank");
 
 // ---- union-find in LDS (local indices ly * 64 + lx: monotone in the global linear index)
 __device__ inline int lds_load(const int *L, int x) { return __hip_atomic_load(L + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -190,7 +189,6 @@ __global__ __launch_bounds__(kThreads) void inst_border_kernel(int *parent, int 
 // the other threads have flattened meanwhile.
 __global__ __launch_bounds__(kThreads) void inst_flatten_kernel(int *parent, int n, int *__restrict__ block_count)
 {
-    __shared__ int wave_roots[kThreads / 64];
     const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
     bool is_root = false;
     if (i < n) {
@@ -202,44 +200,15 @@ __global__ __launch_bounds__(kThreads) void inst_flatten_kernel(int *parent, int
             is_root = r == (int)i;
         }
     }
-    const unsigned long long m = __ballot(is_root);
-    if ((threadIdx.x & 63) == 0)
-        wave_roots[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < kThreads / 64; ++w)
-            s += wave_roots[w];
-        block_count[blockIdx.x] = s;
-    }
+    block_flag_count(is_root, block_count);
 }
 
 // 4 ------------------------------------------------------------------------------------------------------------------------
-// One workgroup: thread t sums its run of blocks, the 1024 sums are scanned in LDS, the run is rewritten as exclusive offsets.
 __global__ __launch_bounds__(kScanThreads) void inst_scan_kernel(int *__restrict__ block_count, int n_blocks, int *__restrict__ n_found)
 {
-    __shared__ int s[kScanThreads];
-    const int t = (int)threadIdx.x, run = (n_blocks + kScanThreads - 1) / kScanThreads;
-    const long long lo = (long long)t * run, hi = lo + run < n_blocks ? lo + run : n_blocks;
-    int sum = 0;
-    for (long long b = lo; b < hi; ++b)
-        sum += block_count[b];
-    s[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < kScanThreads; d <<= 1) {
-        const int v = t >= d ? s[t - d] : 0;
-        __syncthreads();
-        s[t] += v;
-        __syncthreads();
-    }
-    int base = s[t] - sum;
-    for (long long b = lo; b < hi; ++b) {
-        const int c = block_count[b];
-        block_count[b] = base;
-        base += c;
-    }
-    if (t == kScanThreads - 1)
-        *n_found = s[t];
+    const int total = block_scan_exclusive(block_count, n_blocks);
+    if (threadIdx.x == kScanThreads - 1)
+        *n_found = total;
 }
 
 // 5 ------------------------------------------------------------------------------------------------------------------------
@@ -247,20 +216,11 @@ __global__ __launch_bounds__(kThreads) void inst_number_kernel(int *__restrict__
                                                                 const int *__restrict__ n_found, int H, int W, int classes, int cap,
                                                                 int *__restrict__ boxes, unsigned long long *__restrict__ counts)
 {
-    __shared__ int wave_roots[kThreads / 64];
     const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
     const bool is_root = i < n && parent[i] == (int)i;
-    const unsigned long long m = __ballot(is_root);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0)
-        wave_roots[wave] = __popcll(m);
-    __syncthreads();
-    if (is_root) {
-        int id = block_base[blockIdx.x] + __popcll(m & ((1ull << lane) - 1)) + 1;
-        for (int w = 0; w < wave; ++w)
-            id += wave_roots[w];
+    const int id = block_flag_rank(is_root, block_base) + 1;
+    if (is_root)
         parent[i] = -id - 1;       // <= -2: told from background (-1) and from a parent (>= 0)
-    }
     // the rows launch 6 adds into: n_found <= n, so one thread per row is enough
     const int found = *n_found, rows = found < cap ? found : cap;
     if (i < rows) {
@@ -297,14 +257,8 @@ __global__ __launch_bounds__(kThreads) void inst_reduce_kernel(const uint8_t *__
         if (labels)
             labels[i] = id;
     }
-    const bool todo = id >= 1 && id <= cap;
-    unsigned long long rem = __ballot(todo);
-    while (rem) {                                    // wave-uniform; every round retires at least one lane
-        const int first = __ffsll((long long)rem) - 1;
-        const int lead = __shfl(id, first);
-        const bool mine = todo && id == lead;
-        const unsigned long long g = __ballot(mine);
-        const int last = 63 - __clzll((long long)g);
+    for_each_wave_group(id >= 1 && id <= cap, id, [&](int first, unsigned long long g, bool mine) {
+        const int lead = __shfl(id, first), last = 63 - __clzll((long long)g);
         const int x0 = __shfl(x, first), y0 = __shfl(y, first), x1 = __shfl(x, last), y1 = __shfl(y, last);
         int *box = boxes + (size_t)(lead - 1) * 4;
         if (y0 == y1) {
@@ -320,17 +274,12 @@ __global__ __launch_bounds__(kThreads) void inst_reduce_kernel(const uint8_t *__
             atomicMax(box + 2, x + 1);
             atomicMax(box + 3, y + 1);
         }
-        unsigned long long crem = g;
-        while (crem) {
-            const int cf = __ffsll((long long)crem) - 1;
+        for_each_wave_group(mine, cls, [&](int cf, unsigned long long cm, bool) {
             const int c = __shfl(cls, cf);
-            const unsigned long long cm = __ballot(mine && cls == c);
             if (lane == cf)
                 atomicAdd(counts + (size_t)(lead - 1) * classes + c, (unsigned long long)__popcll(cm));
-            crem &= ~cm;
-        }
-        rem &= ~g;
-    }
+        });
+    });
 }
 
 }  // namespace
@@ -357,8 +306,8 @@ extern "C" gs_status gs_slide_instances(const uint8_t *class_map, int height, in
     const gs_status st = plan_instances(height, width, classes, cap, plan);
     if (st != GS_OK)
         return st;
-    GS_REQUIRE(class_map && ((uintptr_t)class_map & 3) == 0, "gs_slide_instances: class_map is NULL or not 4-byte aligned");
-    GS_REQUIRE(workspace && ((uintptr_t)workspace & 3) == 0, "gs_slide_instances: workspace is NULL or not 4-byte aligned");
+    GS_REQUIRE(aligned(class_map, 4), "gs_slide_instances: class_map is NULL or not 4-byte aligned");
+    GS_REQUIRE(aligned(workspace, 4), "gs_slide_instances: workspace is NULL or not 4-byte aligned");
     GS_REQUIRE(boxes && counts && n_found, "gs_slide_instances: boxes, counts and n_found must not be NULL");
     GS_REQUIRE(workspace_bytes >= plan.bytes, "gs_slide_instances: a %d x %d map needs %zu bytes of workspace (got %zu)", height, width,
                plan.bytes, workspace_bytes);

@@ -1,0 +1,29 @@
+"""A public header under include/ against its prototype table in _lib.py and the built library."""
+import os
+import re
+import subprocess
+
+from conftest import REPO
+
+
+def assert_declared_exported_prototyped(header, table, names):
+    """the entries include/<header> declares are exactly `names` and exactly `table`'s (one of _lib's *_PROTOTYPES), none of them is
+    in another table, the library exports each, and each has the table's argument types and as many parameters as the header
+    gives it.  -> the header's text, for the caller's own phrase checks"""
+    from glomeruli_segmentation_amd import _lib
+    with open(os.path.join(REPO, "include", header)) as fh:
+        text = fh.read()
+    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    declared = set(re.findall(r"\b(gs_[a-z0-9_]+)\s*\(", code))
+    assert declared == set(table) == set(names)
+    others = [t for k, t in vars(_lib).items() if k.endswith("PROTOTYPES") and t is not table]
+    assert others and not any(declared & set(t) for t in others)
+    lib = _lib.load()
+    assert lib.gs_abi_version() == _lib.ABI_VERSION == 10         # not bumped: the entries are found by looking them up
+    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
+    assert declared <= set(re.findall(r" T (gs_[a-z0-9_]+)", out))
+    for name in declared:
+        assert getattr(lib, name).argtypes == table[name][1]
+        n_params = len(re.search(name + r"\s*\((.*?)\)\s*;", code, flags=re.S).group(1).split(","))
+        assert n_params == len(table[name][1]), name
+    return text

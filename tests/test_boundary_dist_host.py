@@ -7,9 +7,6 @@ import ctypes
 import io
 import math
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,6 +16,8 @@ from conftest import REPO
 
 from helpers import boundary_dist_ref as bref
 from helpers import instance_match_ref as mref
+from helpers.header_binding import assert_declared_exported_prototyped
+from helpers.sanitized_driver import assert_no_hip, run_sanitized_driver
 
 
 # ------------------------------------------------------------------------------------------ the checker
@@ -83,24 +82,11 @@ def test_pinned_figures():
 # ------------------------------------------------------------------------------------------ header, binding, library
 def test_boundary_entries_declared_exported_prototyped():
     from glomeruli_segmentation_amd import _lib, build
-    with open(os.path.join(REPO, "include", "glomseg_boundary_dist.h")) as fh:
-        text = fh.read()
-    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = set(re.findall(r"\b(gs_[a-z0-9_]+)\s*\(", header))
-    assert declared == set(_lib.BOUNDARY_PROTOTYPES) == {"gs_boundary_dist_plan", "gs_instance_boundary_dist"}
-    others = [_lib.PROTOTYPES, _lib.SCORING_PROTOTYPES, _lib.PLAN_PROTOTYPES, _lib.INSTANCE_PROTOTYPES, _lib.MATCH_PROTOTYPES]
-    assert not any(declared & set(t) for t in others)
-    lib = _lib.load()
-    assert lib.gs_abi_version() == _lib.ABI_VERSION == 10         # not bumped: the entries are found by looking them up
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    assert declared <= set(re.findall(r" T (gs_[a-z0-9_]+)", out))
-    for name in declared:
-        assert getattr(lib, name).argtypes == _lib.BOUNDARY_PROTOTYPES[name][1]
-        n_params = len(re.search(name + r"\s*\((.*?)\)\s*;", header, flags=re.S).group(1).split(","))
-        assert n_params == len(_lib.BOUNDARY_PROTOTYPES[name][1]), name
+    text = assert_declared_exported_prototyped("glomseg_boundary_dist.h", _lib.BOUNDARY_PROTOTYPES,
+                                               {"gs_boundary_dist_plan", "gs_instance_boundary_dist"})
     for word in ("boundary pixel", "PARTNER INSTANCE ONLY", "2 * 32767^2", "binary_erosion"):
         assert word in text                                       # the definitions live in the header
-    assert "boundary_dist.hip" in build.SOURCES and "boundary_dist_plan.h" in build.HEADERS
+    assert "boundary_dist.hip" in build.SOURCES and {"boundary_dist_plan.h", "slide_map_plan.h", "wave_block.h"} <= set(build.HEADERS)
 
 
 # ------------------------------------------------------------------------------------------ the plan and the refusals
@@ -175,27 +161,12 @@ def test_entry_refusals_need_no_device():
 
 
 def test_plan_header_under_asan_ubsan(tmp_path):
-    """csrc/boundary_dist_plan.h needs no HIP: tests/helpers/boundary_dist_plan_driver.cpp is built with g++ alone and run as a
-    program of its own (no preload)"""
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("g++ not available")
-    exe = tmp_path / "boundary_dist_plan_driver"
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-I" + os.path.join(REPO, "glomeruli_segmentation_amd", "csrc"),
-           os.path.join(REPO, "tests", "helpers", "boundary_dist_plan_driver.cpp"), "-o", str(exe)]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    if built.returncode != 0 and "sanitize" in built.stderr and ("cannot find" in built.stderr or "unrecognized" in built.stderr):
-        pytest.skip("sanitizer runtime not available: " + built.stderr[-300:])
-    assert built.returncode == 0, built.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:exitcode=77", UBSAN_OPTIONS="halt_on_error=1:exitcode=78")
-    res = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, (res.returncode, res.stdout[-500:], res.stderr[-3000:])
-    assert "boundary dist plan ok:" in res.stdout
-    for word in ("AddressSanitizer", "runtime error"):
-        assert word not in res.stderr, res.stderr[-3000:]
-    with open(os.path.join(REPO, "glomeruli_segmentation_amd", "csrc", "boundary_dist_plan.h")) as fh:
-        assert "hip" not in re.sub(r"//.*", "", fh.read()).lower()                 # no HIP include: a plain host compiler reads it
+    """csrc/boundary_dist_plan.h and csrc/slide_map_plan.h need no HIP: tests/helpers/slide_map_plan_driver.cpp is built with g++
+    alone and run as a program of its own (no preload)"""
+    out = run_sanitized_driver(tmp_path, "slide_map_plan_driver.cpp", "slide map plans ok", flags=("-Wall",))
+    assert "boundary dist plan ok:" in out and "shared checks ok:" in out
+    assert_no_hip("boundary_dist_plan.h")
+    assert_no_hip("slide_map_plan.h")
 
 
 # ------------------------------------------------------------------------------------------ ratios, rows, command line

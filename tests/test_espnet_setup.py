@@ -13,13 +13,13 @@ import functools
 import hashlib
 import json
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, REPO, load_weights, random_state_dict
+
+from helpers.sanitized_driver import run_sanitized_driver
 
 # (name, p, q, classes, encoder_only); "fold1": tests/golden/weights_fold1.npz, else random_state_dict(p, q, classes, seed=0).
 # The padded class counts 4, 5, 8, 12, 16 and 20, p = 0, q = 0, blocks with and without a fused next reduce, both handle kinds.
@@ -211,20 +211,4 @@ def test_setup_headers_under_asan_ubsan(tmp_path):
     """csrc/espnet_weights.h and csrc/workspace_plan.h need no HIP: tests/helpers/espnet_setup_driver.cpp is built with g++ alone
     and run as a program of its own (no preload) -- every class count 2..20, p and q in 0..3, both handle kinds; tile sizes 8,
     64 and 520 in both dimensions at batch 1 and 3"""
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("g++ not available")
-    exe = tmp_path / "espnet_setup_driver"
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D_GLIBCXX_SANITIZE_VECTOR",
-           "-I" + os.path.join(REPO, "glomeruli_segmentation_amd", "csrc"),
-           os.path.join(REPO, "tests", "helpers", "espnet_setup_driver.cpp"), "-o", str(exe)]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    if built.returncode != 0 and "sanitize" in built.stderr and ("cannot find" in built.stderr or "unrecognized" in built.stderr):
-        pytest.skip("sanitizer runtime not available: " + built.stderr[-300:])
-    assert built.returncode == 0, built.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:exitcode=77", UBSAN_OPTIONS="halt_on_error=1:exitcode=78")
-    res = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, (res.returncode, res.stdout[-500:], res.stderr[-3000:])
-    assert "espnet setup ok: 608 packs, 2736 plans" in res.stdout
-    for word in ("AddressSanitizer", "runtime error"):
-        assert word not in res.stderr, res.stderr[-3000:]
+    run_sanitized_driver(tmp_path, "espnet_setup_driver.cpp", "espnet setup ok: 608 packs, 2736 plans", flags=("-D_GLIBCXX_SANITIZE_VECTOR",))

@@ -78,6 +78,17 @@ def test_case_equals_checker(name, connectivity):
         assert got[2][0].tolist() == [155100, 155100]
 
 
+def test_table_of_two_blocks_per_scan_thread():
+    """pair_cap = height * width: 524288 slots in 2048 counting blocks, so every thread of the scan's one workgroup sums and rewrites
+    a run of two blocks -- at the caps above the table has 256 blocks at the most and a run is one block or none"""
+    from glomeruli_segmentation_amd import instance_eval
+    map_gt, map_pred = ref.case_maps("random_300x517")
+    r = ref.reference("random_300x517", 4)
+    pair_cap = 300 * 517
+    assert 524288 * 24 <= instance_eval.workspace_bytes(300, 517, pair_cap) < 2 * 524288 * 24 and len(r["pairs"]) == 15264
+    assert_equals_checker(run_entries(map_gt, map_pred, r, pair_cap), r, pair_cap)
+
+
 def test_thresholds():
     """all 571 pairs exactly at 1/2 stay unmatched; a pair at exactly 3/5 matches at 1/2 and 59/100 and not at 3/5"""
     map_gt, map_pred = ref.case_maps("random_300x517")

@@ -5,8 +5,6 @@ conditions the GPU cases of tests/test_instance_match.py rely on."""
 import ctypes
 import math
 import os
-import re
-import shutil
 import subprocess
 import sys
 
@@ -17,6 +15,8 @@ from conftest import REPO
 
 from helpers import instance_maps as maps
 from helpers import instance_match_ref as ref
+from helpers.header_binding import assert_declared_exported_prototyped
+from helpers.sanitized_driver import assert_no_hip, run_sanitized_driver
 
 
 # ------------------------------------------------------------------------------------------ the checker
@@ -85,22 +85,9 @@ def test_gpu_case_conditions():
 # ------------------------------------------------------------------------------------------ header, binding, library
 def test_match_entries_declared_exported_prototyped():
     from glomeruli_segmentation_amd import _lib
-    with open(os.path.join(REPO, "include", "glomseg_instance_match.h")) as fh:
-        text = fh.read()
-    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = set(re.findall(r"\b(gs_[a-z0-9_]+)\s*\(", header))
-    assert declared == set(_lib.MATCH_PROTOTYPES) == {"gs_instance_match_plan", "gs_instance_overlaps", "gs_instance_match"}
-    others = [_lib.PROTOTYPES, _lib.SCORING_PROTOTYPES, _lib.PLAN_PROTOTYPES, _lib.INSTANCE_PROTOTYPES]
-    assert not any(declared & set(t) for t in others)
+    text = assert_declared_exported_prototyped("glomseg_instance_match.h", _lib.MATCH_PROTOTYPES,
+                                               {"gs_instance_match_plan", "gs_instance_overlaps", "gs_instance_match"})
     assert set(_lib.INSTANCE_PROTOTYPES) == {"gs_instances_plan", "gs_slide_instances"}
-    lib = _lib.load()
-    assert lib.gs_abi_version() == _lib.ABI_VERSION == 10         # not bumped: the entries are found by looking them up
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    assert declared <= set(re.findall(r" T (gs_[a-z0-9_]+)", out))
-    for name in declared:
-        assert getattr(lib, name).argtypes == _lib.MATCH_PROTOTYPES[name][1]
-        n_params = len(re.search(name + r"\s*\((.*?)\)\s*;", header, flags=re.S).group(1).split(","))
-        assert n_params == len(_lib.MATCH_PROTOTYPES[name][1]), name
     assert "Proof" in text and "2 * inter > union" in text       # the uniqueness proof lives in the header
 
 
@@ -195,27 +182,11 @@ def test_match_refusals_need_no_device():
 
 
 def test_plan_header_under_asan_ubsan(tmp_path):
-    """csrc/instance_match_plan.h needs no HIP: tests/helpers/instance_match_plan_driver.cpp is built with g++ alone and run as a
+    """csrc/instance_match_plan.h needs no HIP: tests/helpers/slide_map_plan_driver.cpp is built with g++ alone and run as a
     program of its own (no preload): the plan over edge sizes, the threshold range"""
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("g++ not available")
-    exe = tmp_path / "instance_match_plan_driver"
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-I" + os.path.join(REPO, "glomeruli_segmentation_amd", "csrc"),
-           os.path.join(REPO, "tests", "helpers", "instance_match_plan_driver.cpp"), "-o", str(exe)]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    if built.returncode != 0 and "sanitize" in built.stderr and ("cannot find" in built.stderr or "unrecognized" in built.stderr):
-        pytest.skip("sanitizer runtime not available: " + built.stderr[-300:])
-    assert built.returncode == 0, built.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:exitcode=77", UBSAN_OPTIONS="halt_on_error=1:exitcode=78")
-    res = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, (res.returncode, res.stdout[-500:], res.stderr[-3000:])
-    assert "instance match plan ok:" in res.stdout
-    for word in ("AddressSanitizer", "runtime error"):
-        assert word not in res.stderr, res.stderr[-3000:]
-    with open(os.path.join(REPO, "glomeruli_segmentation_amd", "csrc", "instance_match_plan.h")) as fh:
-        assert "hip" not in re.sub(r"//.*", "", fh.read()).lower()                 # no HIP include: a plain host compiler reads it
+    out = run_sanitized_driver(tmp_path, "slide_map_plan_driver.cpp", "slide map plans ok", flags=("-Wall",))
+    assert "instance match plan ok:" in out
+    assert_no_hip("instance_match_plan.h")
 
 
 # ------------------------------------------------------------------------------------------ rows, summary, command line

@@ -1,9 +1,7 @@
 """CPU tests of the instance table (include/glomseg_instances.h, glomeruli_segmentation_amd/instances.py): the numpy checker
-against scipy, the header against the binding and the library, the refusals and the plan (no device), the rows of the CSV and
+against scipy, the header against the binding and the library, the refusals and the plan (no device), the plan header under sanitizers, the rows of the CSV and
 the command line's parser, and the conditions the GPU cases of tests/test_instances.py rely on."""
 import ctypes
-import os
-import re
 import subprocess
 import sys
 
@@ -13,7 +11,9 @@ import pytest
 from conftest import REPO
 
 from helpers import instance_maps as maps
+from helpers.header_binding import assert_declared_exported_prototyped
 from helpers.instances_ref import label_instances_ref
+from helpers.sanitized_driver import assert_no_hip, run_sanitized_driver
 
 CONNECTIVITIES = (4, 8)
 
@@ -81,17 +81,15 @@ def test_gpu_case_conditions():
 # ------------------------------------------------------------------------------------------ header, binding, library
 def test_instance_entries_declared_exported_prototyped():
     from glomeruli_segmentation_amd import _lib
-    with open(os.path.join(REPO, "include", "glomseg_instances.h")) as fh:
-        header = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    declared = set(re.findall(r"\b(gs_[a-z0-9_]+)\s*\(", header))
-    assert declared == set(_lib.INSTANCE_PROTOTYPES) == {"gs_instances_plan", "gs_slide_instances"}
-    assert not declared & (set(_lib.PROTOTYPES) | set(_lib.SCORING_PROTOTYPES) | set(_lib.PLAN_PROTOTYPES))
-    lib = _lib.load()
-    assert lib.gs_abi_version() == _lib.ABI_VERSION            # not bumped: the entries are found by looking them up
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    assert declared <= set(re.findall(r" T (gs_[a-z0-9_]+)", out))
-    for name in declared:
-        assert getattr(lib, name).argtypes == _lib.INSTANCE_PROTOTYPES[name][1]
+    assert_declared_exported_prototyped("glomseg_instances.h", _lib.INSTANCE_PROTOTYPES, {"gs_instances_plan", "gs_slide_instances"})
+
+
+def test_plan_header_under_asan_ubsan(tmp_path):
+    """csrc/instance_plan.h needs no HIP: tests/helpers/slide_map_plan_driver.cpp is built with g++ alone and run as a program of
+    its own (no preload): tiles, counting blocks and the two parts of the workspace over edge sizes, 1 x INT_MAX included"""
+    out = run_sanitized_driver(tmp_path, "slide_map_plan_driver.cpp", "slide map plans ok", flags=("-Wall",))
+    assert "instance plan ok:" in out
+    assert_no_hip("instance_plan.h")
 
 
 # ------------------------------------------------------------------------------------------ refusals and the plan
