@@ -162,6 +162,11 @@ PLAN_PROTOTYPES = {
 }
 GS_PLAN_LAZY_B2, GS_PLAN_L3C_IN_REDUCE, GS_PLAN_CLS_IN_L3 = 1, 2, 4
 
+# every symbol include/glomseg_lean.h declares (an addition with a header of its own)
+LEAN_PROTOTYPES = {
+    "gs_espnet_plan_lean": (_I, [_I] * 9 + [ctypes.POINTER(_I)]),
+}
+
 # every symbol include/glomseg_instances.h declares (additions to ABI 10 with a header of their own)
 INSTANCE_PROTOTYPES = {
     "gs_instances_plan": (_I, [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)]),
@@ -196,9 +201,10 @@ def load():
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     for name, (res, args) in list(PROTOTYPES.items()) + list(SCORING_PROTOTYPES.items()) + list(PLAN_PROTOTYPES.items()) + \
-            list(INSTANCE_PROTOTYPES.items()) + list(MATCH_PROTOTYPES.items()) + list(BOUNDARY_PROTOTYPES.items()):
-        if name in PLAN_PROTOTYPES and not hasattr(lib, name):
-            continue   # (an ABI 9 library from before glomseg_plan.h, loaded for an A/B: engine.plan_flags then raises)
+            list(INSTANCE_PROTOTYPES.items()) + list(MATCH_PROTOTYPES.items()) + list(BOUNDARY_PROTOTYPES.items()) + \
+            list(LEAN_PROTOTYPES.items()):
+        if (name in PLAN_PROTOTYPES or name in LEAN_PROTOTYPES) and not hasattr(lib, name):
+            continue   # (a library from before glomseg_plan.h / glomseg_lean.h, loaded for an A/B: engine.plan_flags / plan_lean then raise)
         fn = getattr(lib, name)   # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -285,6 +285,11 @@ constexpr int F_SIDE1X1(int classes) { return classes << F_SIDE_SHIFT; }
 // dec1_sums_kernel adds ((A0 + A1) + (B0 + B1)), A = output2_0's launch, B = output2's, the index the lane half.
 // Needs MT == 32, F_BNACT, NDIL == 5 and COUT * CLS_REC floats in whole DMA pieces, one per wave.
 constexpr int F_CLS1X1 = 256;
+// An F_CLS1X1 launch whose OUTPUT nobody reads: the network's last level-3 block of a mask-only forward (ForwardPlan::lean).  Since
+// the classifier became side sums, output2 has one reader left, gs_espnet_read_stage, so such a launch keeps its residual add,
+// BN + PReLU and class sums and drops the primary store (134 MB at batch 32).  Not F_NOSTORE: that one belongs to F_DUAL, whose
+// second store is then the block's only output.  Needs F_CLS1X1; no F_FUSE1X1 (a next block would read the map) and no F_DUAL.
+constexpr int F_CLS_ONLY = 2048;
 constexpr int CLS_N = 5, CLS_REC = 8;   // classes of the side sums; floats of a record (dec1_record<5>)
 constexpr int F_X_NOLOAD = 16;  // GS_DIAG timing experiments only (results are garbage): no activation loads in the loop
 constexpr int F_X_NOLDS = 32;   // GS_DIAG: no LDS weight reads in the loop
@@ -332,7 +337,7 @@ constexpr int conv_ring_depth(int MT, int TAPS, int NDIL, int P, int G)
 template <int MT, int WAVES, int CINP, int TAPS, int STRIDE, int NDIL, int NOUT1, int NOUT, int P, int G, int FLAGS>
 __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_mfma_kernel(const ConvArgs a)
 {
-    constexpr bool BNACT = FLAGS & F_BNACT, RES = FLAGS & F_RES, STORE1 = !(FLAGS & F_NOSTORE), DUAL = FLAGS & F_DUAL;
+    constexpr bool BNACT = FLAGS & F_BNACT, RES = FLAGS & F_RES, STORE1 = !(FLAGS & (F_NOSTORE | F_CLS_ONLY)), DUAL = FLAGS & F_DUAL;
     constexpr bool S2P = FLAGS & F_S2PAIR;
     constexpr bool VEC = FLAGS & F_VEC;
     constexpr bool AGL = FLAGS & F_A_GLOBAL, FUSE = FLAGS & F_FUSE1X1;
@@ -345,6 +350,8 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
     static_assert(!CLSF || (MT == 32 && NDIL == 5 && TAPS == 9 && (FLAGS & F_BNACT) && !(FLAGS & (F_DUAL | F_NOSTORE | F_BNLOAD | F_X_ALL)) &&
                             !SIDE && ((NOUT1 + (NDIL - 1) * NOUT) * CLS_REC) % 256 == 0 && (NOUT1 + (NDIL - 1) * NOUT) * CLS_REC / 256 <= WAVES),
                   "F_CLS1X1 is for the level-3 branch launches: 32-row accumulators, five slots, the records in whole DMA pieces");
+    static_assert(!(FLAGS & F_CLS_ONLY) || (CLSF && !(FLAGS & (F_FUSE1X1 | F_DUAL))),
+                  "F_CLS_ONLY drops the store of a launch whose class sums are its only output: F_CLS1X1 without a fused 1x1 or a second store");
     static_assert(!SIDE || ((FLAGS & F_S2PAIR) && TAPS == 9 && STRIDE == 2 && MT == 32 && NDIL == 1 && SCLS <= SIDE_REC &&
                             (CINP / M_KL_OF(MT)) % G == 0 && G * M_KL_OF(MT) <= SIDE_ZROWS && !(FLAGS & (F_A_GLOBAL | F_VEC | F_X_ALL))),
                   "F_SIDE1X1 is for the stride-2 3x3 reduce on 32-pixel runs, a tap row in whole chunks");

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/glomseg_plan.h"
+#include "../../include/glomseg_lean.h"
 #include "conv_mfma.h"
 #include "dec_tail_args.h"
 #include "enc_head.h"
@@ -89,6 +90,7 @@ struct Model : Workspace {   // (the activations: workspace_plan.h)
     }
     int last_n = 0;
     bool b2_lazy = false;    // planes 64..127 of the stage "b2" are not materialised by the last forward (read_stage fills them)
+    bool lean = false;       // the last forward was lean (ForwardPlan::lean): the stages such a request leaves out (read_stage's message)
 
     // profiling
     bool profile = false;
@@ -352,9 +354,18 @@ static gs_status launch_l3_esp_fused(const Model *m, form::l3_esp_fused f, const
     return not_planned("l3_esp_fused");
 }
 
-// cls5: as launch_l3_down's, for the network's last block: channels 128..255
-static gs_status launch_l3_esp_last(const Model *m, form::l3_esp_last f, bool cls5, const ConvArgs &ca, hipStream_t s)
+// cls5: as launch_l3_down's, for the network's last block: channels 128..255.  cls_only: the plan's `lean` -- nothing of this forward
+// reads that block's map, so every form runs without its primary store (F_CLS_ONLY)
+static gs_status launch_l3_esp_last(const Model *m, form::l3_esp_last f, bool cls5, bool cls_only, const ConvArgs &ca, hipStream_t s)
 {
+    if (cls5 && cls_only)
+        switch (f) {
+        case form::l3_esp_last::P1R: return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | F_RES | POL_L3_ESP | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0) | F_CLS1X1 | F_CLS_ONLY>(ca, m->num_cus, s);
+        case form::l3_esp_last::P2R_VEC: return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | F_RES | F_VEC | POL_L3_ESP | SKIP_L3 | F_CLS1X1 | F_CLS_ONLY>(ca, m->num_cus, s);
+        case form::l3_esp_last::BR_VEC: return launch_conv_mfma<CFG_L3_BR, F_BNACT | F_RES | F_VEC | POL_L3_ESP | F_CLS1X1 | F_CLS_ONLY>(ca, m->num_cus, s);
+        case form::l3_esp_last::P2: return launch_conv_mfma<CFG_L3_BR_P2, F_BNACT | F_RES | F_CLS1X1 | F_CLS_ONLY>(ca, m->num_cus, s);
+        case form::l3_esp_last::none: return not_planned("l3_esp_last");
+        }
     if (cls5)
         switch (f) {
         case form::l3_esp_last::P1R: return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | F_RES | POL_L3_ESP | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0) | F_CLS1X1>(ca, m->num_cus, s);
@@ -417,6 +428,7 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
     const double px1 = (double)H1 * W1, px2 = (double)H2 * W2, px3 = (double)H3 * W3;
     m->stages.clear();
     m->last_n = n;
+    m->lean = plan.lean;
     // ---- stem (Model.py:346-350)
     L.run(K_STEM, px1 * (27 * 16 * 2), [&] {
         StemArgs a{};
@@ -442,7 +454,7 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
         return GS_OK;
     });
     L.run(K_POOL, 0, [&] {
-        hipLaunchKernelGGL(pool_kernel, dim3(blocks_for((long long)n * 3 * H2 * W2)), dim3(256), 0, s, view(m->inp1),
+        hipLaunchKernelGGL(pool_kernel, dim3(blocks_for((long long)n * 3 * H2 * (W2 / POOL_PX))), dim3(256), 0, s, view(m->inp1),
                            view(m->inp2), n, 3, m->p > 0 ? wb + m->w.b2 : nullptr, view(m->a1), 128, 131);
         return GS_OK;
     });
@@ -581,12 +593,16 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
             if (fuse_next)
                 return launch_l3_esp_fused(m, plan.l3_esp_fused, with_fused(ca, m->r3[rd3 ^ 1], 25), i, s);
             const bool cls5 = plan.cls_in_l3 && i == m->q - 1;   // the network's last block holds output2
-            return launch_l3_esp_last(m, plan.l3_esp_last, cls5, cls5 ? with_cls(ca, 1) : ca, s);
+            return launch_l3_esp_last(m, plan.l3_esp_last, cls5, plan.lean, cls5 ? with_cls(ca, 1) : ca, s);
         });
         have_r3 = fuse_next;
         rd3 ^= have_r3 ? 1 : 0;
         cur3 = nxt;
         m->set_stage("level3." + std::to_string(i), m->cc[cur3], 128);
+        // a lean forward's last block stores no map (F_CLS_ONLY): its buffer holds no stage this forward vouches for -- not
+        // output2, and no longer the block before the last one's input either, which the line above has just dropped
+        if (plan.lean && i == m->q - 1)
+            m->stages.erase("level3." + std::to_string(i));
     }
     return {cur3, lazy_b2};
 }
@@ -656,31 +672,41 @@ static gs_status decode(Model *m, Launcher &L, const ForwardPlan &plan, const Fo
     m->set_stage("up_l3", m->o2c, ncls);
 
     // ---- level3_C + cat + BR (Model.py:372-373)
-    L.run(K_DEC2, plan.l3c_in_reduce ? 0 : px2 * (131 * ncls * 2), [&] {
-        Dec2Args a{};
-        a.o2c = view(m->o2c);
-        a.br = wb + m->w.cbr0;
-        a.t = view(m->tt);
-        a.N = n;
-        a.classes = ncls;
-        if constexpr (l3c_side_sums(CLS)) {
-            if (plan.l3c_in_reduce) {   // level3_C came out of the stride-2 reduce: what is left is the cat's BR over 2 * CLS small planes
+    // Five classes: level3_C came out of the stride-2 reduce and dec3_cat_kernel applies the cat's BR to both raw halves on load, so
+    // the forward itself needs no dec2 launch: there dec2_br_kernel only materialises the 2 * CLS normalised planes as the stage
+    // "combine_t", and a lean forward (the plan: no logits asked for) does not run it and has no such stage.
+    if constexpr (l3c_side_sums(CLS)) {
+        if (!plan.l3c_in_reduce) {
+            set_error("internal: a %d-class decoder without level3_C from the stride-2 reduce", CLS);
+            return GS_ERR_INVALID;
+        }
+    }
+    const bool cat_on_load = l3c_side_sums(CLS);
+    if (!plan.lean) {
+        L.run(K_DEC2, cat_on_load ? 0 : px2 * (131 * ncls * 2), [&] {
+            Dec2Args a{};
+            a.o2c = view(m->o2c);
+            a.br = wb + m->w.cbr0;
+            a.t = view(m->tt);
+            a.N = n;
+            a.classes = ncls;
+            if constexpr (l3c_side_sums(CLS)) {
                 a.a1 = view(m->l3c);
                 hipLaunchKernelGGL(dec2_br_kernel<CLS>, dim3(blocks_for((long long)n * H2 * W2)), dim3(256), 0, s, a);
-                return GS_OK;
+            } else {
+                a.a1 = view(m->a1);
+                a.raw = view(m->bb[0]);
+                a.b2 = wb + m->w.b2;
+                a.raw_c0 = 64;
+                a.raw_cn = enc.lazy_b2 ? 64 : 0;
+                a.w3c = wb + m->w.w3c;
+                hipLaunchKernelGGL(dec2_kernel<CLS>, dim3((unsigned)(((long long)n * H2 * W2 + 63) / 64)), dim3(256), 0, s, a);   // 64 pixels x 4 channel quarters
             }
-        }
-        a.a1 = view(m->a1);
-        a.raw = view(m->bb[0]);
-        a.b2 = wb + m->w.b2;
-        a.raw_c0 = 64;
-        a.raw_cn = enc.lazy_b2 ? 64 : 0;
-        a.w3c = wb + m->w.w3c;
-        hipLaunchKernelGGL(dec2_kernel<CLS>, dim3((unsigned)(((long long)n * H2 * W2 + 63) / 64)), dim3(256), 0, s, a);   // 64 pixels x 4 channel quarters
-        return GS_OK;
-    });
-    if (ncls == CLS)   // (with padding planes in between the two halves are not one contiguous stage)
-        m->set_stage("combine_t", m->tt, 2 * CLS);
+            return GS_OK;
+        });
+        if (ncls == CLS)   // (with padding planes in between the two halves are not one contiguous stage)
+            m->set_stage("combine_t", m->tt, 2 * CLS);
+    }
     // ---- CBR(2c,c,3) + up_l2 (Model.py:373)
     if constexpr (dec3_on_mfma(CLS)) {
         // many classes: the 3x3 over 2 * CLS planes is 7 200 FMAs per pixel at twenty classes -- on the matrix cores (a plain
@@ -701,16 +727,30 @@ static gs_status decode(Model *m, Launcher &L, const ForwardPlan &plan, const Fo
         });
     } else {
         L.run(K_DEC3, px2 * (2 * ncls * 9 * ncls * 2) + px2 * (ncls * ncls * 4 * 2), [&] {
-            Dec3Args a{};
-            a.t = view(m->tt);
-            a.wc = wb + m->w.wcc;
-            a.bnc = wb + m->w.bncc;
-            a.wup = wb + m->w.wup2;
-            a.bnu = wb + m->w.bnu2;
-            a.e = view(m->ee);
-            a.N = n;
-            a.classes = ncls;
-            hipLaunchKernelGGL(dec3_kernel<CLS>, dim3(blocks_for((long long)n * H2 * W2)), dim3(256), 0, s, a);
+            if constexpr (l3c_side_sums(CLS)) {   // the raw cat, its BR on load: a 2 x 2 block of pixels per thread
+                Dec3CatArgs a{};
+                a.l3c = view(m->l3c);
+                a.o2c = view(m->o2c);
+                a.br = wb + m->w.cbr0;
+                a.wc = wb + m->w.wcc;
+                a.bnc = wb + m->w.bncc;
+                a.wup = wb + m->w.wup2;
+                a.bnu = wb + m->w.bnu2;
+                a.e = view(m->ee);
+                a.N = n;
+                hipLaunchKernelGGL(dec3_cat_kernel<CLS>, dim3(blocks_for((long long)n * H2 * W2 / DEC3_PX)), dim3(256), 0, s, a);
+            } else {
+                Dec3Args a{};
+                a.t = view(m->tt);
+                a.wc = wb + m->w.wcc;
+                a.bnc = wb + m->w.bncc;
+                a.wup = wb + m->w.wup2;
+                a.bnu = wb + m->w.bnu2;
+                a.e = view(m->ee);
+                a.N = n;
+                a.classes = ncls;
+                hipLaunchKernelGGL(dec3_kernel<CLS>, dim3(blocks_for((long long)n * H2 * W2)), dim3(256), 0, s, a);
+            }
             return GS_OK;
         });
     }
@@ -778,7 +818,7 @@ static gs_status decode(Model *m, Launcher &L, const ForwardPlan &plan, const Fo
 static gs_status forward_any(Model *m, const ForwardReq &r)
 {
     Launcher L{m, r.s, GS_OK, r.n};
-    const ForwardPlan plan = plan_forward(r.n, r.H, r.W, m->p, m->q, m->cp, m->num_cus, no_vec(), m->encoder_only);   // every choice of a kernel form
+    const ForwardPlan plan = plan_forward(r.n, r.H, r.W, m->p, m->q, m->cp, m->num_cus, no_vec(), m->encoder_only, r.logits != nullptr);   // every choice of a kernel form
     const Encoded e = encode(m, L, plan, r);
     switch (m->cp) {
     case 5: return decode<5>(m, L, plan, r, e);
@@ -1148,7 +1188,9 @@ gs_status gs_espnet_read_stage(gs_espnet *h, const char *stage, int image, float
     GS_REQUIRE(h && stage && dims, "gs_espnet_read_stage: null argument");
     Model &m = h->m;
     auto it = m.stages.find(stage);
-    GS_REQUIRE(it != m.stages.end(), "stage '%s' was not produced by the last forward", stage);
+    GS_REQUIRE(it != m.stages.end(), "stage '%s' was not produced by the last forward%s", stage,
+               m.lean ? " (a lean forward -- mask-only, glomseg_lean.h -- materialises neither 'combine_t' nor the last 'level3.<i>', and no "
+                        "mask-only forward keeps 'conv': request logits to read them)" : "");
     GS_REQUIRE(image >= 0 && image < m.last_n, "image index %d out of range", image);
     const Act &a = it->second.first;
     const int C = it->second.second;
@@ -1212,7 +1254,7 @@ gs_status gs_espnet_block_forward(gs_espnet *h, int kind, int level, int index, 
             r = kind == 1 ? launch_l3_reduce(&m, form::l3_reduce::C1S, false, rca, s) : launch_l3_c1(&m, rca, s);
             if (r != GS_OK) return r;
             r = kind == 1 ? launch_l3_down(&m, unfused_l3_down(dst.W, no_vec()), false, bca, s)
-                          : launch_l3_esp_last(&m, whole_row_l3_esp(dst.W, no_vec()), false, bca, s);
+                          : launch_l3_esp_last(&m, whole_row_l3_esp(dst.W, no_vec()), false, false, bca, s);
         }
         if (r != GS_OK) return r;
         hipLaunchKernelGGL(unpad_kernel, dim3(blocks_for((long long)nout)), dim3(256), 0, s, view(dst), 0, cout, tmp);
@@ -1253,6 +1295,17 @@ gs_status gs_espnet_plan_flags(int n, int height, int width, int p, int q, int c
     if (st != GS_OK) return st;
     const ForwardPlan pl = plan_forward(n, height, width, p, q, padded_classes(classes), num_cus, no_vec(), encoder_only != 0);
     *flags = (pl.lazy_b2 ? GS_PLAN_LAZY_B2 : 0) | (pl.l3c_in_reduce ? GS_PLAN_L3C_IN_REDUCE : 0) | (pl.cls_in_l3 ? GS_PLAN_CLS_IN_L3 : 0);
+    return GS_OK;
+}
+
+gs_status gs_espnet_plan_lean(int n, int height, int width, int p, int q, int classes, int encoder_only, int num_cus, int want_logits,
+                              int *lean)
+{
+    GS_REQUIRE(lean, "gs_espnet_plan_lean: null argument");
+    int count = 0;
+    gs_status st = gs_espnet_plan_forward(n, height, width, p, q, classes, num_cus, nullptr, 0, &count);   // (the same refusals)
+    if (st != GS_OK) return st;
+    *lean = plan_forward(n, height, width, p, q, padded_classes(classes), num_cus, no_vec(), encoder_only != 0, want_logits != 0).lean;
     return GS_OK;
 }
 

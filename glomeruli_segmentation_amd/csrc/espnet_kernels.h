@@ -30,7 +30,8 @@ __device__ __forceinline__ float ldz(const ActV &t, int n, int c, int y, int x)
     return ok ? v : 0.0f;
 }
 // Once-only streams are marked non-temporal (see F_RES_NT in conv_mfma.h); per-kernel switches for measurement:
-// dec2 0.117 -> 0.100 ms, dec1 0.070 -> 0.067, the stride-2 reduce after the stem 0.107 -> 0.095, dec4 unchanged.
+// dec2 0.117 -> 0.100 ms, dec1 0.070 -> 0.067, the stride-2 reduce after the stem 0.107 -> 0.095, dec4 unchanged; dec3_cat_kernel's
+// 84 MB of stores 0.0434 -> 0.0414 ms (profiles/lean_forward_ab.txt).
 #ifndef NT_STEM_ST
 #define NT_STEM_ST 1
 #endif
@@ -43,7 +44,11 @@ __device__ __forceinline__ float ldz(const ActV &t, int n, int c, int y, int x)
 #ifndef NT_DEC4_ST
 #define NT_DEC4_ST 1
 #endif
+#ifndef NT_DEC3_ST
+#define NT_DEC3_ST 1
+#endif
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
 template <bool NT>
 __device__ __forceinline__ float ld_stream(const float *p)
 {
@@ -292,26 +297,46 @@ __global__ void __launch_bounds__(256) stem_kernel(const StemArgs a)
 }
 
 // second AvgPool2d(3,2,1) of sample2.  reference: Model.py:232-239,348
+// Two horizontally adjacent outputs per thread (the output width is even: no tail), as the stem: their 3x5 window is input
+// columns 2x-1 .. 2x+3 with x even, i.e. one 16-byte load (column 2x is 16-byte aligned: rows are 128-byte aligned and `in` has no
+// halo) and one dword to its left per row, from a row pointer, instead of eighteen clamped dword loads with a 64-bit address
+// each; the results leave as 8-byte stores.  The input has as many rows and columns as twice the output's, so only row -1 (y = 0)
+// and column -1 (x = 0) are padding.  An output's sum is the one it always was: from 0.0f, ky outer, kx inner, then / 9.0f.
+constexpr int POOL_PX = 2;
 __global__ void __launch_bounds__(256)
 pool_kernel(const ActV in, const ActV out, int N, int C, const float *bnp2, const ActV out2, int coff2, int C2)
 {
+    const int WP = out.W / POOL_PX;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)N * C * out.H * out.W)
+    if (idx >= (long long)N * C * out.H * WP)
         return;
-    const int x = (int)(idx % out.W);
-    const int y = (int)((idx / out.W) % out.H);
-    const int c = (int)((idx / ((long long)out.W * out.H)) % C);
-    const int n = (int)(idx / ((long long)out.W * out.H * C));
-    float s = 0.0f;
+    const int x = (int)(idx % WP) * POOL_PX;
+    const int y = (int)((idx / WP) % out.H);
+    const int c = (int)((idx / ((long long)WP * out.H)) % C);
+    const int n = (int)(idx / ((long long)WP * out.H * C));
+    const float *row0 = at(in, n, c, 2 * y, 0);
+    float s[POOL_PX] = {0.0f, 0.0f};
 #pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
+    for (int ky = 0; ky < 3; ++ky) {
+        // branch-free (see ldz): clamp, load, select
+        const bool rok = ky > 0 || y > 0;
+        const float *row = row0 + (rok ? ky - 1 : 0) * in.pitch;
+        const float4 q = *reinterpret_cast<const float4 *>(row + 2 * x);
+        const float l = row[x > 0 ? 2 * x - 1 : 0];
+        const float v[5] = {rok && x > 0 ? l : 0.0f, rok ? q.x : 0.0f, rok ? q.y : 0.0f, rok ? q.z : 0.0f, rok ? q.w : 0.0f};
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx)
-            s += ldz(in, n, c, 2 * y - 1 + ky, 2 * x - 1 + kx);
-    s = s / 9.0f;
-    *at(out, n, c, y, x) = s;
+#pragma unroll
+            for (int p = 0; p < POOL_PX; ++p)
+                s[p] += v[2 * p + kx];
+    }
+#pragma unroll
+    for (int p = 0; p < POOL_PX; ++p)
+        s[p] = s[p] / 9.0f;
+    *reinterpret_cast<f32x2_t *>(at(out, n, c, y, x)) = f32x2_t{s[0], s[1]};
     if (bnp2)   // the inp2 slice of b2 = BR(131) over cat([output1, output1_0, inp2]) (Model.py:359)
-        *at(out2, n, coff2 + c, y, x) = bn_prelu(s, bnp2, C2, coff2 + c);
+        *reinterpret_cast<f32x2_t *>(at(out2, n, coff2 + c, y, x)) =
+            f32x2_t{bn_prelu(s[0], bnp2, C2, coff2 + c), bn_prelu(s[1], bnp2, C2, coff2 + c)};
 }
 
 // b2: cat([output1, output1_0, inp2]) -> BR(131).  reference: Model.py:359 (291)
@@ -718,6 +743,119 @@ __global__ void __launch_bounds__(256) dec3_kernel(const Dec3Args a)
         for (int dy = 0; dy < 2; ++dy)
             if (o < ncls)
                 *reinterpret_cast<float2 *>(at(a.e, n, o, 2 * y + dy, 2 * x)) = make_float2(up[o][dy][0], up[o][dy][1]);
+}
+
+// The five-class networks' form of the same stage, reading the cat RAW: planes 0..4 are level3_C as the stride-2 reduce wrote
+// it (F_SIDE1X1), planes 5..9 up_l3 as dec1_sums_kernel wrote it, and combine_l2_l3.0's BR(10) is applied to every value on
+// load -- the function and operands of dec2_br_kernel, which a forward therefore no longer needs (it runs only to materialise
+// the stage "combine_t" where a request keeps it).  Padding is zero AFTER the BR (BN of a zero is not zero): a select on the
+// normalised value, as F_BNLOAD's.
+// A thread owns a 2 x 2 block of 1/4-scale pixels (H/4 and W/4 are even: no tail).  Its 4 x 4 window of a plane is fetched row
+// by row from a row pointer -- the aligned 16 bytes that hold the thread's two columns, and one dword beside them: to the left
+// for the lane whose columns are the first two of the four, to the right for its neighbour -- normalised once and shared by
+// the four pixels; one-pixel-per-thread dec3_kernel spent more instructions on its 90 clamped loads than on its 550 FMAs.
+// The two pixels of a row are a pair in v_pk_fma_f32 with the weight broadcast, each component the IEEE operation of the scalar
+// form, and a pixel's accumulation order is dec3_kernel's: planes 0..9, then ky, then kx, one fmaf chain per output channel from
+// 0.0f; BN + PReLU; the 2x2 deconvolution's chain over i ascending; BR.  Same bits.  A pair's 2 x 2 results per output row are
+// one 16-byte store, and neighbouring lanes' stores are neighbours in memory: with four pixels of ONE row per thread a lane
+// owned 32 consecutive bytes, each store instruction filled every other 16, and the kernel took 66 us instead of 42
+// (profiles/lean_forward_ab.txt).
+struct Dec3CatArgs {
+    ActV l3c;            // level3_C, raw (CLS planes)
+    ActV o2c;            // up_l3, raw (CLS planes)
+    const float *br;     // combine_l2_l3.0 folded [3][2*CLS]
+    const float *wc;     // combine_l2_l3.1.conv.weight [CLS][2*CLS][3][3]
+    const float *bnc;    // combine_l2_l3.1 bn+act folded [3][CLS]
+    const float *wup;    // up_l2.0.weight [CLS][CLS][2][2]
+    const float *bnu;    // up_l2.1 folded [3][CLS]
+    ActV e;              // out: comb_l2_l3 at 1/2 scale, CLS channels
+    int N;
+};
+constexpr int DEC3_PX = 4;   // pixels per thread: 2 x 2
+
+__device__ __forceinline__ f32x2_t bn_prelu2(f32x2_t v, const float *bnp, int C, int c)
+{
+    const float alpha = bnp[2 * C + c], pin = alpha <= 1.0f ? __builtin_inff() : -__builtin_inff();
+    v = __builtin_elementwise_fma(v, (f32x2_t)(bnp[c]), (f32x2_t)(bnp[C + c]));
+    const f32x2_t av = v * alpha;
+    return f32x2_t{__builtin_amdgcn_fmed3f(v[0], av[0], pin), __builtin_amdgcn_fmed3f(v[1], av[1], pin)};
+}
+
+template <int CLS>
+__global__ void __launch_bounds__(256) dec3_cat_kernel(const Dec3CatArgs a)
+{
+    const int H2 = a.l3c.H, W2 = a.l3c.W, HB = H2 / 2, WB = W2 / 2;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)a.N * HB * WB)
+        return;
+    const int x = (int)(idx % WB) * 2;
+    const int y = (int)((idx / WB) % HB) * 2;
+    const int n = (int)(idx / ((long long)WB * HB));
+    // window rows y-1 .. y+2, columns x-1 .. x+2.  Columns x, x+1 lie in the aligned four that start at x & ~3 (inside the row's
+    // pitch, a multiple of 32 floats); `second`: they are its last two, and the dword beside the four is column x+2, else x-1
+    const bool second = x & 2;
+    const int x4 = x & ~3, xe = second ? min(x + 2, W2 - 1) : max(x - 1, 0);
+    const bool cok[4] = {x > 0, true, true, x + 2 < W2}, rok[4] = {y > 0, true, true, y + 2 < H2};
+    const int ry[4] = {max(y - 1, 0), y, y + 1, min(y + 2, H2 - 1)};
+    f32x2_t s[2][CLS];   // [row of the block][output channel], the row's two pixels
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int k = 0; k < CLS; ++k)
+            s[r][k] = (f32x2_t)(0.0f);
+    for (int c = 0; c < 2 * CLS; ++c) {
+        const bool lo = c < CLS;   // (uniform)
+        const float *plane = lo ? at(a.l3c, n, c, 0, 0) : at(a.o2c, n, c - CLS, 0, 0);
+        const int pitch = lo ? a.l3c.pitch : a.o2c.pitch;
+        f32x2_t w[4][2];   // the normalised window: [row][column pair]
+#pragma unroll
+        for (int wr = 0; wr < 4; ++wr) {
+            // branch-free (see ldz): clamp, load, normalise, select
+            const float *row = plane + ry[wr] * pitch;
+            const float4 q = *reinterpret_cast<const float4 *>(row + x4);
+            const float e = row[xe];
+            const f32x2_t t0 = bn_prelu2(f32x2_t{second ? q.y : e, second ? q.z : q.x}, a.br, 2 * CLS, c);
+            const f32x2_t t1 = bn_prelu2(f32x2_t{second ? q.w : q.y, second ? e : q.z}, a.br, 2 * CLS, c);
+            w[wr][0] = f32x2_t{rok[wr] && cok[0] ? t0[0] : 0.0f, rok[wr] ? t0[1] : 0.0f};
+            w[wr][1] = f32x2_t{rok[wr] ? t1[0] : 0.0f, rok[wr] && cok[3] ? t1[1] : 0.0f};
+        }
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+                for (int k = 0; k < CLS; ++k) {
+                    const f32x2_t wk = (f32x2_t)(a.wc[((k * 2 * CLS + c) * 3 + ky) * 3 + kx]);
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+                        const f32x2_t *wp = w[r + ky];   // the pair's taps: columns kx, kx + 1 of the window
+                        const f32x2_t v = kx == 0 ? wp[0] : kx == 1 ? f32x2_t{wp[0][1], wp[1][0]} : wp[1];
+                        s[r][k] = __builtin_elementwise_fma(wk, v, s[r][k]);
+                    }
+                }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+#pragma unroll
+        for (int k = 0; k < CLS; ++k)
+            s[r][k] = bn_prelu2(s[r][k], a.bnc, CLS, k);
+#pragma unroll
+        for (int o = 0; o < CLS; ++o)
+#pragma unroll
+            for (int dy = 0; dy < 2; ++dy) {
+                f32x2_t up[2];
+#pragma unroll
+                for (int dx = 0; dx < 2; ++dx) {
+                    f32x2_t t = (f32x2_t)(0.0f);
+#pragma unroll
+                    for (int i = 0; i < CLS; ++i)
+                        t = __builtin_elementwise_fma(s[r][i], (f32x2_t)(a.wup[((i * CLS + o) * 2 + dy) * 2 + dx]), t);
+                    up[dx] = bn_prelu2(t, a.bnu, CLS, o);
+                }
+                // output columns 2x .. 2x + 3: (pixel 0: dx 0, 1), (pixel 1: dx 0, 1)
+                st_stream<NT_DEC3_ST>(reinterpret_cast<f32x4_t *>(at(a.e, n, o, 2 * (y + r) + dy, 2 * x)), f32x4_t{up[0][0], up[1][0], up[0][1], up[1][1]});
+            }
+    }
 }
 
 // up_l2 alone: ConvTranspose2d(classes,classes,2,2) -> BR(classes) on the output of combine_l2_l3.1 when that convolution ran on the

@@ -118,6 +118,10 @@ struct ForwardPlan {
     bool l3c_in_reduce = false;   // the stride-2 reduce also writes level3_C's raw output (F_SIDE1X1); dec2 reads that
     bool cls_in_l3 = false;       // the level-3 down-sampler and the last ESP block also write the classifier's partial sums
                                   // (F_CLS1X1); dec1_sums_kernel adds them in dec1_kernel's place
+    bool lean = false;            // a fact of the REQUEST: no logits are asked for and both side sums are planned, so nothing of the
+                                  // forward reads output2 (the last level-3 block's map) -- that launch does not store it
+                                  // (F_CLS_ONLY) -- or the normalised cat, which dec2_br_kernel is then not launched for: the
+                                  // stages "level3.<q-1>" and "combine_t" do not exist after such a forward
     // one form code per launch class, in table order (the ABI's view of a plan)
     void codes(int *out) const { GS_LAUNCH_CLASSES(GS_PLAN_CODE) }
 };
@@ -160,8 +164,9 @@ constexpr form::l3_esp_last whole_row_l3_esp(int W3, bool no_vec)
 // What a forward of n tiles of H x W runs on a device with num_cus CUs, for ESPNet(classes, p, q) with cp = padded_classes(classes).
 // no_vec (GS_NO_VEC of -DGS_DIAG builds; false in the product) keeps every launch off the vector mappings and the small-batch forms.
 // (An ESPNet-C handle -- encoder_only -- stops before the decoder: its dec3 / dec_conv entries are not launched, and nothing of
-// it asks for level3_C.)
-inline ForwardPlan plan_forward(int n, int H, int W, int p, int q, int cp, int num_cus, bool no_vec, bool encoder_only = false)
+// it asks for level3_C.)  want_logits: whether the request has a logits buffer (ForwardReq::logits) -- it changes no form, only `lean`.
+inline ForwardPlan plan_forward(int n, int H, int W, int p, int q, int cp, int num_cus, bool no_vec, bool encoder_only = false,
+                                bool want_logits = true)
 {
     namespace f = form;
     const int W1 = W / 2, H2 = H / 4, W2 = W / 4, H3 = H / 8, W3 = W / 8;
@@ -170,6 +175,7 @@ inline ForwardPlan plan_forward(int n, int H, int W, int p, int q, int cp, int n
     pl.lazy_b2 = b2_is_lazy(p);
     pl.l3c_in_reduce = !encoder_only && l3c_side_sums(cp);   // in every form of the reduce: lazy or not, any task shape
     pl.cls_in_l3 = !encoder_only && cls_side_sums(cp, q);    // in every form of the two launches: a fact of the model only
+    pl.lean = !want_logits && pl.cls_in_l3 && pl.l3c_in_reduce;   // a full five-class network with q >= 1, asked for the mask only
 
     // ---- level 2.  Small batches: 32-pixel tasks (two pixels per lane) while there are at most CFG_SMALL2_WAVES of them per CU
     const bool small2 = CFG_SMALL2_WAVES > 0 && (long long)n * H2 * cdiv(W2, 64) * 2 <= cus * CFG_SMALL2_WAVES &&

@@ -339,6 +339,16 @@ def plan_cls_in_l3(n, height, width, p, q, classes, num_cus, encoder_only=False)
     return bool(flags.value & _lib.GS_PLAN_CLS_IN_L3)
 
 
+def plan_lean(n, height, width, p, q, classes, num_cus, encoder_only=False, want_logits=False):
+    """Whether a forward of this shape and model is lean when asked for logits or not: no logits, and both decoder projections
+    planned as side sums of their producers, so that the last level-3 launch stores no map and the stage "level3.<q-1>" does
+    not exist afterwards (gs_espnet_plan_lean, include/glomseg_lean.h).  Host-only: needs no GPU."""
+    lean = ctypes.c_int()
+    _lib.check(_lib.load().gs_espnet_plan_lean(n, height, width, p, q, classes, int(bool(encoder_only)), num_cus, int(bool(want_logits)),
+                                               ctypes.byref(lean)))
+    return bool(lean.value)
+
+
 def pack_weights(state_dict, classes=5, p=2, q=8, encoder_only=False):
     """(blob, pieces): the fp32 weight blob gs_espnet_create uploads for this model and {piece name: (float offset, floats)} of
     its pieces in order (gs_espnet_pack_weights, include/glomseg_plan.h).  Host-only: needs no GPU."""

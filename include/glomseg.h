@@ -348,7 +348,15 @@ gs_status gs_espnet_ensemble_forward(gs_espnet *const *models, int n_models, con
 /* Debug/test hook: copy one named intermediate activation of the LAST forward (image index
  * `image`) to host memory as contiguous CHW fp32.  Names follow tests/golden stage names
  * ("b1","level2_0","level2.0",...,"b2","level3_0","level3.7","up_l3","combine_t","up_l2",...).
- * dims receives {C,H,W}.  cap counts floats. */
+ * dims receives {C,H,W}.  cap counts floats.
+ * Which stages exist depends on the request.  A forward WITH a logits buffer leaves every stage of its model: the last two
+ * "level2.<i>" / "level3.<i>" (earlier ping-pong buffers are written again), "level3_C" where the stride-2 reduce computes it,
+ * "combine_t" (class counts without padding planes) and "conv".  A forward WITHOUT one (mask-only) leaves no "conv"; when it is
+ * lean (glomseg_lean.h: the full five-class networks with q >= 1) it also leaves no "combine_t" (the 3x3 normalises the raw cat
+ * on load and nothing materialises it) and no "level3.<q-1>" (the map its last level-3 launch does not store).  Everything else
+ * -- "b1", "sample2", "b2", "level3_0", "level3.<q-2>", "level3_C", "up_l3", "up_l2", ... -- reads the same after either kind, and
+ * a model that is never lean (another class count, q = 0, ESPNet-C) keeps every stage but "conv".  Asking for a stage the last
+ * forward did not leave is GS_ERR_INVALID; after a lean forward the message says to request logits. */
 gs_status gs_espnet_read_stage(gs_espnet *h, const char *stage, int image, float *dst, size_t cap,
                                int dims[3]);
 
