@@ -10,6 +10,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/glomseg_plan.h"
@@ -199,6 +200,56 @@ static ConvArgs conv_args(const Act &in, const float *wpack, const Act &out, con
     return a;
 }
 
+// The optional outputs of a conv launch, each added to the arguments conv_args made.
+// F_DUAL: the second store, through its own BN + PReLU, into planes coff.. of a concat buffer
+static ConvArgs with_dual(ConvArgs a, const Act &cat, int coff)
+{
+    a.out2 = cat.base;
+    a.out2_sn = cat.sn;
+    a.out2_sc = cat.sc;
+    a.out2_pitch = cat.pitch;
+    a.out2_off = cat.off;
+    a.out2_coff = coff;
+    a.out2_img_bytes = (unsigned)(cat.sn * sizeof(float));
+    return a;
+}
+// F_FUSE1X1: the next block's reduced map is written by this block's epilogue (the two maps alternate)
+static ConvArgs with_fused(ConvArgs a, const Act &r, int nout3)
+{
+    a.out3 = r.base;
+    a.out3_sn = r.sn;
+    a.out3_sc = r.sc;
+    a.out3_pitch = r.pitch;
+    a.out3_off = r.off;
+    a.out3_img_bytes = (unsigned)(r.sn * sizeof(float));
+    a.nout3 = nout3;
+    return a;
+}
+// F_SIDE1X1: the stride-2 reduce also writes level3_C's raw output
+static ConvArgs with_side(ConvArgs a, const Act &side)
+{
+    a.side = side.base;
+    a.side_sn = side.sn;
+    a.side_sc = side.sc;
+    a.side_pitch = side.pitch;
+    a.side_off = side.off;
+    a.side_img_bytes = (unsigned)(side.sn * sizeof(float));
+    return a;
+}
+// F_CLS1X1: the classifier's partial sums of one producer (0: output2_0, channels 0..127; 1: output2, 128..255; b3: its
+// channel records) go to its two groups of class planes in tt, which nothing reads or writes before dec2 (cls_side_sums,
+// espnet_facts.h).  `a` is a level-3 launch: a.H x a.W is the 1/8-scale map.
+static ConvArgs with_cls(ConvArgs a, const float *b3, const Act &tt, int producer)
+{
+    a.crec = b3 + (long long)producer * 128 * CLS_REC;
+    a.cls_sc = a.H * a.W;
+    a.cls_pitch = a.W;
+    a.cls = tt.base + (long long)producer * 2 * CLS_N * a.cls_sc;
+    a.cls_sn = tt.sn;
+    a.cls_img_bytes = (unsigned)((size_t)2 * CLS_N * a.cls_sc * sizeof(float));
+    return a;
+}
+
 static inline unsigned blocks_for(long long items) { return (unsigned)((items + 255) / 256); }
 
 // Timing / stamp variants of the forward (GS_VARIANT: ablations, per-wave stamps, the kernels a round replaced) live in
@@ -216,205 +267,159 @@ static inline unsigned blocks_for(long long items) { return (unsigned)((items + 
 #define GS_DIAG_TRY(call) \
     do {                  \
     } while (0)
-#define GS_DIAG_STAMPED(var, tag, ca, ...)
+#define GS_DIAG_STAMPED(F, S, block)
 #endif
 
 // ------------------------------------------------------------------------------------------
-// The per-class dispatch: every conv_mfma_kernel instantiation of the forward is spelled here, once -- one `case` per form of
-// forward_plan.h's table.  The forward (encode / decode) and the single-block hook (gs_espnet_block_forward) launch through these and decide
-// nothing themselves; the caller has put the second / third output of a fused form into `ca` (with_dual / with_fused).
+// The switchboard: every conv_mfma_kernel instantiation the forward can run is spelled here once, as the Spec of its form in
+// forward_plan.h's table.  The forward (encode / decode) and the single-block hook (gs_espnet_block_forward) launch through
+// launch_planned and decide nothing themselves; the caller has put a form's optional outputs into `ca` (with_dual .. with_cls).
 static gs_status not_planned(const char *launch_class)
 {
     set_error("internal: the forward plan has no form for launch class %s", launch_class);
     return GS_ERR_INVALID;
 }
 
-// The two pixel mappings of a unit-stride conv launch; `vec` (F_VEC) is the plan's decision.  (The level-2 small-batch forms
-// are only ever planned with it: their scalar twins are instantiated and never launched.)
-template <int FLAGS, int... C>
-static gs_status launch_vec(const ConvArgs &ca, int num_cus, hipStream_t s, bool vec)
+// A form's instantiation: its base mask (F_VEC and F_SKIP_PAD are the form's), the modifier bits a launch may OR onto it (MAY:
+// the side sums the plan asks for -- F_SIDE1X1, F_CLS1X1, F_CLS_ONLY) and its CFG_* tuple.  A modifier outside MAY is a pair the
+// plan never makes: launch_form refuses it and it is never instantiated.
+template <int FLAGS, int MAY, int... C>
+struct Inst {
+    static constexpr int flags = FLAGS, pixels = cfg_pixels(C...);
+    static constexpr bool carries(int extra) { return !(extra & ~MAY); }
+    template <int EXTRA>
+    static gs_status launch(const ConvArgs &ca, int num_cus, hipStream_t s) { return launch_conv_mfma<C..., FLAGS | EXTRA>(ca, num_cus, s); }
+};
+struct NotConv {   // a row that is no conv launch: a plain kernel, or a decoder shape at a class count of the other MFMA shape
+    static constexpr bool carries(int) { return false; }
+};
+// Spec<class, form, CLS>: one per row of the table (a row without one does not compile); CLS is the decoder's padded class count
+template <typename E, E F, int CLS>
+struct Spec;
+#define GS_SPEC(id, ...) \
+    template <int CLS>   \
+    struct Spec<decltype(form::id), form::id, CLS> : __VA_ARGS__ {};
+
+// the level-2 branch kernels.  The down-sampler stores the raw output only, with or without ESP blocks behind it: b2 is applied
+// by the consumers (p > 0: the level-3 stride-2 reduce and dec2 on load; p == 0: cat_b2_kernel)
+constexpr int L2_DOWN = F_BNACT | (POL_L2_DOWN & F_ST_NT), L2_ESP = F_BNACT | F_RES | POL_L2_ESP;
+constexpr int L2_LAST = F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST;
+GS_SPEC(l2_down::P2S_VEC, Inst<L2_DOWN | FUSE_L2 | F_VEC, 0, CFG_L2_BR_P2S>)
+GS_SPEC(l2_down::P4S_VEC_SKIP, Inst<L2_DOWN | FUSE_L2 | F_VEC | F_SKIP_PAD, 0, CFG_L2_BR_P4S>)
+GS_SPEC(l2_down::P4_VEC, Inst<L2_DOWN | FUSE_L2 | F_VEC, 0, CFG_L2_BR_P4>)
+GS_SPEC(l2_down::P4, Inst<L2_DOWN | FUSE_L2, 0, CFG_L2_BR_P4>)
+GS_SPEC(l2_down::UNFUSED_P4_VEC, Inst<L2_DOWN | F_VEC, 0, CFG_L2_BR_P4>)
+GS_SPEC(l2_down::UNFUSED_P4, Inst<L2_DOWN, 0, CFG_L2_BR_P4>)
+GS_SPEC(l2_esp_fused::P2S_VEC, Inst<L2_ESP | FUSE_L2 | F_VEC, 0, CFG_L2_BR_P2S>)
+GS_SPEC(l2_esp_fused::P4_VEC, Inst<L2_ESP | FUSE_L2 | F_VEC, 0, CFG_L2_BR_P4>)
+GS_SPEC(l2_esp_fused::P4, Inst<L2_ESP | FUSE_L2, 0, CFG_L2_BR_P4>)
+GS_SPEC(l2_esp_fused::UNFUSED_P4_VEC, Inst<L2_ESP | F_VEC, 0, CFG_L2_BR_P4>)
+GS_SPEC(l2_esp_fused::UNFUSED_P4, Inst<L2_ESP, 0, CFG_L2_BR_P4>)
+GS_SPEC(l2_esp_last::P2S_VEC, Inst<L2_LAST | F_VEC, 0, CFG_L2_BR_P2S>)
+GS_SPEC(l2_esp_last::P4_VEC, Inst<L2_LAST | F_VEC, 0, CFG_L2_BR_P4>)
+GS_SPEC(l2_esp_last::P4, Inst<L2_LAST, 0, CFG_L2_BR_P4>)
+GS_SPEC(cat_b2::KERNEL, NotConv)
+// the level-3 stride-2 reduce (the F_BNLOAD forms: planes 64..127 of output1_cat hold output1_0 RAW, b2 is applied to the B
+// operands on load); every form can also compute the five-class level3_C (F_SIDE1X1)
+constexpr int L3_REDUCE = F_S2PAIR | POL_L3_C1S | S2FLIP_L3;
+GS_SPEC(l3_reduce::BNL_P1, Inst<L3_REDUCE | F_BNLOAD, F_SIDE1X1(5), CFG_L3_C1S_BNL_P1>)
+GS_SPEC(l3_reduce::BNL, Inst<L3_REDUCE | F_BNLOAD, F_SIDE1X1(5), CFG_L3_C1S_BNL>)
+GS_SPEC(l3_reduce::C1S, Inst<L3_REDUCE, F_SIDE1X1(5), CFG_L3_C1S>)
+// the level-3 branch kernels.  The classifier's side sums (F_CLS1X1) go with every form the plan pairs them with: not the unfused
+// forms (cls_side_sums) or the down-sampler's four-pixel one (plan_forward); only the network's last block may drop its map (F_CLS_ONLY)
+constexpr int L3_DOWN = F_BNACT | POL_L3_DOWN | FUSE_L3, L3_ESP = F_BNACT | F_RES | POL_L3_ESP;
+constexpr int AGL_SMALL = CFG_SMALL_AGL ? F_A_GLOBAL : 0;
+GS_SPEC(l3_down::P1R, Inst<L3_DOWN | SKIP_L3 | AGL_SMALL, F_CLS1X1, CFG_L3_BR_P1R>)
+GS_SPEC(l3_down::P2R_VEC, Inst<L3_DOWN | F_VEC | SKIP_L3, F_CLS1X1, CFG_L3_BR_P2R>)
+GS_SPEC(l3_down::BR_VEC, Inst<L3_DOWN | F_VEC, 0, CFG_L3_BR>)
+GS_SPEC(l3_down::P2F, Inst<L3_DOWN, F_CLS1X1, CFG_L3_BR_P2F>)
+GS_SPEC(l3_down::UNFUSED_BR_VEC, Inst<F_BNACT | POL_L3_DOWN | F_VEC, 0, CFG_L3_BR>)
+GS_SPEC(l3_down::UNFUSED_BR, Inst<F_BNACT | POL_L3_DOWN, 0, CFG_L3_BR>)
+GS_SPEC(l3_esp_fused::P1R, Inst<L3_ESP | FUSE_L3 | SKIP_L3 | AGL_SMALL, 0, CFG_L3_BR_P1R>)
+GS_SPEC(l3_esp_fused::P2R_VEC, Inst<L3_ESP | FUSE_L3 | F_VEC | SKIP_L3, 0, CFG_L3_BR_P2R>)
+GS_SPEC(l3_esp_fused::P2F, Inst<F_BNACT | F_RES | FUSE_L3, 0, CFG_L3_BR_P2F>)
+GS_SPEC(l3_esp_last::P1R, Inst<L3_ESP | SKIP_L3 | AGL_SMALL, F_CLS1X1 | F_CLS_ONLY, CFG_L3_BR_P1R>)
+GS_SPEC(l3_esp_last::P2R_VEC, Inst<L3_ESP | F_VEC | SKIP_L3, F_CLS1X1 | F_CLS_ONLY, CFG_L3_BR_P2R>)   // tap rows in the halo skipped
+GS_SPEC(l3_esp_last::BR_VEC, Inst<L3_ESP | F_VEC, F_CLS1X1 | F_CLS_ONLY, CFG_L3_BR>)
+GS_SPEC(l3_esp_last::P2, Inst<F_BNACT | F_RES, F_CLS1X1 | F_CLS_ONLY, CFG_L3_BR_P2>)
+// The decoder's 3x3 convolutions as plain conv_mfma launches (MFMA rows = the padded output channels, BN + PReLU in the
+// epilogue).  The shape is a property of the class count: the plan names it from the same CLS = Model::cp (dec_mt), and a form
+// of the other shape is no launch at this CLS.
+// (Deeper operand rings and four pixels per lane were measured on the conv launch: no gain -- at twenty classes it is at 90 % of
+// what its padded matrix work allows, 20 of 32 rows.)
+template <int CLS, int MT, int FLAGS, int CINP>
+using DecInst = std::conditional_t<dec_mt(CLS) == MT, Inst<FLAGS, 0, MT, 8, CINP, 9, 1, 1, CLS, CLS, dec_pixels(CLS), 3>, NotConv>;
+constexpr int dec_conv_cinp(int cls) { return (19 + cls + 3) / 4 * 4; }
+GS_SPEC(dec3::KERNEL, NotConv)
+GS_SPEC(dec3::MT16, DecInst<CLS, 16, F_BNACT, 2 * CLS>)
+GS_SPEC(dec3::MT16_VEC, DecInst<CLS, 16, F_BNACT | F_VEC, 2 * CLS>)
+GS_SPEC(dec3::MT32, DecInst<CLS, 32, F_BNACT, 2 * CLS>)
+GS_SPEC(dec3::MT32_VEC, DecInst<CLS, 32, F_BNACT | F_VEC, 2 * CLS>)
+GS_SPEC(dec_conv::TAIL, NotConv)
+GS_SPEC(dec_conv::MT16, DecInst<CLS, 16, F_BNACT | POL_DEC_CONV, dec_conv_cinp(CLS)>)
+GS_SPEC(dec_conv::MT16_VEC, DecInst<CLS, 16, F_BNACT | POL_DEC_CONV | F_VEC, dec_conv_cinp(CLS)>)
+GS_SPEC(dec_conv::MT32, DecInst<CLS, 32, F_BNACT | POL_DEC_CONV, dec_conv_cinp(CLS)>)
+GS_SPEC(dec_conv::MT32_VEC, DecInst<CLS, 32, F_BNACT | POL_DEC_CONV | F_VEC, dec_conv_cinp(CLS)>)
+#undef GS_SPEC
+
+// One form's launch: its spec with EXTRA on top (`what`: the launch class, for the refusal; `block`: the ESP block's index, which a
+// stamp variant of -DGS_DIAG builds asks for).  The table's vector width is the spec's: vec_fits trusts the one, the kernel runs the other.
+template <auto F, int EXTRA, int CLS>
+static gs_status launch_form(const Model *m, const ConvArgs &ca, hipStream_t s, int block, const char *what)
 {
-    return vec ? launch_conv_mfma<C..., FLAGS | F_VEC>(ca, num_cus, s) : launch_conv_mfma<C..., FLAGS>(ca, num_cus, s);
+    using S = Spec<decltype(F), F, CLS>;
+    if constexpr (!S::carries(EXTRA)) {
+        return not_planned(what);
+    } else {
+        static_assert((S::flags & F_VEC) ? pixels_per_lane(F) == S::pixels : pixels_per_lane(F) == 0,
+                      "forward_plan.h's pixels per lane of a form is not the vector width of its Spec");
+        if constexpr (EXTRA == 0) {   // (the side sums refuse every F_X_* flag)
+            GS_DIAG_STAMPED(F, S, block)
+        }
+        return S::template launch<EXTRA>(ca, m->num_cus, s);
+    }
 }
+// launch_planned<EXTRA, CLS>(m, form, ca, s): the one switch of each launch class, a `case` per row of its table
+#define GS_FORM_CASE(id, name, ppl) \
+    case F::id: return launch_form<F::id, EXTRA, CLS>(m, ca, s, block, what);
+#define GS_CLASS_SWITCH(cls, FORMS)                                                                                                \
+    template <int EXTRA = 0, int CLS = 0>                                                                                          \
+    static gs_status launch_planned(const Model *m, form::cls f, const ConvArgs &ca, hipStream_t s, int block = -1, const char *what = #cls) \
+    {                                                                                                                              \
+        using F = form::cls;                                                                                                       \
+        switch (f) {                                                                                                               \
+            FORMS(GS_FORM_CASE)                                                                                                    \
+        case F::none: break;                                                                                                       \
+        }                                                                                                                          \
+        return not_planned(what);                                                                                                  \
+    }
+GS_LAUNCH_CLASSES(GS_CLASS_SWITCH)
+#undef GS_FORM_CASE
+#undef GS_CLASS_SWITCH
 
 // the launches that have one form: the level-2 stride-2 reduce and the 1x1 reduces that no epilogue computed
 static gs_status launch_l2_reduce(const Model *m, const ConvArgs &ca, hipStream_t s) { return launch_conv_mfma<CFG_L2_C1S, F_S2PAIR | POL_L2_C1S | S2FLIP_L2>(ca, m->num_cus, s); }
 static gs_status launch_l2_c1(const Model *m, const ConvArgs &ca, hipStream_t s) { return launch_conv_mfma<CFG_L2_C1, POL_L2_C1>(ca, m->num_cus, s); }   // 1x1: the run mapping measured no slower
 static gs_status launch_l3_c1(const Model *m, const ConvArgs &ca, hipStream_t s) { return launch_conv_mfma<CFG_L3_C1, POL_L3_C1>(ca, m->num_cus, s); }
 
-// the raw output only, with or without ESP blocks behind it: b2 is applied by the consumers (p > 0: the level-3 stride-2
-// reduce and dec2 on load; p == 0: cat_b2_kernel)
-static gs_status launch_l2_down(const Model *m, form::l2_down f, const ConvArgs &ca, hipStream_t s)
-{
-    switch (f) {
-    case form::l2_down::P2S_VEC: return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2, CFG_L2_BR_P2S>(ca, m->num_cus, s, true);
-    case form::l2_down::P4S_VEC_SKIP:
-        GS_DIAG_STAMPED(162, "l2down", ca, F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2 | F_VEC, CFG_L2_BR_P4)
-        return launch_conv_mfma<CFG_L2_BR_P4S, F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2 | F_VEC | F_SKIP_PAD>(ca, m->num_cus, s);
-    case form::l2_down::P4_VEC:
-        GS_DIAG_STAMPED(162, "l2down", ca, F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2 | F_VEC, CFG_L2_BR_P4)
-        return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2, CFG_L2_BR_P4>(ca, m->num_cus, s, true);
-    case form::l2_down::P4: return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT) | FUSE_L2, CFG_L2_BR_P4>(ca, m->num_cus, s, false);
-    case form::l2_down::UNFUSED_P4_VEC: return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT), CFG_L2_BR_P4>(ca, m->num_cus, s, true);
-    case form::l2_down::UNFUSED_P4: return launch_vec<F_BNACT | (POL_L2_DOWN & F_ST_NT), CFG_L2_BR_P4>(ca, m->num_cus, s, false);
-    case form::l2_down::none: break;
-    }
-    return not_planned("l2_down");
-}
-
-static gs_status launch_l2_esp_fused(const Model *m, form::l2_esp_fused f, const ConvArgs &ca, hipStream_t s)
-{
-    switch (f) {
-    case form::l2_esp_fused::P2S_VEC: return launch_vec<F_BNACT | F_RES | POL_L2_ESP | FUSE_L2, CFG_L2_BR_P2S>(ca, m->num_cus, s, true);
-    case form::l2_esp_fused::P4_VEC:
-        GS_DIAG_STAMPED(161, "l2esp", ca, F_BNACT | F_RES | POL_L2_ESP | FUSE_L2 | F_VEC, CFG_L2_BR_P4)
-        return launch_vec<F_BNACT | F_RES | POL_L2_ESP | FUSE_L2, CFG_L2_BR_P4>(ca, m->num_cus, s, true);
-    case form::l2_esp_fused::P4: return launch_vec<F_BNACT | F_RES | POL_L2_ESP | FUSE_L2, CFG_L2_BR_P4>(ca, m->num_cus, s, false);
-    case form::l2_esp_fused::UNFUSED_P4_VEC: return launch_vec<F_BNACT | F_RES | POL_L2_ESP, CFG_L2_BR_P4>(ca, m->num_cus, s, true);
-    case form::l2_esp_fused::UNFUSED_P4: return launch_vec<F_BNACT | F_RES | POL_L2_ESP, CFG_L2_BR_P4>(ca, m->num_cus, s, false);
-    case form::l2_esp_fused::none: break;
-    }
-    return not_planned("l2_esp_fused");
-}
-
-static gs_status launch_l2_esp_last(const Model *m, form::l2_esp_last f, const ConvArgs &ca, hipStream_t s)
-{
-    switch (f) {
-    case form::l2_esp_last::P2S_VEC: return launch_vec<F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST, CFG_L2_BR_P2S>(ca, m->num_cus, s, true);
-    case form::l2_esp_last::P4_VEC:
-        GS_DIAG_STAMPED(163, "l2last", ca, F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST | F_VEC, CFG_L2_BR_P4)
-        return launch_vec<F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST, CFG_L2_BR_P4>(ca, m->num_cus, s, true);
-    case form::l2_esp_last::P4: return launch_vec<F_BNACT | F_RES | F_NOSTORE | F_DUAL | POL_L2_LAST, CFG_L2_BR_P4>(ca, m->num_cus, s, false);
-    case form::l2_esp_last::none: break;
-    }
-    return not_planned("l2_esp_last");
-}
-
-// (the F_BNLOAD forms: planes 64..127 of output1_cat hold output1_0 RAW, b2 is applied to the B operands on load)
-// side5: the plan's l3c_in_reduce -- every form also computes the five-class level3_C into ca.side (F_SIDE1X1)
+// ... and those whose modifier is the plan's: EXTRA is picked here, once.
+// side5: the plan's l3c_in_reduce -- the five-class level3_C goes to ca.side (with_side)
 static gs_status launch_l3_reduce(const Model *m, form::l3_reduce f, bool side5, const ConvArgs &ca, hipStream_t s)
 {
-    constexpr int SIDE5 = F_SIDE1X1(5);
-    if (side5)
-        switch (f) {
-        case form::l3_reduce::BNL_P1: return launch_conv_mfma<CFG_L3_C1S_BNL_P1, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD | SIDE5>(ca, m->num_cus, s);
-        case form::l3_reduce::BNL: return launch_conv_mfma<CFG_L3_C1S_BNL, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD | SIDE5>(ca, m->num_cus, s);
-        case form::l3_reduce::C1S: return launch_conv_mfma<CFG_L3_C1S, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | SIDE5>(ca, m->num_cus, s);
-        case form::l3_reduce::none: return not_planned("l3_reduce");
-        }
-    switch (f) {
-    case form::l3_reduce::BNL_P1: return launch_conv_mfma<CFG_L3_C1S_BNL_P1, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD>(ca, m->num_cus, s);
-    case form::l3_reduce::BNL:
-        GS_DIAG_STAMPED(165, "l3c1s", ca, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD, CFG_L3_C1S_BNL)
-        return launch_conv_mfma<CFG_L3_C1S_BNL, F_S2PAIR | POL_L3_C1S | S2FLIP_L3 | F_BNLOAD>(ca, m->num_cus, s);
-    case form::l3_reduce::C1S: return launch_conv_mfma<CFG_L3_C1S, F_S2PAIR | POL_L3_C1S | S2FLIP_L3>(ca, m->num_cus, s);
-    case form::l3_reduce::none: break;
-    }
-    return not_planned("l3_reduce");
+    return side5 ? launch_planned<F_SIDE1X1(5)>(m, f, ca, s) : launch_planned(m, f, ca, s);
 }
-
-// cls5: the plan's cls_in_l3 -- every form the plan picks with it also sums the five-class classifier's channels 0..127 into
-// ca.cls (F_CLS1X1); the unfused forms (cls_side_sums) and the four-pixel one (plan_forward) are never planned with it
+// cls5: the plan's cls_in_l3 -- the five-class classifier's channels 0..127 are summed into ca.cls (with_cls)
 static gs_status launch_l3_down(const Model *m, form::l3_down f, bool cls5, const ConvArgs &ca, hipStream_t s)
 {
-    if (cls5)
-        switch (f) {
-        case form::l3_down::P1R: return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | POL_L3_DOWN | FUSE_L3 | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0) | F_CLS1X1>(ca, m->num_cus, s);
-        case form::l3_down::P2R_VEC: return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | POL_L3_DOWN | FUSE_L3 | F_VEC | SKIP_L3 | F_CLS1X1>(ca, m->num_cus, s);
-        case form::l3_down::P2F: return launch_conv_mfma<CFG_L3_BR_P2F, F_BNACT | POL_L3_DOWN | FUSE_L3 | F_CLS1X1>(ca, m->num_cus, s);
-        default: return not_planned("l3_down with the classifier's side sums");
-        }
-    switch (f) {
-    case form::l3_down::P1R: return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | POL_L3_DOWN | FUSE_L3 | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(ca, m->num_cus, s);
-    case form::l3_down::P2R_VEC:
-        GS_DIAG_STAMPED(164, "l3down", ca, F_BNACT | POL_L3_DOWN | FUSE_L3 | F_VEC | SKIP_L3, CFG_L3_BR_P2R)
-        return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | POL_L3_DOWN | FUSE_L3 | F_VEC | SKIP_L3>(ca, m->num_cus, s);
-    case form::l3_down::BR_VEC: return launch_conv_mfma<CFG_L3_BR, F_BNACT | POL_L3_DOWN | FUSE_L3 | F_VEC>(ca, m->num_cus, s);
-    case form::l3_down::P2F: return launch_conv_mfma<CFG_L3_BR_P2F, F_BNACT | POL_L3_DOWN | FUSE_L3>(ca, m->num_cus, s);
-    case form::l3_down::UNFUSED_BR_VEC: return launch_vec<F_BNACT | POL_L3_DOWN, CFG_L3_BR>(ca, m->num_cus, s, true);
-    case form::l3_down::UNFUSED_BR: return launch_vec<F_BNACT | POL_L3_DOWN, CFG_L3_BR>(ca, m->num_cus, s, false);
-    case form::l3_down::none: break;
-    }
-    return not_planned("l3_down");
+    return cls5 ? launch_planned<F_CLS1X1>(m, f, ca, s, -1, "l3_down with the classifier's side sums") : launch_planned(m, f, ca, s);
 }
-
-// `block`: the ESP block's index (a stamp variant of -DGS_DIAG builds takes block 1)
-static gs_status launch_l3_esp_fused(const Model *m, form::l3_esp_fused f, const ConvArgs &ca, int block, hipStream_t s)
-{
-    switch (f) {
-    case form::l3_esp_fused::P1R: return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | F_RES | POL_L3_ESP | FUSE_L3 | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(ca, m->num_cus, s);
-    case form::l3_esp_fused::P2R_VEC:
-        if (block == 1) {
-            GS_DIAG_STAMPED(160, "l3esp", ca, F_BNACT | F_RES | F_VEC | POL_L3_ESP | FUSE_L3 | SKIP_L3, CFG_L3_BR_P2R)
-        }
-        return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | F_RES | F_VEC | POL_L3_ESP | FUSE_L3 | SKIP_L3>(ca, m->num_cus, s);
-    case form::l3_esp_fused::P2F: return launch_conv_mfma<CFG_L3_BR_P2F, F_BNACT | F_RES | FUSE_L3>(ca, m->num_cus, s);
-    case form::l3_esp_fused::none: break;
-    }
-    return not_planned("l3_esp_fused");
-}
-
 // cls5: as launch_l3_down's, for the network's last block: channels 128..255.  cls_only: the plan's `lean` -- nothing of this forward
-// reads that block's map, so every form runs without its primary store (F_CLS_ONLY)
+// reads that block's map, so it runs without its primary store; a block without the sums has nothing but its map and keeps it
 static gs_status launch_l3_esp_last(const Model *m, form::l3_esp_last f, bool cls5, bool cls_only, const ConvArgs &ca, hipStream_t s)
 {
-    if (cls5 && cls_only)
-        switch (f) {
-        case form::l3_esp_last::P1R: return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | F_RES | POL_L3_ESP | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0) | F_CLS1X1 | F_CLS_ONLY>(ca, m->num_cus, s);
-        case form::l3_esp_last::P2R_VEC: return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | F_RES | F_VEC | POL_L3_ESP | SKIP_L3 | F_CLS1X1 | F_CLS_ONLY>(ca, m->num_cus, s);
-        case form::l3_esp_last::BR_VEC: return launch_conv_mfma<CFG_L3_BR, F_BNACT | F_RES | F_VEC | POL_L3_ESP | F_CLS1X1 | F_CLS_ONLY>(ca, m->num_cus, s);
-        case form::l3_esp_last::P2: return launch_conv_mfma<CFG_L3_BR_P2, F_BNACT | F_RES | F_CLS1X1 | F_CLS_ONLY>(ca, m->num_cus, s);
-        case form::l3_esp_last::none: return not_planned("l3_esp_last");
-        }
-    if (cls5)
-        switch (f) {
-        case form::l3_esp_last::P1R: return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | F_RES | POL_L3_ESP | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0) | F_CLS1X1>(ca, m->num_cus, s);
-        case form::l3_esp_last::P2R_VEC: return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | F_RES | F_VEC | POL_L3_ESP | SKIP_L3 | F_CLS1X1>(ca, m->num_cus, s);
-        case form::l3_esp_last::BR_VEC: return launch_conv_mfma<CFG_L3_BR, F_BNACT | F_RES | F_VEC | POL_L3_ESP | F_CLS1X1>(ca, m->num_cus, s);
-        case form::l3_esp_last::P2: return launch_conv_mfma<CFG_L3_BR_P2, F_BNACT | F_RES | F_CLS1X1>(ca, m->num_cus, s);
-        case form::l3_esp_last::none: return not_planned("l3_esp_last");
-        }
-    switch (f) {
-    case form::l3_esp_last::P1R: return launch_conv_mfma<CFG_L3_BR_P1R, F_BNACT | F_RES | POL_L3_ESP | SKIP_L3 | (CFG_SMALL_AGL ? F_A_GLOBAL : 0)>(ca, m->num_cus, s);
-    case form::l3_esp_last::P2R_VEC: return launch_conv_mfma<CFG_L3_BR_P2R, F_BNACT | F_RES | F_VEC | POL_L3_ESP | SKIP_L3>(ca, m->num_cus, s);   // tap rows in the halo skipped
-    case form::l3_esp_last::BR_VEC: return launch_conv_mfma<CFG_L3_BR, F_BNACT | F_RES | F_VEC | POL_L3_ESP>(ca, m->num_cus, s);
-    case form::l3_esp_last::P2: return launch_conv_mfma<CFG_L3_BR_P2, F_BNACT | F_RES>(ca, m->num_cus, s);
-    case form::l3_esp_last::none: break;
-    }
-    return not_planned("l3_esp_last");
-}
-
-// The decoder's 3x3 convolutions as plain conv_mfma launches (MFMA rows = the padded output channels, BN + PReLU in the
-// epilogue).  The shape is a property of the instantiation: the plan names it from the same CLS = Model::cp (dec_mt).
-// (Deeper operand rings and four pixels per lane were measured on the conv launch: no gain -- at twenty classes it is at 90 % of
-// what its padded matrix work allows, 20 of 32 rows.)
-template <int CLS>
-static gs_status launch_dec3(const Model *m, form::dec3 f, const ConvArgs &ca, hipStream_t s)
-{
-    switch (f) {
-    case form::dec3::MT16:
-    case form::dec3::MT32: return launch_vec<F_BNACT, dec_mt(CLS), 8, 2 * CLS, 9, 1, 1, CLS, CLS, dec_pixels(CLS), 3>(ca, m->num_cus, s, false);
-    case form::dec3::MT16_VEC:
-    case form::dec3::MT32_VEC: return launch_vec<F_BNACT, dec_mt(CLS), 8, 2 * CLS, 9, 1, 1, CLS, CLS, dec_pixels(CLS), 3>(ca, m->num_cus, s, true);
-    case form::dec3::KERNEL:
-    case form::dec3::none: break;
-    }
-    return not_planned("dec3");
-}
-
-template <int CLS>
-static gs_status launch_dec_conv(const Model *m, form::dec_conv f, const ConvArgs &ca, hipStream_t s)
-{
-    constexpr int CINP = (19 + CLS + 3) / 4 * 4;
-    switch (f) {
-    case form::dec_conv::MT16:
-    case form::dec_conv::MT32: return launch_vec<F_BNACT | POL_DEC_CONV, dec_mt(CLS), 8, CINP, 9, 1, 1, CLS, CLS, dec_pixels(CLS), 3>(ca, m->num_cus, s, false);
-    case form::dec_conv::MT16_VEC:
-    case form::dec_conv::MT32_VEC: return launch_vec<F_BNACT | POL_DEC_CONV, dec_mt(CLS), 8, CINP, 9, 1, 1, CLS, CLS, dec_pixels(CLS), 3>(ca, m->num_cus, s, true);
-    case form::dec_conv::TAIL:
-    case form::dec_conv::none: break;
-    }
-    return not_planned("dec_conv");
+    if (!cls5)
+        return launch_planned(m, f, ca, s);
+    return cls_only ? launch_planned<F_CLS1X1 | F_CLS_ONLY>(m, f, ca, s) : launch_planned<F_CLS1X1>(m, f, ca, s);
 }
 
 // The forward is the encoder (stem .. the last level-3 block), the same code for every class count, then the decoder instantiated
@@ -470,44 +475,12 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
     // only its b2-normalised form (planes 0..63 of output1_cat), the pool kernel writes planes 128..130 normalised, and
     // output1_0 is stored RAW into planes 64..127 (lazy b2, espnet_config.h: the consumers normalise on load).  With p == 0
     // the unfused cat kernel runs.
-    auto with_dual = [&](ConvArgs a, int coff) {
-        a.out2 = m->a1.base;
-        a.out2_sn = m->a1.sn;
-        a.out2_sc = m->a1.sc;
-        a.out2_pitch = m->a1.pitch;
-        a.out2_off = m->a1.off;
-        a.out2_coff = coff;
-        a.out2_img_bytes = (unsigned)(m->a1.sn * sizeof(float));
-        return a;
-    };
-    // F_FUSE1X1: the next block's reduced map is written by this block's epilogue (the two maps alternate)
-    auto with_fused = [&](ConvArgs a, const Act &r, int nout3) {
-        a.out3 = r.base;
-        a.out3_sn = r.sn;
-        a.out3_sc = r.sc;
-        a.out3_pitch = r.pitch;
-        a.out3_off = r.off;
-        a.out3_img_bytes = (unsigned)(r.sn * sizeof(float));
-        a.nout3 = nout3;
-        return a;
-    };
-    // F_CLS1X1: the classifier's partial sums of one producer (0: output2_0, channels 0..127; 1: output2, 128..255) go to its
-    // two groups of class planes in tt, which nothing reads or writes before dec2 (cls_side_sums, espnet_facts.h)
-    auto with_cls = [&](ConvArgs a, int producer) {
-        a.crec = wb + m->w.b3 + (long long)producer * 128 * CLS_REC;
-        a.cls_sc = H3 * W3;
-        a.cls_pitch = W3;
-        a.cls = m->tt.base + (long long)producer * 2 * CLS_N * a.cls_sc;
-        a.cls_sn = m->tt.sn;
-        a.cls_img_bytes = (unsigned)((size_t)2 * CLS_N * a.cls_sc * sizeof(float));
-        return a;
-    };
     const bool lazy_b2 = plan.lazy_b2;
     m->b2_lazy = lazy_b2;
     int rd2 = 0;   // index of the reduced map the next level-2 branch kernel reads
     L.run(K_L2_DOWN, px2 * (12 * 9 * 64 * 2) + (m->w.l2_0.fused_next ? px2 * (64 * 12 * 2) : 0), [&] {
         const ConvArgs ca = conv_args(m->r2[rd2], wb + m->w.l2_0.br, m->bb[0], nullptr, n);
-        return launch_l2_down(m, plan.l2_down, m->w.l2_0.fused_next ? with_fused(ca, m->r2[rd2 ^ 1], 12) : ca, s);
+        return launch_planned(m, plan.l2_down, m->w.l2_0.fused_next ? with_fused(ca, m->r2[rd2 ^ 1], 12) : ca, s);
     });
     bool have_r2 = m->w.l2_0.fused_next;   // the reduced map of the next block already exists
     rd2 ^= have_r2 ? 1 : 0;
@@ -524,8 +497,8 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
         L.run(K_L2_ESP, px2 * (12 * 9 * 64 * 2) + (fuse_next ? px2 * (64 * 12 * 2) : 0), [&] {
             const ConvArgs ca = conv_args(m->r2[rd2], wb + m->w.l2[i].br, m->bb[nxt], &m->bb[cur2], n);
             if (last)
-                return launch_l2_esp_last(m, plan.l2_esp_last, with_dual(ca, 0), s);
-            return launch_l2_esp_fused(m, plan.l2_esp_fused, fuse_next ? with_fused(ca, m->r2[rd2 ^ 1], 12) : ca, s);
+                return launch_planned(m, plan.l2_esp_last, with_dual(ca, m->a1, 0), s);
+            return launch_planned(m, plan.l2_esp_fused, fuse_next ? with_fused(ca, m->r2[rd2 ^ 1], 12) : ca, s);
         });
         have_r2 = fuse_next;
         rd2 ^= have_r2 ? 1 : 0;
@@ -551,15 +524,7 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
             ca.bnl_s0 = 64 / 2;      // k-groups of two channels
             ca.bnl_s1 = 128 / 2;
         }
-        if (plan.l3c_in_reduce) {
-            ca.side = m->l3c.base;
-            ca.side_sn = m->l3c.sn;
-            ca.side_sc = m->l3c.sc;
-            ca.side_pitch = m->l3c.pitch;
-            ca.side_off = m->l3c.off;
-            ca.side_img_bytes = (unsigned)(m->l3c.sn * sizeof(float));
-        }
-        return launch_l3_reduce(m, plan.l3_reduce, plan.l3c_in_reduce, ca, s);
+        return launch_l3_reduce(m, plan.l3_reduce, plan.l3c_in_reduce, plan.l3c_in_reduce ? with_side(ca, m->l3c) : ca, s);
     });
     if (plan.l3c_in_reduce)
         m->set_stage("level3_C", m->l3c, m->classes);
@@ -571,7 +536,7 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
                 set_error("internal: the classifier's partial planes do not fit the workspace's tt");
                 return GS_ERR_INVALID;
             }
-            ca = with_cls(ca, 0);
+            ca = with_cls(ca, wb + m->w.b3, m->tt, 0);
         }
         return launch_l3_down(m, plan.l3_down, plan.cls_in_l3, m->w.l3_0.fused_next ? with_fused(ca, m->r3[rd3 ^ 1], 25) : ca, s);
     });
@@ -591,9 +556,9 @@ static Encoded encode(Model *m, Launcher &L, const ForwardPlan &plan, const Forw
             const ConvArgs ca = conv_args(m->r3[rd3], wb + m->w.l3[i].br, m->cc[nxt], &m->cc[cur3], n);
             GS_DIAG_TRY(diag_l3_esp(m, ca, i, s, dst_));
             if (fuse_next)
-                return launch_l3_esp_fused(m, plan.l3_esp_fused, with_fused(ca, m->r3[rd3 ^ 1], 25), i, s);
+                return launch_planned(m, plan.l3_esp_fused, with_fused(ca, m->r3[rd3 ^ 1], 25), s, i);
             const bool cls5 = plan.cls_in_l3 && i == m->q - 1;   // the network's last block holds output2
-            return launch_l3_esp_last(m, plan.l3_esp_last, cls5, plan.lean, cls5 ? with_cls(ca, 1) : ca, s);
+            return launch_l3_esp_last(m, plan.l3_esp_last, cls5, plan.lean, cls5 ? with_cls(ca, wb + m->w.b3, m->tt, 1) : ca, s);
         });
         have_r3 = fuse_next;
         rd3 ^= have_r3 ? 1 : 0;
@@ -712,7 +677,7 @@ static gs_status decode(Model *m, Launcher &L, const ForwardPlan &plan, const Fo
         // many classes: the 3x3 over 2 * CLS planes is 7 200 FMAs per pixel at twenty classes -- on the matrix cores (a plain
         // conv_mfma launch, BN + PReLU in its epilogue), the deconvolution + BR as a second, small kernel
         L.run(K_DEC3, px2 * (2 * ncls * 9 * ncls * 2), [&] {
-            return launch_dec3<CLS>(m, plan.dec3, conv_args(m->tt, wb + m->w.wcc_mfma, m->t3, nullptr, n), s);
+            return launch_planned<0, CLS>(m, plan.dec3, conv_args(m->tt, wb + m->w.wcc_mfma, m->t3, nullptr, n), s);
         });
         L.run(K_DEC3, px2 * (ncls * ncls * 4 * 2), [&] {
             Dec3Args a{};
@@ -791,7 +756,7 @@ static gs_status decode(Model *m, Launcher &L, const ForwardPlan &plan, const Fo
         // buffer as a plain conv_mfma launch (MFMA rows = the padded output channels, BN + PReLU in its epilogue), then the
         // classifier deconvolution + argmax + counts (+ the ensemble's softmax accumulation) as a second kernel.
         L.run(K_DEC_CONV, px1 * ((19 + ncls) * 9 * ncls * 2), [&] {
-            return launch_dec_conv<CLS>(m, plan.dec_conv, conv_args(m->a0c, wb + m->w.wconv, m->ff, nullptr, n), s);
+            return launch_planned<0, CLS>(m, plan.dec_conv, conv_args(m->a0c, wb + m->w.wconv, m->ff, nullptr, n), s);
         });
         m->set_stage("conv", m->ff, ncls);
         L.run(K_DEC4, px1 * (ncls * ncls * 4 * 2), [&] {
@@ -1248,8 +1213,8 @@ gs_status gs_espnet_block_forward(gs_espnet *h, int kind, int level, int index, 
         if (level == 2) {
             r = kind == 1 ? launch_l2_reduce(&m, rca, s) : launch_l2_c1(&m, rca, s);
             if (r != GS_OK) return r;
-            r = kind == 1 ? launch_l2_down(&m, unfused_l2_down(dst.W, no_vec()), bca, s)
-                          : launch_l2_esp_fused(&m, unfused_l2_esp(dst.W, no_vec()), bca, s);
+            r = kind == 1 ? launch_planned(&m, unfused_l2_down(dst.W, no_vec()), bca, s)
+                          : launch_planned(&m, unfused_l2_esp(dst.W, no_vec()), bca, s);
         } else {
             r = kind == 1 ? launch_l3_reduce(&m, form::l3_reduce::C1S, false, rca, s) : launch_l3_c1(&m, rca, s);
             if (r != GS_OK) return r;

@@ -3,8 +3,9 @@
 // plan_forward decides, the forward executes: it switches over the plan's forms and asks nothing about widths or task counts
 // itself.  Host-only and free of HIP calls; gs_espnet_plan_forward / gs_espnet_form_info (include/glomseg.h) expose the
 // function and the table to CPU tests, which is how tests/test_kernel_forms.py knows what a GPU case runs.
-// A new form is added in three places: a row of the table, a branch of plan_forward, one `case` of its class's launch_*
-// switch in espnet.hip.  Included by espnet.hip only, after espnet_config.h (whose CFG_* tuples and switches it reads).
+// A new form is added in three places: a row of the table, a branch of plan_forward, its Spec in espnet.hip (tuple and mask; the
+// class's switch is generated from the table, so a row without a Spec does not compile, and a static_assert there holds the
+// row's pixels per lane to the Spec's).  Included by espnet.hip only, after espnet_config.h (whose CFG_* tuples and switches it reads).
 #pragma once
 #include "espnet_config.h"
 

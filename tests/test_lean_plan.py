@@ -91,4 +91,9 @@ def test_the_store_flag_is_guarded():
     uses = [m.start() for m in re.finditer(r"\bF_CLS_ONLY\b", espnet) if not espnet[:m.start()].rsplit("\n", 1)[-1].lstrip().startswith("//")]
     start = espnet.index("static gs_status launch_l3_esp_last(")
     end = espnet.index("\n}\n", start)
-    assert len(uses) == 4 and all(start < u < end for u in uses)      # the four forms of the class, each once
+    # outside comments the flag is named where launch_l3_esp_last builds its modifier mask, once, and as a modifier the four forms
+    # of that class may carry, once each: no other launch class, spec or launch site names it
+    in_launch = [u for u in uses if start < u < end]
+    in_specs = [u for u in uses if espnet[:u].rsplit("\n", 1)[-1].startswith("GS_SPEC(l3_esp_last::")]
+    assert len(in_launch) == 1 and len(in_specs) == 4 and len(uses) == 5
+    assert len(re.findall(r"^GS_SPEC\(l3_esp_last::", espnet, re.M)) == 4
