@@ -186,6 +186,12 @@ BOUNDARY_PROTOTYPES = {
     "gs_instance_boundary_dist": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P, _P]),
 }
 
+# every symbol include/glomseg_morphometry.h declares (additions to ABI 10 with a header of their own)
+MORPH_PROTOTYPES = {
+    "gs_morphometry_plan": (_I, [_I, _I, ctypes.c_longlong, ctypes.POINTER(ctypes.c_size_t)]),
+    "gs_instance_morphometry": (_I, [_P, _P, _I, _I, _I, _P, ctypes.c_size_t, ctypes.c_longlong, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -202,7 +208,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     for name, (res, args) in list(PROTOTYPES.items()) + list(SCORING_PROTOTYPES.items()) + list(PLAN_PROTOTYPES.items()) + \
             list(INSTANCE_PROTOTYPES.items()) + list(MATCH_PROTOTYPES.items()) + list(BOUNDARY_PROTOTYPES.items()) + \
-            list(LEAN_PROTOTYPES.items()):
+            list(LEAN_PROTOTYPES.items()) + list(MORPH_PROTOTYPES.items()):
         if (name in PLAN_PROTOTYPES or name in LEAN_PROTOTYPES) and not hasattr(lib, name):
             continue   # (a library from before glomseg_plan.h / glomseg_lean.h, loaded for an A/B: engine.plan_flags / plan_lean then raise)
         fn = getattr(lib, name)   # AttributeError if the symbol is not exported
