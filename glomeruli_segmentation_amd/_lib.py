@@ -81,6 +81,17 @@ class WeightPiece(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("offset", ctypes.c_longlong), ("floats", ctypes.c_longlong)]
 
 
+class WorkspaceReport(ctypes.Structure):
+    _fields_ = [("must_be_zero", ctypes.c_longlong), ("offenders", ctypes.c_longlong), ("piece", ctypes.c_char * 16),
+                ("image", ctypes.c_int), ("plane", ctypes.c_int), ("row", ctypes.c_int), ("col", ctypes.c_int), ("bits", ctypes.c_uint)]
+
+
+class WorkspacePiece(ctypes.Structure):
+    _fields_ = [("name", ctypes.c_char * 16), ("offset", ctypes.c_ulonglong), ("own_words", ctypes.c_ulonglong),
+                ("span_words", ctypes.c_ulonglong), ("padded", ctypes.c_int)] + \
+               [(k, ctypes.c_int) for k in ("C", "Cp", "H", "W", "pitch", "sc", "off")]
+
+
 class KernelTime(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 64), ("total_ms", ctypes.c_double), ("launches", ctypes.c_int64),
                 ("flops_per_tile", ctypes.c_double)]
@@ -192,6 +203,15 @@ MORPH_PROTOTYPES = {
     "gs_instance_morphometry": (_I, [_P, _P, _I, _I, _I, _P, ctypes.c_size_t, ctypes.c_longlong, _P, _P, _P, _P]),
 }
 
+# every symbol include/glomseg_workspace.h declares (test tools; an addition with a header of its own)
+WORKSPACE_PROTOTYPES = {
+    "gs_espnet_workspace_classes": (_I, [_I] * 8 + [ctypes.POINTER(WorkspacePiece), _P, ctypes.c_size_t, ctypes.POINTER(_I)]),
+    "gs_espnet_workspace_audit_host": (_I, [_I] * 7 + [_P, ctypes.c_size_t, ctypes.POINTER(WorkspaceReport)]),
+    "gs_espnet_workspace_audit": (_I, [_P, _I, ctypes.POINTER(WorkspaceReport)]),
+    "gs_espnet_workspace_poison": (_I, [_P, _I, ctypes.c_uint]),
+}
+GS_WS_FREE, GS_WS_INTERIOR, GS_WS_MUST_BE_ZERO = 0, 1, 2
+
 _lib = None
 
 
@@ -208,9 +228,9 @@ def load():
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     for name, (res, args) in list(PROTOTYPES.items()) + list(SCORING_PROTOTYPES.items()) + list(PLAN_PROTOTYPES.items()) + \
             list(INSTANCE_PROTOTYPES.items()) + list(MATCH_PROTOTYPES.items()) + list(BOUNDARY_PROTOTYPES.items()) + \
-            list(LEAN_PROTOTYPES.items()) + list(MORPH_PROTOTYPES.items()):
-        if (name in PLAN_PROTOTYPES or name in LEAN_PROTOTYPES) and not hasattr(lib, name):
-            continue   # (a library from before glomseg_plan.h / glomseg_lean.h, loaded for an A/B: engine.plan_flags / plan_lean then raise)
+            list(LEAN_PROTOTYPES.items()) + list(MORPH_PROTOTYPES.items()) + list(WORKSPACE_PROTOTYPES.items()):
+        if (name in PLAN_PROTOTYPES or name in LEAN_PROTOTYPES or name in WORKSPACE_PROTOTYPES) and not hasattr(lib, name):
+            continue   # (a library from before glomseg_plan.h / glomseg_lean.h / glomseg_workspace.h, loaded for an A/B: the engine's callers then raise)
         fn = getattr(lib, name)   # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -15,6 +15,7 @@
 
 #include "../../include/glomseg_plan.h"
 #include "../../include/glomseg_lean.h"
+#include "../../include/glomseg_workspace.h"
 #include "conv_mfma.h"
 #include "dec_tail_args.h"
 #include "enc_head.h"
@@ -25,6 +26,7 @@
 #include "espnet_weights.h"
 #include "host_copy.h"
 #include "host_pipe.h"
+#include "workspace_audit.h"
 #include "workspace_plan.h"
 
 namespace gs {
@@ -1091,6 +1093,129 @@ gs_status gs_espnet_workspace_plan(int n, int height, int width, int p, int q, i
     st = plan_workspace(n, height, width, padded_classes(classes), p, encoder_only != 0, plan);
     *bytes = plan.bytes;
     return st;
+}
+
+// ---- include/glomseg_workspace.h: test tools over csrc/workspace_audit.h
+static gs_status workspace_plan_checked(const char *fn, int n, int height, int width, int p, int q, int classes, int encoder_only,
+                                        gs::WorkspacePlan &plan)
+{
+    gs_status st = check_shape(n, height, width);
+    if (st != GS_OK) return st;
+    GS_REQUIRE(p >= 0 && q >= 0, "%s: p and q must be non-negative", fn);
+    if (classes < 2 || classes > 20) {
+        set_error("%s: classes must be 2..20 (got %d)", fn, classes);
+        return GS_ERR_UNSUPPORTED;
+    }
+    return plan_workspace(n, height, width, padded_classes(classes), p, encoder_only != 0, plan);
+}
+
+static void fill_report(const WsReport &rep, gs_workspace_report *out)
+{
+    static_assert(sizeof(WsReport) == sizeof(gs_workspace_report), "WsReport is gs_workspace_report field for field");
+    std::memcpy(out, &rep, sizeof rep);
+}
+
+gs_status gs_espnet_workspace_classes(int ws_n, int height, int width, int p, int q, int classes, int encoder_only, int piece,
+                                      gs_workspace_piece *info, unsigned char *map, size_t cap, int *n_pieces)
+{
+    WorkspacePlan plan;
+    const gs_status st = workspace_plan_checked("gs_espnet_workspace_classes", ws_n, height, width, p, q, classes, encoder_only, plan);
+    if (st != GS_OK) return st;
+    if (n_pieces) *n_pieces = WS_PIECES;
+    if (!info && !map)
+        return GS_OK;
+    GS_REQUIRE(piece >= 0 && piece < WS_PIECES, "gs_espnet_workspace_classes: piece %d of %d", piece, WS_PIECES);
+    const WsPiece pc = ws_piece(plan, ws_n, piece, classes);
+    if (info) {
+        *info = gs_workspace_piece{};
+        std::strncpy(info->name, pc.name, sizeof info->name - 1);
+        info->offset = pc.at, info->own_words = pc.own_words, info->span_words = pc.span_words, info->padded = pc.padded;
+        info->C = pc.act.C, info->Cp = pc.act.Cp, info->H = pc.act.H, info->W = pc.act.W;
+        info->pitch = pc.act.pitch, info->sc = pc.act.sc, info->off = pc.act.off;
+    }
+    if (map) {
+        GS_REQUIRE(cap >= pc.span_words, "gs_espnet_workspace_classes: %zu bytes needed, room for %zu", pc.span_words, cap);
+        ws_class_map(pc, map);
+    }
+    return GS_OK;
+}
+
+gs_status gs_espnet_workspace_audit_host(int ws_n, int height, int width, int p, int q, int classes, int encoder_only,
+                                         const void *copy, size_t bytes, gs_workspace_report *report)
+{
+    GS_REQUIRE(copy && report, "gs_espnet_workspace_audit_host: null argument");
+    WorkspacePlan plan;
+    const gs_status st = workspace_plan_checked("gs_espnet_workspace_audit_host", ws_n, height, width, p, q, classes, encoder_only, plan);
+    if (st != GS_OK) return st;
+    GS_REQUIRE(bytes == plan.bytes, "gs_espnet_workspace_audit_host: the workspace has %zu bytes, the copy %zu", plan.bytes, bytes);
+    WsReport rep;
+    for (int i = 0; i < WS_PIECES; ++i) {
+        const WsPiece pc = ws_piece(plan, ws_n, i, classes);
+        ws_audit_piece(pc, reinterpret_cast<const uint32_t *>(static_cast<const char *>(copy) + pc.at), rep);
+    }
+    fill_report(rep, report);
+    return GS_OK;
+}
+
+// the plan of a lane's workspace as layout_workspace laid it out
+static gs_status lane_workspace_plan(const Model &m, WorkspacePlan &plan)
+{
+    const gs_status st = plan_workspace(m.ws_n, m.ws_h, m.ws_w, m.cp, m.p, m.encoder_only, plan);
+    if (st != GS_OK) return st;
+    GS_REQUIRE(plan.bytes == m.ws_bytes, "internal: the workspace has %zu bytes, its plan %zu", m.ws_bytes, plan.bytes);
+    return GS_OK;
+}
+
+gs_status gs_espnet_workspace_audit(gs_espnet *h, int lane, gs_workspace_report *report)
+{
+    GS_REQUIRE(h && report, "gs_espnet_workspace_audit: null argument");
+    GS_REQUIRE(lane >= 0 && lane <= (int)h->lanes.size(), "lane %d does not exist (gs_espnet_set_lanes)", lane);
+    const Model &m = h->lane(lane);
+    WsReport rep;
+    GS_HIP(hipDeviceSynchronize());
+    if (m.ws) {
+        WorkspacePlan plan;
+        const gs_status st = lane_workspace_plan(m, plan);
+        if (st != GS_OK) return st;
+        std::vector<uint32_t> host;
+        for (int i = 0; i < WS_PIECES; ++i) {
+            const WsPiece pc = ws_piece(plan, m.ws_n, i, m.classes);
+            host.resize(pc.span_words);
+            GS_HIP(hipMemcpy(host.data(), static_cast<const char *>(m.ws) + pc.at, pc.span_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            ws_audit_piece(pc, host.data(), rep);
+        }
+    }
+    fill_report(rep, report);
+    return GS_OK;
+}
+
+gs_status gs_espnet_workspace_poison(gs_espnet *h, int lane, unsigned int pattern)
+{
+    GS_REQUIRE(h, "gs_espnet_workspace_poison: null handle");
+    GS_REQUIRE(lane >= 0 && lane <= (int)h->lanes.size(), "lane %d does not exist (gs_espnet_set_lanes)", lane);
+    Model &m = h->lane(lane);
+    GS_HIP(hipDeviceSynchronize());
+    if (!m.ws)
+        return GS_OK;
+    if (m.ws_bytes > ((size_t)1 << 30)) {
+        set_error("gs_espnet_workspace_poison: a workspace of %zu bytes is above the 1 GiB this test tool takes", m.ws_bytes);
+        return GS_ERR_UNSUPPORTED;
+    }
+    WorkspacePlan plan;
+    const gs_status st = lane_workspace_plan(m, plan);
+    if (st != GS_OK) return st;
+    std::vector<uint32_t> host;
+    for (int i = 0; i < WS_PIECES; ++i) {   // a span goes down, its interior and free words are overwritten, and it goes back
+        const WsPiece pc = ws_piece(plan, m.ws_n, i, m.classes);
+        char *dev = static_cast<char *>(m.ws) + pc.at;
+        host.resize(pc.span_words);
+        GS_HIP(hipMemcpy(host.data(), dev, pc.span_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        ws_poison_piece(pc, host.data(), pattern);
+        GS_HIP(hipMemcpy(dev, host.data(), pc.span_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    GS_HIP(hipDeviceSynchronize());
+    m.stages.clear();   // the workspace no longer holds a forward's stages
+    return GS_OK;
 }
 
 gs_status gs_espnet_set_lanes(gs_espnet *h, int n_lanes)

@@ -284,6 +284,21 @@ class EspnetEngine:
                                                         h, w, out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
+    def workspace_audit(self, lane=0):
+        """Test tool (gs_espnet_workspace_audit, include/glomseg_workspace.h): waits for the device and reports the words of lane
+        `lane`'s activation workspace that must be zero and are not -> {"must_be_zero": words looked at, "offenders": how many
+        are not 0x00000000, "first": None | {"piece", "image", "plane", "row", "col", "bits"}}."""
+        rep = _lib.WorkspaceReport()
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.gs_espnet_workspace_audit(self.handle, lane, ctypes.byref(rep)))
+        return _workspace_report(rep)
+
+    def workspace_poison(self, pattern=0x7fc00000, lane=0):
+        """Test tool (gs_espnet_workspace_poison): overwrites every interior and free float of lane `lane`'s activation workspace
+        with the 32-bit pattern (a quiet NaN by default) and leaves the words that must be zero as they are."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.gs_espnet_workspace_poison(self.handle, lane, pattern))
+
     def profile(self, on):
         _lib.check(self.lib.gs_espnet_profile_enable(self.handle, 1 if on else 0))
 
@@ -369,6 +384,44 @@ def workspace_bytes(n, height, width, p, q, classes, encoder_only=False):
     b = ctypes.c_size_t()
     _lib.check(_lib.load().gs_espnet_workspace_plan(n, height, width, p, q, classes, int(bool(encoder_only)), ctypes.byref(b)))
     return b.value
+
+
+def _workspace_report(rep):
+    first = None
+    if rep.offenders:
+        first = {"piece": rep.piece.decode(), "image": rep.image, "plane": rep.plane, "row": rep.row, "col": rep.col, "bits": rep.bits}
+    return {"must_be_zero": rep.must_be_zero, "offenders": rep.offenders, "first": first}
+
+
+def workspace_classes(ws_n, height, width, p, q, classes, encoder_only=False):
+    """[(piece, class map)] of the activation workspace reserve(ws_n, height, width) lays out per lane, in allocation order:
+    piece = {"name", "offset" (bytes), "own_words", "span_words", "padded", "C", "Cp", "H", "W", "pitch", "sc", "off"}, class map =
+    uint8 [span_words] of _lib.GS_WS_FREE / GS_WS_INTERIOR / GS_WS_MUST_BE_ZERO (gs_espnet_workspace_classes,
+    include/glomseg_workspace.h).  Host-only: needs no GPU."""
+    lib = _lib.load()
+    head = (ws_n, height, width, p, q, classes, int(bool(encoder_only)))
+    count = ctypes.c_int()
+    _lib.check(lib.gs_espnet_workspace_classes(*head, 0, None, None, 0, ctypes.byref(count)))
+    out = []
+    for i in range(count.value):
+        info = _lib.WorkspacePiece()
+        _lib.check(lib.gs_espnet_workspace_classes(*head, i, ctypes.byref(info), None, 0, None))
+        cmap = np.empty(info.span_words, dtype=np.uint8)
+        _lib.check(lib.gs_espnet_workspace_classes(*head, i, None, cmap.ctypes.data_as(ctypes.c_void_p), cmap.size, None))
+        piece = {k: getattr(info, k) for k, _ in _lib.WorkspacePiece._fields_}
+        piece["name"], piece["padded"] = info.name.decode(), bool(info.padded)
+        out.append((piece, cmap))
+    return out
+
+
+def workspace_audit_host(copy, ws_n, height, width, p, q, classes, encoder_only=False):
+    """The audit of EspnetEngine.workspace_audit over a host copy (uint32 or float32 array) of a whole workspace allocation
+    (gs_espnet_workspace_audit_host).  Host-only: needs no GPU."""
+    copy = np.ascontiguousarray(copy)
+    rep = _lib.WorkspaceReport()
+    _lib.check(_lib.load().gs_espnet_workspace_audit_host(ws_n, height, width, p, q, classes, int(bool(encoder_only)),
+                                                          copy.ctypes.data_as(ctypes.c_void_p), copy.nbytes, ctypes.byref(rep)))
+    return _workspace_report(rep)
 
 
 def crop_preprocess(crop_u8, mean, std, out_h, out_w, out=None):
