@@ -203,6 +203,16 @@ MORPH_PROTOTYPES = {
     "gs_instance_morphometry": (_I, [_P, _P, _I, _I, _I, _P, ctypes.c_size_t, ctypes.c_longlong, _P, _P, _P, _P]),
 }
 
+# every symbol include/glomseg_split.h declares (additions to ABI 10 with a header of their own)
+SPLIT_PROTOTYPES = {
+    "gs_edt_plan": (_I, [_I, _I, ctypes.POINTER(ctypes.c_size_t)]),
+    "gs_label_peaks_plan": (_I, [_I, ctypes.POINTER(ctypes.c_size_t)]),
+    "gs_split_plan": (_I, [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)]),
+    "gs_foreground_edt": (_I, [_P, _I, _I, _I, _P, ctypes.c_size_t, _P, _P]),
+    "gs_label_peaks": (_I, [_P, _P, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P]),
+    "gs_split_cut": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P, _P, _P]),
+}
+
 # every symbol include/glomseg_workspace.h declares (test tools; an addition with a header of its own)
 WORKSPACE_PROTOTYPES = {
     "gs_espnet_workspace_classes": (_I, [_I] * 8 + [ctypes.POINTER(WorkspacePiece), _P, ctypes.c_size_t, ctypes.POINTER(_I)]),
@@ -228,7 +238,8 @@ def load():
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     for name, (res, args) in list(PROTOTYPES.items()) + list(SCORING_PROTOTYPES.items()) + list(PLAN_PROTOTYPES.items()) + \
             list(INSTANCE_PROTOTYPES.items()) + list(MATCH_PROTOTYPES.items()) + list(BOUNDARY_PROTOTYPES.items()) + \
-            list(LEAN_PROTOTYPES.items()) + list(MORPH_PROTOTYPES.items()) + list(WORKSPACE_PROTOTYPES.items()):
+            list(LEAN_PROTOTYPES.items()) + list(MORPH_PROTOTYPES.items()) + list(SPLIT_PROTOTYPES.items()) + \
+            list(WORKSPACE_PROTOTYPES.items()):
         if (name in PLAN_PROTOTYPES or name in LEAN_PROTOTYPES or name in WORKSPACE_PROTOTYPES) and not hasattr(lib, name):
             continue   # (a library from before glomseg_plan.h / glomseg_lean.h / glomseg_workspace.h, loaded for an A/B: the engine's callers then raise)
         fn = getattr(lib, name)   # AttributeError if the symbol is not exported
