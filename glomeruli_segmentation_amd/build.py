@@ -8,9 +8,11 @@ sources (e.g. `--out variants_so/libglomseg_nofuse.so -- -DCFG_FUSE_L3=0`), sele
 with GLOMSEG_EXPERIMENT=1 GLOMSEG_LIB=...; `-DGS_DIAG` adds the timing / stamp variants the product build leaves out.
 """
 import os
+import shutil
 import subprocess
 import sys
 import tempfile
+import time
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
@@ -41,7 +43,8 @@ def _stale(lib):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build_lib(force=False, verbose=False, out=None, extra_flags=()):
+def build_lib(force=False, verbose=False, out=None, extra_flags=(), timeout=None):
+    """timeout: seconds the compiler jobs, and then the link, may take (None: no limit); jobs still running then are killed"""
     lib = os.path.abspath(out) if out else LIB
     if not (force or _stale(lib)):
         return lib
@@ -58,14 +61,24 @@ def build_lib(force=False, verbose=False, out=None, extra_flags=()):
         if verbose:
             print(" ".join(cmd))
         procs.append((cmd, subprocess.Popen(cmd)))
-    for cmd, p in procs:
-        if p.wait() != 0:
-            raise RuntimeError("hipcc failed: " + " ".join(cmd))
+    deadline = None if timeout is None else time.monotonic() + timeout
+    try:
+        for cmd, p in procs:
+            if p.wait(None if deadline is None else max(0.0, deadline - time.monotonic())) != 0:
+                raise RuntimeError("hipcc failed: " + " ".join(cmd))
+    except BaseException:      # a failed job or the time limit: leave no compiler running
+        for _, p in procs:
+            if p.poll() is None:
+                p.kill()
+                p.wait()
+        raise
     # rpath is only a fallback: inside a torch process the already-loaded libamdhip64.so.7 wins
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + ["-Wl,-rpath,/opt/rocm/lib"]
     if verbose:
         print(" ".join(cmd))
-    subprocess.check_call(cmd)
+    subprocess.run(cmd, check=True, timeout=timeout)
+    if out is not None:
+        shutil.rmtree(objdir, ignore_errors=True)
     return lib
 
 

@@ -38,15 +38,17 @@ DELETED = ("F_EPI_PIPE", "CFG_EPI_SPLIT", "CFG_EPI_PRIO", "CFG_EPI_PRELOAD", "CF
            "CFG_L3_FUSE_P4", "CFG_AGL_", "CFG_SKIP_PAD_L2", "CFG_RES_RING_DIV", "CFG_RES_TOP", "CFG_L2_MINW", "CFG_LAZY_B2",
            "CFG_L2_C1S_REV", "rev_n", "F_XMERGE", "wconv_xm")
 # the forms the library enumerates and no shape reaches with the shipped defaults, each with the switch that keeps it away
-# (found by the sweep of reachable_forms; test_every_enumerated_form_is_accounted_for)
+# (found by the sweep of reachable_forms; test_every_enumerated_form_is_accounted_for), and the variant build and case of
+# test_variant_forms.py (helpers/variant_builds.py) that runs it against float64 all the same
 UNREACHABLE_AT_DEFAULTS = {
-    ("l2_down", "CFG_L2_BR_P4+F_VEC"): "CFG_L2_DOWN_SKIP = 1 takes every width that is a multiple of four first",
-    ("l2_esp_fused", "unfused CFG_L2_BR_P4+F_VEC"): "CFG_FUSE_L2 = 1: every block but the last computes the next 1x1 (the block hook runs it)",
-    ("l2_esp_fused", "unfused CFG_L2_BR_P4"): "CFG_FUSE_L2 = 1 (the block hook runs it)",
-    ("l3_down", "CFG_L3_BR+F_VEC"): "CFG_L3_DOWN_P2 = 1 takes every even width first",
-    ("l3_esp_last", "CFG_L3_BR+F_VEC"): "CFG_L3_LAST_P2 = 1 takes every even width first (the block hook runs it)",
-    ("dec_conv", "MFMA MT32"): "no switch: tile widths are multiples of 8, so W/2 is always a multiple of the four pixels per lane "
-                               "(GS_NO_VEC of a -DGS_DIAG build runs it)",
+    ("l2_down", "CFG_L2_BR_P4+F_VEC"): ("CFG_L2_DOWN_SKIP = 1 takes every width that is a multiple of four first", "alt", "K1"),
+    ("l2_esp_fused", "unfused CFG_L2_BR_P4+F_VEC"): ("CFG_FUSE_L2 = 1: every block but the last computes the next 1x1 (the block hook runs it)",
+                                                     "unfused", "M1"),
+    ("l2_esp_fused", "unfused CFG_L2_BR_P4"): ("CFG_FUSE_L2 = 1 (the block hook runs it)", "unfused", "M2"),
+    ("l3_down", "CFG_L3_BR+F_VEC"): ("CFG_L3_DOWN_P2 = 1 takes every even width first", "alt", "K2"),
+    ("l3_esp_last", "CFG_L3_BR+F_VEC"): ("CFG_L3_LAST_P2 = 1 takes every even width first (the block hook runs it)", "alt", "K1"),
+    ("dec_conv", "MFMA MT32"): ("no switch: tile widths are multiples of 8, so W/2 is always a multiple of the four pixels per lane "
+                                "(GS_NO_VEC of a -DGS_DIAG build runs it)", "novec", "N1"),
 }
 
 
@@ -240,6 +242,12 @@ def test_every_enumerated_form_is_accounted_for():
     reached = reachable_forms(256)
     assert reached <= enumerated, sorted(reached - enumerated)
     assert enumerated - reached == set(UNREACHABLE_AT_DEFAULTS), sorted((enumerated - reached) ^ set(UNREACHABLE_AT_DEFAULTS))
+    # ... and every pinned form names the switch that keeps it away and a variant case that exists and has it as a target
+    from helpers.variant_builds import BY_NAME, variant_cases
+    for (cls, form), (why, variant, name) in UNREACHABLE_AT_DEFAULTS.items():
+        assert why and variant in BY_NAME, (cls, form)
+        named = [vc.case for vc in variant_cases(variant) if vc.case.name == name]
+        assert len(named) == 1 and named[0].targets.get(cls) == form, (cls, form, variant, name)
 
 
 def test_plan_refuses_bad_arguments():
@@ -429,7 +437,7 @@ class DeviceCase:
         t = torch.from_numpy(tiles).cuda()
         mask, hist, logits = eng.segment(t, mean, std, want_logits=True)
         torch.cuda.synchronize()
-        worst = {}
+        worst = self.worst = {}     # stage -> (error, bound) of the worst image so far: there to be read after a failure too
         for j, k in enumerate(picks):
             got = {name: eng.read_stage(name, image=k) for name in ref if name != "logits"}
             got["logits"] = logits[k].cpu().numpy()
