@@ -17,6 +17,8 @@ GS_IN_U8_BGR_NHWC = 0
 GS_IN_F32_NCHW = 1
 ABI_VERSION = 10
 GS_BUILD_DIAG = 1
+GS_BUILD_NO_ODD_2B = 2      # a -DCFG_L3_ODD_2B=0 build: the A/B side of the two-block step of the level-3 branch kernels
+GS_FORM_ODD_2B_LEGAL, GS_FORM_ODD_2B_BUILT = 1, 2
 GS_FORM_NONE = -1
 GS_MAX_ENSEMBLE_C = 8      # most ESPNet-C members of an ensemble (include/glomseg.h)
 MAX_CROPS_PER_CALL = 64
@@ -179,6 +181,11 @@ LEAN_PROTOTYPES = {
 }
 
 # every symbol include/glomseg_instances.h declares (additions to ABI 10 with a header of their own)
+# every symbol include/glomseg_forms.h declares (an addition with a header of its own)
+FORMS_PROTOTYPES = {
+    "gs_espnet_form_odd_2b": (_I, [_I, _I]),
+}
+
 INSTANCE_PROTOTYPES = {
     "gs_instances_plan": (_I, [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)]),
     "gs_slide_instances": (_I, [_P, _I, _I, _I, _I, _P, ctypes.c_size_t, _I, _P, _P, _P, _P, _P]),
@@ -239,8 +246,8 @@ def load():
     for name, (res, args) in list(PROTOTYPES.items()) + list(SCORING_PROTOTYPES.items()) + list(PLAN_PROTOTYPES.items()) + \
             list(INSTANCE_PROTOTYPES.items()) + list(MATCH_PROTOTYPES.items()) + list(BOUNDARY_PROTOTYPES.items()) + \
             list(LEAN_PROTOTYPES.items()) + list(MORPH_PROTOTYPES.items()) + list(SPLIT_PROTOTYPES.items()) + \
-            list(WORKSPACE_PROTOTYPES.items()):
-        if (name in PLAN_PROTOTYPES or name in LEAN_PROTOTYPES or name in WORKSPACE_PROTOTYPES) and not hasattr(lib, name):
+            list(WORKSPACE_PROTOTYPES.items()) + list(FORMS_PROTOTYPES.items()):
+        if (name in PLAN_PROTOTYPES or name in LEAN_PROTOTYPES or name in WORKSPACE_PROTOTYPES or name in FORMS_PROTOTYPES) and not hasattr(lib, name):
             continue   # (a library from before glomseg_plan.h / glomseg_lean.h / glomseg_workspace.h, loaded for an A/B: the engine's callers then raise)
         fn = getattr(lib, name)   # AttributeError if the symbol is not exported
         fn.restype = res

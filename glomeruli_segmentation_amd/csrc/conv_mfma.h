@@ -49,6 +49,7 @@ __device__ __forceinline__ void static_for(F &&f)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x32 __attribute__((ext_vector_type(32)));
 
 template <int MT>
 struct Mfma;
@@ -59,6 +60,17 @@ struct Mfma<32> {
     static __device__ __forceinline__ acc_t run(float a, float b, acc_t c)
     {
         return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+    }
+    // F_ODD_2B: ONE input channel into the accumulators of TWO pixel groups, v_mfma_f32_32x32x1_2b_f32 (16 passes, as one
+    // 32x32x2): block 0 = c0, block 1 = c1, each in the 32x32x2 register layout.  Lane n < 32 gives B of block 0's column n,
+    // lane 32 + n of block 1's; A is block 0's (lanes 0..31: the weights of the rows) broadcast to both (cbsz = 1, abid = 0).
+    static __device__ __forceinline__ void run_2b(float a, float b, acc_t &c0, acc_t &c1)
+    {
+        f32x32 w = __builtin_shufflevector(c0, c1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24,
+                                           25, 26, 27, 28, 29, 30, 31);
+        w = __builtin_amdgcn_mfma_f32_32x32x1f32(a, b, w, 1, 0, 0);
+        c0 = __builtin_shufflevector(w, w, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+        c1 = __builtin_shufflevector(w, w, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31);
     }
     // output row held by accumulator register r of a lane in k-group kq (= lane / 32)
     static __device__ __forceinline__ int row(int r, int kq) { return (r & 3) + 8 * (r >> 2) + 4 * kq; }
@@ -251,6 +263,16 @@ constexpr int F_S2_FLIP = 1048576;
 // level-3 map: d16 half of the rows, d8 a quarter, ...: 6.5 % of the branch k-steps).  When a chunk is exactly one tap row
 // (G == NSTEP) such a chunk is skipped (wave-uniform), and the operand ring is refilled with the next LIVE chunk instead.
 constexpr int F_SKIP_PAD = 4194304;
+// An ODD number of real input channels on the 32x32x2 shape (level 3: 25 of CINP = 26): the last k-step of every tap multiplies the
+// last channel together with an all-zero padding channel, once per pixel group.  Under this flag that step is ONE two-block K = 1
+// instruction per PAIR of pixel groups (Mfma<32>::run_2b): 25 matrix instructions per tap and pixel-group pair where there were 26,
+// and its B operand one dword per pair (lane half kq takes the pixel of group 2j + kq; the pair's second ring register stays
+// unused, so slot indices do not move).  The dropped product is 0 x the padding plane: the same sums.  The caller's part: channel
+// CINP - 1 is padding (zero weights).  Needs MT == 32, TAPS == 9, STRIDE == 1, P in {2, 4}; P = 1 has no second group to fill block 1.
+// And a chunk of whole tap rows (G * KL a multiple of CINP), so that the step's place in the unrolled chunk is a compile-time
+// constant: in the three-row-group chunks (G = 3 of 13) it is a wave-uniform branch around the matrix instructions, and hipcc
+// answers with 300-700 register copies and 12-440 bytes of scratch per lane (profiles/odd_2b_ab.txt) -- those forms keep the K = 2 step.
+constexpr int F_ODD_2B = 524288;
 constexpr int F_BNLOAD = 8388608;  // see ConvArgs::bnl_s0
 // A 1x1 convolution of the stride-2 reduce's INPUT, computed on the vector ALU beside the matrix instructions (level3_C, the
 // decoder's 131 -> classes projection of output1_cat, Model.py:372).  Output pixel (y, x) loads input pixels (2y-1..2y+1,
@@ -359,6 +381,10 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
     static_assert(!SKIP || (TAPS == 9 && STRIDE == 1 && !(FLAGS & F_S2PAIR) && G * M_KL_OF(MT) == CINP),
                   "F_SKIP_PAD: unit-stride 3x3 with one tap row per chunk");
     static_assert(!S2FLIP || (STRIDE == 2 && TAPS == 9 && NDIL == 1), "F_S2_FLIP is for the stride-2 3x3 reduce");
+    constexpr bool ODD = FLAGS & F_ODD_2B;
+    static_assert(!ODD || (MT == 32 && TAPS == 9 && STRIDE == 1 && (P == 2 || P == 4) && CINP % 2 == 0 && (G * M_KL_OF(MT)) % CINP == 0 &&
+                           !(FLAGS & (F_S2PAIR | F_BNLOAD)) && !SIDE),
+                  "F_ODD_2B: unit-stride 3x3 on 32-pixel groups in pairs, the last of an even CINP channels padding, a chunk whole tap rows");
     static_assert(kDiag || !(FLAGS & F_X_ALL), "timing / stamp variants exist in -DGS_DIAG builds only");
     constexpr int IAUX = (FLAGS & F_IN_NT) ? 2 : 0;
     constexpr int RAUX = (FLAGS & F_RES_NT) ? 2 : 0, SAUX = (FLAGS & F_ST_NT) ? 2 : 0, SAUX2 = (FLAGS & F_ST2_NT) ? 2 : 0;
@@ -420,6 +446,8 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
     // pixel owned by (lane, p): x0 + p*MT + px (run form) or x0 + px*P + p (F_VEC: P consecutive pixels per lane)
     const int xl = VEC ? px * P : px;
     const int voff = (kq * a.in_sc + xl * STRIDE) * 4;
+    // F_ODD_2B: in a tap's last k-step lane half kq reads ONE channel, at the pixel that group kq of a pair gives lane px
+    const int voff_odd = ODD ? (VEC ? xl + kq : kq * MT + px) * 4 : 0;
     const int lbase = kq * NROW + (px < NROW ? px : NROW - 1);
     const int vout = (kq * KSTR * a.out_sc + xl) * 4;
     const int vres = RES ? (kq * KSTR * a.res_sc + xl) * 4 : 0;
@@ -604,6 +632,13 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
             const int soff = sb + (toff + sidx * KL * a.in_sc) * 4;
             if ((FLAGS & F_X_NOLOAD) && staged)   // (timing only: the ring keeps the values of the task's first chunk -- no instruction at all)
                 return;
+            if (ODD && sidx == NSTEP - 1) {   // (a compile-time constant after unrolling: a chunk is whole tap rows)
+#pragma unroll
+                for (int j = 0; j < P / 2; ++j)
+                    bq[(g * TXN + tx) % R][2 * j] = __builtin_bit_cast(
+                        float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff_odd + 2 * j * (VEC ? 1 : MT) * 4, soff, IAUX));
+                return;
+            }
             if (VEC) {
                 buf_load_vec<P, IAUX>(rs, voff, soff, bq[S2P ? 0 : (g * TXN + tx) % R]);
                 return;
@@ -1005,6 +1040,19 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
                         for (int k = 0; k < SCLS; ++k)
                             sw[k] = wr[k];
                     }
+                    // F_ODD_2B: the tap's last k-step holds one real channel: both pixel groups of a pair in one two-block instruction
+                    bool odd_step = false;
+                    if constexpr (ODD) {
+                        int ty0s, sidxs;
+                        decode_rg(c % CPD, g, ty0s, sidxs);
+                        odd_step = sidxs == NSTEP - 1;   // (a compile-time constant after unrolling: a chunk is whole tap rows)
+                        if (odd_step) {
+#pragma unroll
+                            for (int j = 0; j < P / 2; ++j)
+                                M::run_2b(aq[u % RA], bq[u % R][2 * j], acc[2 * j], acc[2 * j + 1]);
+                        }
+                    }
+                    if (!odd_step) {
 #pragma unroll
                     for (int p = 0; p < P; ++p) {
                         acc[p] = M::run(aq[u % RA], BNL ? bt[BNL ? g & 1 : 0][p][S2P ? tx : 0]
@@ -1026,6 +1074,7 @@ __global__ void __launch_bounds__(WAVES * 64, WAVES >= 8 ? WAVES / 8 : 2) conv_m
                                 asm volatile("" : "+v"(side[p][k][0]), "+v"(side[p][k][1]));
                             }
                         }
+                    }
                     }
                     // the slot just consumed is refilled with the step R later: of this chunk, or of the next one
                     refill(u);

@@ -15,6 +15,7 @@
 
 #include "../../include/glomseg_plan.h"
 #include "../../include/glomseg_lean.h"
+#include "../../include/glomseg_forms.h"
 #include "../../include/glomseg_workspace.h"
 #include "conv_mfma.h"
 #include "dec_tail_args.h"
@@ -288,12 +289,22 @@ static gs_status not_planned(const char *launch_class)
 template <int FLAGS, int MAY, int... C>
 struct Inst {
     static constexpr int flags = FLAGS, pixels = cfg_pixels(C...);
+    static constexpr bool odd_2b_legal = false;
     static constexpr bool carries(int extra) { return !(extra & ~MAY); }
     template <int EXTRA>
     static gs_status launch(const ConvArgs &ca, int num_cus, hipStream_t s) { return launch_conv_mfma<C..., FLAGS | EXTRA>(ca, num_cus, s); }
 };
 struct NotConv {   // a row that is no conv launch: a plain kernel, or a decoder shape at a class count of the other MFMA shape
+    static constexpr int flags = 0;
+    static constexpr bool odd_2b_legal = false;
     static constexpr bool carries(int) { return false; }
+};
+// A level-3 branch form with its pixel groups in pairs and a tap row per chunk: 25 real input channels of CINP = 26, so it may carry
+// F_ODD_2B, and does unless the build says CFG_L3_ODD_2B = 0
+template <int FLAGS, int MAY, int... C>
+struct OddInst : Inst<FLAGS | ODD_L3, MAY, C...> {
+    static_assert(cfg_odd_2b_legal(C...), "F_ODD_2B on a form that cannot pair its pixel groups");
+    static constexpr bool odd_2b_legal = true;
 };
 // Spec<class, form, CLS>: one per row of the table (a row without one does not compile); CLS is the decoder's padded class count
 template <typename E, E F, int CLS>
@@ -332,18 +343,18 @@ GS_SPEC(l3_reduce::C1S, Inst<L3_REDUCE, F_SIDE1X1(5), CFG_L3_C1S>)
 constexpr int L3_DOWN = F_BNACT | POL_L3_DOWN | FUSE_L3, L3_ESP = F_BNACT | F_RES | POL_L3_ESP;
 constexpr int AGL_SMALL = CFG_SMALL_AGL ? F_A_GLOBAL : 0;
 GS_SPEC(l3_down::P1R, Inst<L3_DOWN | SKIP_L3 | AGL_SMALL, F_CLS1X1, CFG_L3_BR_P1R>)
-GS_SPEC(l3_down::P2R_VEC, Inst<L3_DOWN | F_VEC | SKIP_L3, F_CLS1X1, CFG_L3_BR_P2R>)
+GS_SPEC(l3_down::P2R_VEC, OddInst<L3_DOWN | F_VEC | SKIP_L3, F_CLS1X1, CFG_L3_BR_P2R>)
 GS_SPEC(l3_down::BR_VEC, Inst<L3_DOWN | F_VEC, 0, CFG_L3_BR>)
 GS_SPEC(l3_down::P2F, Inst<L3_DOWN, F_CLS1X1, CFG_L3_BR_P2F>)
 GS_SPEC(l3_down::UNFUSED_BR_VEC, Inst<F_BNACT | POL_L3_DOWN | F_VEC, 0, CFG_L3_BR>)
 GS_SPEC(l3_down::UNFUSED_BR, Inst<F_BNACT | POL_L3_DOWN, 0, CFG_L3_BR>)
 GS_SPEC(l3_esp_fused::P1R, Inst<L3_ESP | FUSE_L3 | SKIP_L3 | AGL_SMALL, 0, CFG_L3_BR_P1R>)
-GS_SPEC(l3_esp_fused::P2R_VEC, Inst<L3_ESP | FUSE_L3 | F_VEC | SKIP_L3, 0, CFG_L3_BR_P2R>)
+GS_SPEC(l3_esp_fused::P2R_VEC, OddInst<L3_ESP | FUSE_L3 | F_VEC | SKIP_L3, 0, CFG_L3_BR_P2R>)
 GS_SPEC(l3_esp_fused::P2F, Inst<F_BNACT | F_RES | FUSE_L3, 0, CFG_L3_BR_P2F>)
 GS_SPEC(l3_esp_last::P1R, Inst<L3_ESP | SKIP_L3 | AGL_SMALL, F_CLS1X1 | F_CLS_ONLY, CFG_L3_BR_P1R>)
-GS_SPEC(l3_esp_last::P2R_VEC, Inst<L3_ESP | F_VEC | SKIP_L3, F_CLS1X1 | F_CLS_ONLY, CFG_L3_BR_P2R>)   // tap rows in the halo skipped
+GS_SPEC(l3_esp_last::P2R_VEC, OddInst<L3_ESP | F_VEC | SKIP_L3, F_CLS1X1 | F_CLS_ONLY, CFG_L3_BR_P2R>)   // tap rows in the halo skipped
 GS_SPEC(l3_esp_last::BR_VEC, Inst<L3_ESP | F_VEC, F_CLS1X1 | F_CLS_ONLY, CFG_L3_BR>)
-GS_SPEC(l3_esp_last::P2, Inst<F_BNACT | F_RES, F_CLS1X1 | F_CLS_ONLY, CFG_L3_BR_P2>)
+GS_SPEC(l3_esp_last::P2, OddInst<F_BNACT | F_RES, F_CLS1X1 | F_CLS_ONLY, CFG_L3_BR_P2>)
 // The decoder's 3x3 convolutions as plain conv_mfma launches (MFMA rows = the padded output channels, BN + PReLU in the
 // epilogue).  The shape is a property of the class count: the plan names it from the same CLS = Model::cp (dec_mt), and a form
 // of the other shape is no launch at this CLS.
@@ -829,11 +840,11 @@ gs_status gs_device_fault_check(void)
 }
 int gs_build_flags(void)
 {
+    int flags = CFG_L3_ODD_2B ? 0 : GS_BUILD_NO_ODD_2B;
 #ifdef GS_DIAG
-    return GS_BUILD_DIAG;
-#else
-    return 0;
+    flags |= GS_BUILD_DIAG;
 #endif
+    return flags;
 }
 
 // A handle = the model (weights + lane-0 workspace) plus optional extra LANES: shallow copies of the model that share
@@ -1407,6 +1418,28 @@ gs_status gs_espnet_form_info(int launch_class, int form, const char **name, int
     if (name) *name = form == GS_FORM_NONE ? c.name : c.forms[form].name;   // (no form: the class itself)
     if (pixels_per_lane) *pixels_per_lane = form == GS_FORM_NONE ? 0 : c.forms[form].pixels_per_lane;
     return GS_OK;
+}
+
+// gs_espnet_form_odd_2b (glomseg_forms.h): the Spec of every row of the table, in the table's order
+#define GS_ODD_ROW(id, name, ppl) (Spec<decltype(F::id), F::id, 5>::odd_2b_legal ? GS_FORM_ODD_2B_LEGAL : 0) | ((Spec<decltype(F::id), F::id, 5>::flags & F_ODD_2B) ? GS_FORM_ODD_2B_BUILT : 0),
+#define GS_ODD_CLASS(cls, FORMS)                                 \
+    static const int *odd_2b_##cls()                             \
+    {                                                            \
+        using F = form::cls;                                     \
+        static const int rows[] = {FORMS(GS_ODD_ROW) 0};         \
+        return rows;                                             \
+    }
+GS_LAUNCH_CLASSES(GS_ODD_CLASS)
+#undef GS_ODD_ROW
+#undef GS_ODD_CLASS
+int gs_espnet_form_odd_2b(int launch_class, int form)
+{
+#define GS_ODD_PTR(cls, FORMS) odd_2b_##cls(),
+    const int *const rows[] = {GS_LAUNCH_CLASSES(GS_ODD_PTR)};
+#undef GS_ODD_PTR
+    if (launch_class < 0 || launch_class >= kLaunchClassCount || form < 0 || form >= kLaunchClasses[launch_class].n_forms)
+        return -1;
+    return rows[launch_class][form];
 }
 
 gs_status gs_espnet_profile_enable(gs_espnet *h, int on)

@@ -83,6 +83,21 @@ constexpr int S2FLIP_L2 = (CFG_S2_FLIP & 1) ? F_S2_FLIP : 0, S2FLIP_L3 = (CFG_S2
 #define CFG_SKIP_PAD 1
 #endif
 constexpr int SKIP_L3 = CFG_SKIP_PAD ? F_SKIP_PAD : 0;
+// F_ODD_2B (the 25th input channel of a level-3 branch convolution in one two-block K = 1 matrix instruction per pixel-group pair
+// instead of a half-empty K = 2 step per group: 25 instructions per tap and pair where there were 26): the level-3 branch forms
+// with two pixel groups per wave and a tap row per chunk (CFG_L3_BR_P2R, CFG_L3_BR_P2: every level-3 branch launch of a full
+// batch).  The one-group forms (CFG_L3_BR_P1R) have no second block to fill, and the three-row-group chunks (CFG_L3_BR,
+// CFG_L3_BR_P2F) would take the step behind a run-time branch, which hipcc pays for in copies and scratch.  0 rebuilds the K = 2
+// step everywhere, and gs_build_flags() says so (GS_BUILD_NO_ODD_2B).  Measured in profiles/README.md (odd_2b_ab.txt).
+#ifndef CFG_L3_ODD_2B
+#define CFG_L3_ODD_2B 1
+#endif
+constexpr int ODD_L3 = CFG_L3_ODD_2B ? F_ODD_2B : 0;
+// whether a CFG_* tuple may carry F_ODD_2B (the kernel's static_assert; espnet.hip's OddInst asks)
+constexpr bool cfg_odd_2b_legal(int mt, int, int cinp, int taps, int stride, int, int, int, int p, int g)
+{
+    return mt == 32 && taps == 9 && stride == 1 && (p == 2 || p == 4) && cinp % 2 == 0 && (g * 2) % cinp == 0;
+}
 // Lazy b2: b2 = BR(131) over cat([output1, output1_0, inp2]) (Model.py:359) used to be fused into its producers, the
 // down-sampler writing output1_0 TWICE (raw for the level-2 ESP blocks, b2-normalised into planes 64..127 of output1_cat).
 // The normalised copy is now never written: its two consumers -- the level-3 stride-2 reduce (F_IN2: BN + PReLU on the B

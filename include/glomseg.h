@@ -49,8 +49,11 @@ const char *gs_last_error(void);
  * are additions with a header of their own, and a caller finds out by looking the symbols up. */
 int gs_abi_version(void);
 /* How the library was compiled: GS_BUILD_DIAG = a -DGS_DIAG experiment build (timing variants that return wrong results by
- * construction can be switched on through the environment); the product library returns 0 and reads no environment. */
+ * construction can be switched on through the environment); the product library returns 0 and reads no environment.
+ * GS_BUILD_NO_ODD_2B = a -DCFG_L3_ODD_2B=0 build: the level-3 branch kernels keep the half-empty K = 2 step of their 25th input
+ * channel (the same results; the A/B side of the shipped two-block step). */
 #define GS_BUILD_DIAG 1
+#define GS_BUILD_NO_ODD_2B 2
 int gs_build_flags(void);
 /* Synchronises the current device, then reads and clears the device-side fault word: GS_ERR_DEVICE_FAULT when a kernel of an
  * earlier call gave up a bounded wait (the decoder tail's strip-boundary exchange) and went on with stale values -- the masks,
