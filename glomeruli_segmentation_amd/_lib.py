@@ -79,6 +79,14 @@ class DetectorPlan(ctypes.Structure):
                 ("layers", DetectorLayerPlan * 16)]
 
 
+class DetectorStepArgs(ctypes.Structure):
+    """gs_detector_step_args (include/glomseg_detector_steps.h)"""
+    _fields_ = [("inp", ctypes.c_void_p * 3), ("out", ctypes.c_void_p * 3), ("n", ctypes.c_int64), ("h", ctypes.c_int32),
+                ("w", ctypes.c_int32), ("c", ctypes.c_int32), ("k", ctypes.c_int32), ("stride", ctypes.c_int32), ("pad", ctypes.c_int32),
+                ("layer", ctypes.c_int32), ("count", ctypes.c_int32), ("crop", ctypes.c_int32), ("win_h", ctypes.c_float),
+                ("win_w", ctypes.c_float)]
+
+
 class WeightPiece(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("offset", ctypes.c_longlong), ("floats", ctypes.c_longlong)]
 
@@ -186,6 +194,14 @@ FORMS_PROTOTYPES = {
     "gs_espnet_form_odd_2b": (_I, [_I, _I]),
 }
 
+# every symbol include/glomseg_detector_steps.h declares (test entries; an addition with a header of its own)
+DETECTOR_STEPS_PROTOTYPES = {
+    "gs_conv2d_nhwc_pack4": (_I, [_P, _I, _I, _I, _I, _P]),
+    "gs_conv2d_nhwc_packed": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P]),
+    "gs_detector_step_name": (ctypes.c_char_p, [_I]),
+    "gs_detector_step": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(DetectorStepArgs), _P]),
+}
+
 INSTANCE_PROTOTYPES = {
     "gs_instances_plan": (_I, [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)]),
     "gs_slide_instances": (_I, [_P, _I, _I, _I, _I, _P, ctypes.c_size_t, _I, _P, _P, _P, _P, _P]),
@@ -246,8 +262,9 @@ def load():
     for name, (res, args) in list(PROTOTYPES.items()) + list(SCORING_PROTOTYPES.items()) + list(PLAN_PROTOTYPES.items()) + \
             list(INSTANCE_PROTOTYPES.items()) + list(MATCH_PROTOTYPES.items()) + list(BOUNDARY_PROTOTYPES.items()) + \
             list(LEAN_PROTOTYPES.items()) + list(MORPH_PROTOTYPES.items()) + list(SPLIT_PROTOTYPES.items()) + \
-            list(WORKSPACE_PROTOTYPES.items()) + list(FORMS_PROTOTYPES.items()):
-        if (name in PLAN_PROTOTYPES or name in LEAN_PROTOTYPES or name in WORKSPACE_PROTOTYPES or name in FORMS_PROTOTYPES) and not hasattr(lib, name):
+            list(WORKSPACE_PROTOTYPES.items()) + list(FORMS_PROTOTYPES.items()) + list(DETECTOR_STEPS_PROTOTYPES.items()):
+        if (name in PLAN_PROTOTYPES or name in LEAN_PROTOTYPES or name in WORKSPACE_PROTOTYPES or name in FORMS_PROTOTYPES or
+                name in DETECTOR_STEPS_PROTOTYPES) and not hasattr(lib, name):
             continue   # (a library from before glomseg_plan.h / glomseg_lean.h / glomseg_workspace.h, loaded for an A/B: the engine's callers then raise)
         fn = getattr(lib, name)   # AttributeError if the symbol is not exported
         fn.restype = res

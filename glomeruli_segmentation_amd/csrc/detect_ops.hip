@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "../../include/glomseg_detector_steps.h"
 #include "crop_sample.h"
 #include "detect_math.h"
 #include "detect_plan.h"
@@ -24,9 +25,9 @@ typedef unsigned nhwc_u4 __attribute__((ext_vector_type(4)));
 // MFMA tile per wave, any shape) and three that share a 64-pixel x 64-channel wave tile -- its prologue, operand loads
 // and epilogue are the helpers below -- and differ in how they walk K.
 
-// Whole tensors sit behind buffer descriptors: a lane with nothing to read uses this byte offset, which is beyond any
-// descriptor (and stays beyond it with a chunk stride added), and gets 0.
-constexpr int NHWC_OOB = 0x7ffffff0;
+// Whole tensors sit behind buffer descriptors: a lane with nothing to read uses the byte offset NHWC_OOB (detect_plan.h, beside
+// the size limit that keeps it beyond any descriptor these kernels are given), and gets 0.
+static_assert(NHWC_MAX_BYTES <= (long long)NHWC_OOB, "a tensor of the 32-bit-offset kernels ends at or before the no-data offset");
 
 // One 16-byte buffer load as four floats.
 static __device__ __forceinline__ void nhwc_load4(__amdgpu_buffer_rsrc_t rsrc, int off, float *f)
@@ -66,7 +67,7 @@ struct NhwcTile {
         co0 = blockIdx.y * 64;
         if (pix0 >= npix)
             return false;
-        const unsigned in_bytes = (unsigned)min((long long)a.n * a.h * a.w_ * a.cin * 4, (long long)0x7fffffff);
+        const unsigned in_bytes = (unsigned)min((long long)a.n * a.h * a.w_ * a.cin * 4, NHWC_MAX_BYTES);
         const unsigned w_bytes = (unsigned)((long long)a.kh * a.kw * a.cin * a.cout * 4);
         rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.in), 0, in_bytes, 0x00020000);
         rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.w), 0, w_bytes, 0x00020000);
@@ -816,6 +817,29 @@ gs_status gs_conv2d_nhwc(const float *in, int n, int h, int w, int cin, const fl
                "gs_conv2d_nhwc: bad dimensions");
     const ConvNhwcArgs a{in, weight, bias_or_null, out, n, h, w, cin, kh, kw, cout, stride, pad, relu, 0, 0};
     return launch_conv2d_nhwc(a, false, static_cast<hipStream_t>(hip_stream));
+}
+
+// glomseg_detector_steps.h (tests): the packer and the packed-weight launch the detector's handle uses, on the caller's tensors
+gs_status gs_conv2d_nhwc_pack4(const float *weight, int kh, int kw, int cin, int cout, float *packed)
+{
+    GS_REQUIRE(weight && packed, "gs_conv2d_nhwc_pack4: null pointer");
+    GS_REQUIRE(kh > 0 && kw > 0 && cin > 0 && cout > 0, "gs_conv2d_nhwc_pack4: bad dimensions");
+    if (cin % 8 != 0) {   // (the packed kernels walk K in 8-channel chunks: conv_nhwc_form refuses the shape likewise)
+        set_error("gs_conv2d_nhwc_pack4: cin %d is no multiple of 8: shape not supported by the packed-weight kernel", cin);
+        return GS_ERR_UNSUPPORTED;
+    }
+    conv2d_nhwc_pack4(weight, kh, kw, cin, cout, packed);
+    return GS_OK;
+}
+
+gs_status gs_conv2d_nhwc_packed(const float *in, int n, int h, int w, int cin, const float *packed_weight, int kh, int kw, int cout,
+                                const float *bias_or_null, int stride, int pad, int relu, float *out, void *hip_stream)
+{
+    GS_REQUIRE(in && packed_weight && out, "gs_conv2d_nhwc_packed: null pointer");
+    GS_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && kh > 0 && kw > 0 && stride > 0 && pad >= 0,
+               "gs_conv2d_nhwc_packed: bad dimensions");
+    const ConvNhwcArgs a{in, packed_weight, bias_or_null, out, n, h, w, cin, kh, kw, cout, stride, pad, relu, 0, 0};
+    return launch_conv2d_nhwc(a, true, static_cast<hipStream_t>(hip_stream));
 }
 
 gs_status gs_conv2d_nhwc_form(int n, int h, int w, int cin, int kh, int kw, int cout, int stride, int pad, int packed,

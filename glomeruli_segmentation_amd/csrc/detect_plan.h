@@ -51,6 +51,12 @@ constexpr const char *kConvFormNames[] = {"generic", "smallcin", "tiled", "wide"
 struct ConvShape {
     int n, h, w, cin, kh, kw, cout, stride, pad;
 };
+// The 64 x 64 kernels address the input and the weights with 32-bit byte offsets behind buffer descriptors, and a lane with
+// nothing to read uses the byte offset NHWC_OOB, which must lie beyond every descriptor to read as 0: a tensor those kernels
+// take has at most NHWC_OOB bytes (conv_nhwc_form: in32, w32), so the offset is at or past the end of any of them.
+constexpr int NHWC_OOB = 0x7ffffff0;
+constexpr long long NHWC_MAX_BYTES = NHWC_OOB;
+
 struct ConvPlan {
     gs_status status = GS_OK;
     const char *message = "";   // of a refusal
@@ -67,9 +73,9 @@ inline ConvPlan conv_nhwc_form(const ConvShape &s, bool packed)
     p.ho = (s.h + 2 * s.pad - s.kh) / s.stride + 1;
     p.wo = (s.w + 2 * s.pad - s.kw) / s.stride + 1;
     const bool empty = p.ho <= 0 || p.wo <= 0;
-    // the 64 x 64 kernels address the input and the weights with 32-bit byte offsets
-    const bool in32 = (long long)s.n * s.h * s.w * s.cin * 4 < 0x7fffffffLL;
-    const bool w32 = (long long)s.kh * s.kw * s.cin * s.cout * 4 < 0x7fffffffLL;
+    // the 64 x 64 kernels address the input and the weights with 32-bit byte offsets, NHWC_OOB being "no data"
+    const bool in32 = (long long)s.n * s.h * s.w * s.cin * 4 <= NHWC_MAX_BYTES;
+    const bool w32 = (long long)s.kh * s.kw * s.cin * s.cout * 4 <= NHWC_MAX_BYTES;
     const bool tiled = s.cin % 8 == 0 && in32 && w32;   // 8-channel chunks
     if (packed && (empty || !tiled)) {
         // (the message keeps the name of the entry point this check used to live in)

@@ -17,6 +17,10 @@
 #include <string>
 #include <vector>
 
+#include <climits>
+#include <cstring>
+
+#include "../../include/glomseg_detector_steps.h"
 #include "detect_math.h"
 #include "detect_plan.h"
 #include "gs_internal.h"
@@ -553,14 +557,65 @@ struct Detector {
 
 static inline unsigned nblk(long long items) { return (unsigned)((items + 255) / 256); }
 
+// ---- the glue kernels' launches: each takes the shapes and works out its own grid.  gs_detector_forward and the step entry
+// of include/glomseg_detector_steps.h (tests) both go through these, so what a test runs is what the forward runs.
+static void launch_det_preprocess(const unsigned char *in, int n, int h, int w, float *out, hipStream_t s)
+{
+    const int h2 = (h + 1) / 2, w2 = (w + 1) / 2;
+    hipLaunchKernelGGL(det_preprocess_kernel, dim3(nblk((long long)n * h2 * w2 * 4)), dim3(256), 0, s, in, n, h, w, out);
+}
+// [n,h,w,c] -> [n,ho,wo,c], ho = (h + 2 pad - k) / st + 1; c % 4 == 0
+static void launch_det_maxpool(const float *in, long long n, int h, int w, int c, int k, int st, int pad, float *out, hipStream_t s)
+{
+    const int ho = (h + 2 * pad - k) / st + 1, wo = (w + 2 * pad - k) / st + 1;
+    hipLaunchKernelGGL(det_maxpool_kernel, dim3(nblk(n * ho * wo * (c / 4))), dim3(256), 0, s, in, n, h, w, c, k, st, pad, ho, wo, out);
+}
+static void launch_det_objectness(const float *rpn, long long anchors /* of all images */, float *score, hipStream_t s)
+{
+    hipLaunchKernelGGL(det_objectness_kernel, dim3(nblk(anchors)), dim3(256), 0, s, rpn, anchors, score);
+}
+static void launch_det_rpn_decode(const float *rpn, const int *sel, int n, int hf, int wf, int K, float H, float W, float *boxes, hipStream_t s)
+{
+    hipLaunchKernelGGL(det_rpn_decode_kernel, dim3(nblk((long long)n * K)), dim3(256), 0, s, rpn, sel, n, hf, wf, K, H, W, boxes);
+}
+static void launch_det_gather_proposals(const float *boxes, const int *keep, int n, int K, float H, float W, float *prop, float *prop_norm,
+                                        int *box_image, hipStream_t s)
+{
+    hipLaunchKernelGGL(det_gather_proposals_kernel, dim3(nblk((long long)n * DET_PROPOSALS)), dim3(256), 0, s, boxes, keep, n, K, H, W, prop,
+                       prop_norm, box_image);
+}
+// c % 4 == 0, crop even
+static void launch_det_crop_pool(const float *feat, int n, int h, int w, int c, const float *boxes, const int *box_image, int n_boxes, int crop,
+                                 float *out, hipStream_t s)
+{
+    const int half = crop / 2;
+    hipLaunchKernelGGL(det_crop_pool_kernel, dim3(nblk((long long)n_boxes * half * half * (c / 4))), dim3(256), 0, s, feat, n, h, w, c, boxes,
+                       box_image, n_boxes, crop, out);
+}
+static void launch_det_avgpool(const float *in, long long n, int hw, int c, float *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(det_avgpool_kernel, dim3(nblk(n * c)), dim3(256), 0, s, in, n, hw, c, out);
+}
+static void launch_det_head_decode(const float *head, const float *prop, const int *keep, int total, float H, float W, float *score, float *boxes,
+                                   hipStream_t s)
+{
+    hipLaunchKernelGGL(det_head_decode_kernel, dim3(nblk(total)), dim3(256), 0, s, head, prop, keep, total, H, W, score, boxes);
+}
+
+// layer `id` on `images` maps of in_h x in_w with the handle's packed weights, as `cp` (conv_nhwc_form of that shape, packed) has it
+static gs_status conv_layer(const Detector &d, DetLayerId id, long long images, int in_h, int in_w, const ConvPlan &cp, const float *in,
+                            float *out, hipStream_t s)
+{
+    const DetLayerRow &r = kDetLayers[id];
+    ConvNhwcArgs a{in, d.dblob + d.layers[id].w, d.dblob + d.layers[id].b, out, (int)images, in_h, in_w, r.cin, r.k, r.k, r.cout, r.stride,
+                   r.pad, r.relu, 0, 0};
+    return launch_conv2d_nhwc(a, cp, true, s);
+}
 // layer `id` as the plan has it, from `in` to `out`
 static gs_status conv(const Detector &d, const DetectorPlan &pl, DetLayerId id, const float *in, float *out, hipStream_t s)
 {
-    const DetLayerRow &r = kDetLayers[id];
     const DetLayerPlan &l = pl.layer[id];
-    ConvNhwcArgs a{in, d.dblob + d.layers[id].w, d.dblob + d.layers[id].b, out, (int)l.images, l.in_h, l.in_w, r.cin, r.k, r.k, r.cout, r.stride,
-                   r.pad, r.relu, 0, 0};
-    return launch_conv2d_nhwc(a, l.conv, true, s);
+    return conv_layer(d, id, l.images, l.in_h, l.in_w, l.conv, in, out, s);
 }
 
 }  // namespace gs
@@ -692,7 +747,7 @@ gs_status gs_detector_forward(gs_detector *h, const uint8_t *images_rgb, int n, 
         set_error("%s", pl.message);
         return pl.status;
     }
-    const int h2 = pl.h2, w2 = pl.w2, h4 = pl.h4, w4 = pl.w4, hf = pl.hf, wf = pl.wf;
+    const int h2 = pl.h2, w2 = pl.w2, hf = pl.hf, wf = pl.wf;
     const long long cells = pl.cells, anchors = pl.anchors;
     const int P = DET_PROPOSALS, K1 = DET_PRE_NMS, K2 = DET_HEAD_K;
     gs_status st = grow(d.ws, d.ws_bytes, pl.total, "detector workspace");
@@ -704,10 +759,9 @@ gs_status gs_detector_forward(gs_detector *h, const uint8_t *images_rgb, int n, 
 #define DET_TRY(x) do { st = (x); if (st != GS_OK) return st; } while (0)
 
     // ---- backbone
-    hipLaunchKernelGGL(det_preprocess_kernel, dim3(nblk((long long)n * h2 * w2 * 4)), dim3(256), 0, s, images_rgb, n, height, width, F(pl.B));
+    launch_det_preprocess(images_rgb, n, height, width, F(pl.B), s);
     DET_TRY(conv(d, pl, L_C1, F(pl.B), F(pl.A), s));
-    hipLaunchKernelGGL(det_maxpool_kernel, dim3(nblk((long long)n * h4 * w4 * 16)), dim3(256), 0, s, F(pl.A), (long long)n, h2, w2, 64, 3, 2, 1,
-                       h4, w4, F(pl.B));
+    launch_det_maxpool(F(pl.A), (long long)n, h2, w2, kDetLayers[L_C1].cout, 3, 2, 1, F(pl.B), s);   // -> h4 x w4
     DET_TRY(conv(d, pl, L_C2, F(pl.B), F(pl.A), s));
     DET_TRY(conv(d, pl, L_C3, F(pl.A), F(pl.B), s));
     DET_TRY(conv(d, pl, L_C4, F(pl.B), F(pl.A), s));
@@ -716,24 +770,21 @@ gs_status gs_detector_forward(gs_detector *h, const uint8_t *images_rgb, int n, 
     // ---- region proposal network
     DET_TRY(conv(d, pl, L_RPN, F(pl.F), F(pl.A), s));
     DET_TRY(conv(d, pl, L_RPN_HEAD, F(pl.A), F(pl.R), s));
-    hipLaunchKernelGGL(det_objectness_kernel, dim3(nblk((long long)n * anchors)), dim3(256), 0, s, F(pl.R), (long long)n * anchors, F(pl.S));
+    launch_det_objectness(F(pl.R), (long long)n * anchors, F(pl.S), s);
     hipLaunchKernelGGL(det_topk_kernel<DET_PRE_NMS>, dim3(n), dim3(1024), 0, s, F(pl.S), (int)anchors, I(pl.I1), F(pl.S1));
-    hipLaunchKernelGGL(det_rpn_decode_kernel, dim3(nblk((long long)n * K1)), dim3(256), 0, s, F(pl.R), I(pl.I1), n, hf, wf, K1, Hf, Wf, F(pl.B1));
+    launch_det_rpn_decode(F(pl.R), I(pl.I1), n, hf, wf, K1, Hf, Wf, F(pl.B1), s);
     hipLaunchKernelGGL(det_nms_mask_kernel, dim3(K1 / 64, K1 / 64, n), dim3(64), 0, s, F(pl.B1), F(pl.S1), K1, d.rpn_iou, 0.0f,
                        reinterpret_cast<unsigned long long *>(base + pl.M.off));
     hipLaunchKernelGGL(det_nms_scan_kernel, dim3(n), dim3(256), (size_t)K1 * (K1 / 64) * 8, s, reinterpret_cast<unsigned long long *>(base + pl.M.off), F(pl.S1), K1, 0.0f,
                        P, I(pl.K1), I(pl.N1));
-    hipLaunchKernelGGL(det_gather_proposals_kernel, dim3(nblk((long long)n * P)), dim3(256), 0, s, F(pl.B1), I(pl.K1), n, K1, Hf, Wf, F(pl.P),
-                       F(pl.Pn), I(pl.Bi));
+    launch_det_gather_proposals(F(pl.B1), I(pl.K1), n, K1, Hf, Wf, F(pl.P), F(pl.Pn), I(pl.Bi), s);
     // ---- box head on crop_and_resize'd features
-    hipLaunchKernelGGL(det_crop_pool_kernel, dim3(nblk((long long)n * P * 49 * (DET_CF / 4))), dim3(256), 0, s, F(pl.F), n, hf, wf, DET_CF, F(pl.Pn),
-                       I(pl.Bi), n * P, DET_CROP, F(pl.C2));
+    launch_det_crop_pool(F(pl.F), n, hf, wf, DET_CF, F(pl.Pn), I(pl.Bi), n * P, DET_CROP, F(pl.C2), s);
     DET_TRY(conv(d, pl, L_H1, F(pl.C2), F(pl.C), s));             // [nP,7,7,128]
     DET_TRY(conv(d, pl, L_H2, F(pl.C), F(pl.C2), s));             // [nP,4,4,128]
-    hipLaunchKernelGGL(det_avgpool_kernel, dim3(nblk((long long)n * P * DET_CH)), dim3(256), 0, s, F(pl.C2), (long long)n * P, 16, DET_CH, F(pl.C));
+    launch_det_avgpool(F(pl.C2), (long long)n * P, 16, DET_CH, F(pl.C), s);
     DET_TRY(conv(d, pl, L_FC, F(pl.C), F(pl.H), s));              // [nP,6]
-    hipLaunchKernelGGL(det_head_decode_kernel, dim3(nblk((long long)n * P)), dim3(256), 0, s, F(pl.H), F(pl.P), I(pl.K1), n * P, Hf, Wf, F(pl.S2),
-                       F(pl.B2));
+    launch_det_head_decode(F(pl.H), F(pl.P), I(pl.K1), n * P, Hf, Wf, F(pl.S2), F(pl.B2), s);
     // ---- per-class (one foreground class) NMS, score-sorted, padded outputs
     hipLaunchKernelGGL(det_topk_kernel<512>, dim3(n), dim3(1024), 0, s, F(pl.S2), P, I(pl.I2), F(pl.S2s));
     hipLaunchKernelGGL(det_gather_kernel, dim3(nblk((long long)n * K2)), dim3(256), 0, s, F(pl.B2), I(pl.I2), n, P, K2, F(pl.B2s));
@@ -803,6 +854,92 @@ gs_status gs_detector_detect_host(gs_detector *h, const uint8_t *const *windows,
             std::memcpy(classes + (size_t)s.first * D, r + pb * D * 5, sizeof(float) * s.count * D);
             std::memcpy(num + s.first, r + pb * D * 6, sizeof(float) * s.count);
         });
+}
+
+// ---- glomseg_detector_steps.h: one step of the forward on the caller's buffers, through the forward's launchers (tests)
+static const char *const kDetStepNames[] = {"preprocess", "maxpool", "conv", "objectness", "rpn_decode", "gather_proposals",
+                                            "crop_pool", "avgpool", "head_decode"};
+
+const char *gs_detector_step_name(int i)
+{
+    return i >= 0 && i < (int)(sizeof kDetStepNames / sizeof kDetStepNames[0]) ? kDetStepNames[i] : nullptr;
+}
+
+gs_status gs_detector_step(gs_detector *h, const char *step, const gs_detector_step_args *args, void *hip_stream)
+{
+    GS_REQUIRE(step && args, "gs_detector_step: null argument");
+    const gs_detector_step_args &a = *args;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const std::string name = step;
+    // items: the step's thread count; every launch is ceil(items / 256) workgroups on the x axis
+    constexpr long long kMaxItems = 256LL * INT_MAX;
+    const bool map_ok = a.n > 0 && a.n <= INT_MAX && a.h > 0 && a.w > 0;
+    const bool win_ok = a.win_h > 0.0f && a.win_w > 0.0f;   // (false for NaN)
+    auto F = [&](int i) { return static_cast<const float *>(a.in[i]); };
+    auto I = [&](int i) { return static_cast<const int *>(a.in[i]); };
+    auto O = [&](int i) { return static_cast<float *>(a.out[i]); };
+    if (name == "preprocess") {
+        GS_REQUIRE(a.in[0] && a.out[0], "gs_detector_step(preprocess): null pointer");
+        GS_REQUIRE(map_ok, "gs_detector_step(preprocess): n, h, w must be positive (got %lld, %d, %d)", (long long)a.n, a.h, a.w);
+        GS_REQUIRE(a.n * ((a.h + 1LL) / 2) * ((a.w + 1LL) / 2) * 4 <= kMaxItems, "gs_detector_step(preprocess): too large");
+        launch_det_preprocess(static_cast<const unsigned char *>(a.in[0]), (int)a.n, a.h, a.w, O(0), s);
+    } else if (name == "maxpool") {
+        GS_REQUIRE(a.in[0] && a.out[0], "gs_detector_step(maxpool): null pointer");
+        GS_REQUIRE(map_ok && a.c > 0 && a.c % 4 == 0, "gs_detector_step(maxpool): n, h, w must be positive and c a positive multiple of 4 "
+                   "(the kernel moves float4; got %lld, %d, %d, c=%d)", (long long)a.n, a.h, a.w, a.c);
+        GS_REQUIRE(a.k > 0 && a.stride > 0 && a.pad >= 0 && a.pad < a.k, "gs_detector_step(maxpool): want k > 0, stride > 0, 0 <= pad < k "
+                   "(a window of padding alone has no maximum; got k=%d stride=%d pad=%d)", a.k, a.stride, a.pad);
+        GS_REQUIRE(a.h + 2 * a.pad >= a.k && a.w + 2 * a.pad >= a.k, "gs_detector_step(maxpool): empty output");
+        GS_REQUIRE(a.n * ((a.h + 2LL * a.pad - a.k) / a.stride + 1) * ((a.w + 2LL * a.pad - a.k) / a.stride + 1) * (a.c / 4) <= kMaxItems,
+                   "gs_detector_step(maxpool): too large");
+        launch_det_maxpool(F(0), a.n, a.h, a.w, a.c, a.k, a.stride, a.pad, O(0), s);
+    } else if (name == "conv") {
+        GS_REQUIRE(h, "gs_detector_step(conv): the layer's weights are the handle's: null handle");
+        GS_REQUIRE(a.in[0] && a.out[0], "gs_detector_step(conv): null pointer");
+        GS_REQUIRE(a.layer >= 0 && a.layer < DET_LAYERS, "gs_detector_step(conv): layer %d outside [0, %d)", a.layer, (int)DET_LAYERS);
+        GS_REQUIRE(map_ok, "gs_detector_step(conv): n, h, w must be positive (got %lld, %d, %d)", (long long)a.n, a.h, a.w);
+        const DetLayerRow &r = kDetLayers[a.layer];
+        // planned exactly as plan_detector plans a layer
+        const ConvPlan cp = conv_nhwc_form({(int)a.n, a.h, a.w, r.cin, r.k, r.k, r.cout, r.stride, r.pad}, true);
+        return conv_layer(h->d, (DetLayerId)a.layer, a.n, a.h, a.w, cp, F(0), O(0), s);
+    } else if (name == "objectness") {
+        GS_REQUIRE(a.in[0] && a.out[0], "gs_detector_step(objectness): null pointer");
+        GS_REQUIRE(map_ok && a.n * a.h * a.w * DET_A <= kMaxItems, "gs_detector_step(objectness): n, h, w must be positive and not huge");
+        launch_det_objectness(F(0), a.n * a.h * a.w * DET_A, O(0), s);
+    } else if (name == "rpn_decode") {
+        GS_REQUIRE(a.in[0] && a.in[1] && a.out[0], "gs_detector_step(rpn_decode): null pointer");
+        GS_REQUIRE(map_ok && a.count > 0 && win_ok, "gs_detector_step(rpn_decode): n, h, w, count and the window must be positive");
+        // (the kernel's element index and the anchor indices of `sel` are 32-bit ints)
+        GS_REQUIRE(a.n * a.count <= INT_MAX - 256 && (long long)a.h * a.w * DET_A <= INT_MAX, "gs_detector_step(rpn_decode): too large");
+        launch_det_rpn_decode(F(0), I(1), (int)a.n, a.h, a.w, a.count, a.win_h, a.win_w, O(0), s);
+    } else if (name == "gather_proposals") {
+        GS_REQUIRE(a.in[0] && a.in[1] && a.out[0] && a.out[1] && a.out[2], "gs_detector_step(gather_proposals): null pointer");
+        GS_REQUIRE(a.n > 0 && a.count > 0 && win_ok, "gs_detector_step(gather_proposals): n, count and the window must be positive");
+        GS_REQUIRE(a.n * DET_PROPOSALS <= INT_MAX - 256, "gs_detector_step(gather_proposals): too large");
+        launch_det_gather_proposals(F(0), I(1), (int)a.n, a.count, a.win_h, a.win_w, O(0), O(1), static_cast<int *>(a.out[2]), s);
+    } else if (name == "crop_pool") {
+        GS_REQUIRE(a.in[0] && a.in[1] && a.in[2] && a.out[0], "gs_detector_step(crop_pool): null pointer");
+        GS_REQUIRE(map_ok && a.c > 0 && a.c % 4 == 0, "gs_detector_step(crop_pool): n, h, w must be positive and c a positive multiple of 4 "
+                   "(the kernel moves float4; got %lld, %d, %d, c=%d)", (long long)a.n, a.h, a.w, a.c);
+        GS_REQUIRE(a.crop >= 2 && a.crop % 2 == 0, "gs_detector_step(crop_pool): crop must be even (2x2 pooling; got %d)", a.crop);
+        GS_REQUIRE(a.count > 0 && a.count <= INT_MAX / 4 && (long long)a.count * (a.crop / 2) * (a.crop / 2) * (a.c / 4) <= kMaxItems,
+                   "gs_detector_step(crop_pool): count must be positive and not huge");
+        launch_det_crop_pool(F(0), (int)a.n, a.h, a.w, a.c, F(1), I(2), a.count, a.crop, O(0), s);
+    } else if (name == "avgpool") {
+        GS_REQUIRE(a.in[0] && a.out[0], "gs_detector_step(avgpool): null pointer");
+        GS_REQUIRE(map_ok && a.c > 0 && (long long)a.h * a.w <= INT_MAX && a.n * a.c <= kMaxItems,
+                   "gs_detector_step(avgpool): n, h, w, c must be positive and not huge");
+        launch_det_avgpool(F(0), a.n, a.h * a.w, a.c, O(0), s);
+    } else if (name == "head_decode") {
+        GS_REQUIRE(a.in[0] && a.in[1] && a.in[2] && a.out[0] && a.out[1], "gs_detector_step(head_decode): null pointer");
+        GS_REQUIRE(a.count > 0 && a.count <= INT_MAX - 256 && win_ok, "gs_detector_step(head_decode): count and the window must be positive");
+        launch_det_head_decode(F(0), F(1), I(2), a.count, a.win_h, a.win_w, O(0), O(1), s);
+    } else {
+        set_error("gs_detector_step: no step named '%s'", step);
+        return GS_ERR_INVALID;
+    }
+    GS_HIP(hipGetLastError());
+    return GS_OK;
 }
 
 }  // extern "C"

@@ -56,6 +56,45 @@ def synthetic_weights(seed=0):
     return sd
 
 
+# ---- include/glomseg_detector_steps.h: one kernel of the forward on the caller's buffers.  These exist for the tests
+# (tests/test_detector_steps.py); nothing in the product calls them.
+def step_names():
+    """the steps gs_detector_step accepts (gs_detector_step_name), in the header's order"""
+    lib, names = _lib.load(), []
+    while lib.gs_detector_step_name(len(names)) is not None:
+        names.append(lib.gs_detector_step_name(len(names)).decode())
+    return names
+
+
+def step(name, inputs, outputs, handle=None, stream=None, **sizes):
+    """gs_detector_step: `inputs` / `outputs` are device addresses (up to three each) in the order of the header's table, `sizes`
+    the fields of gs_detector_step_args the step reads (n, h, w, c, k, stride, pad, layer, count, crop, win_h, win_w)"""
+    a = _lib.DetectorStepArgs()
+    for i, p in enumerate(inputs):
+        a.inp[i] = p
+    for i, p in enumerate(outputs):
+        a.out[i] = p
+    for key, v in sizes.items():
+        if key not in ("n", "h", "w", "c", "k", "stride", "pad", "layer", "count", "crop", "win_h", "win_w"):
+            raise TypeError("gs_detector_step_args has no field %r" % key)
+        setattr(a, key, v)
+    _lib.check(_lib.load().gs_detector_step(handle, name.encode(), ctypes.byref(a), stream))
+
+
+def pack4(weight):
+    """gs_conv2d_nhwc_pack4 (host): float32 [kh,kw,cin,cout] -> the packed layout, as a flat float32 array"""
+    weight = np.ascontiguousarray(weight, dtype=np.float32)
+    kh, kw, cin, cout = weight.shape
+    out = np.empty(weight.size, dtype=np.float32)
+    _lib.check(_lib.load().gs_conv2d_nhwc_pack4(weight.ctypes.data_as(ctypes.c_void_p), kh, kw, cin, cout, out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+def conv2d_nhwc_packed(inp, n, h, w, cin, packed_weight, kh, kw, cout, bias, stride, pad, relu, out, stream=None):
+    """gs_conv2d_nhwc_packed: device addresses in, sizes as gs_conv2d_nhwc takes them; `bias` may be None"""
+    _lib.check(_lib.load().gs_conv2d_nhwc_packed(inp, n, h, w, cin, packed_weight, kh, kw, cout, bias, stride, pad, int(relu), out, stream))
+
+
 class FrcnnDetector:
     """One detector on one GPU.  Callable with the ``detect_box`` contract: uint8 RGB [N,H,W,3] (numpy or a GPU tensor)
     -> (boxes [N,D,4] normalised [ymin,xmin,ymax,xmax], scores [N,D] descending, classes [N,D], num [N]) as numpy."""
@@ -108,6 +147,12 @@ class FrcnnDetector:
                 self.handle, images.data_ptr(), n, h, w, out["boxes"].data_ptr(), out["scores"].data_ptr(), out["classes"].data_ptr(),
                 out["num"].data_ptr(), dbg[0], dbg[1], dbg[2], dbg[3], ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         return out
+
+    def step(self, name, inputs, outputs, **sizes):
+        """one step of the forward on the caller's device buffers, with this handle's weights (module-level `step`; tests)"""
+        with torch.cuda.device(self.device):
+            step(name, inputs, outputs, handle=self.handle,
+                 stream=ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), **sizes)
 
     def detect_host(self, windows, batch=16):
         """gs_detector_detect_host: a list of equal-size uint8 RGB [H,W,3] windows in host memory (numpy; pinned CPU tensors are

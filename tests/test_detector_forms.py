@@ -1,10 +1,13 @@
 """The detector's kernels (csrc/detect_ops.hip, csrc/detector.hip) at the shapes and inputs where they can go wrong.
 
-1. the four convolution kernels behind launch_conv2d_nhwc: CONV_CASES holds hand-written known answers for its choice, which
-   a CPU test asks of the product itself (gs_conv2d_nhwc_form: conv_nhwc_form of csrc/detect_plan.h, the function the
-   launcher switches over), one float64 reference, one bound for the family, and a CPU test showing that the bound rejects a
-   dropped K-tail, a zeroed tap column and a one-pixel shift; likewise known answers for the detector's host plan
-   (gs_detector_plan, gs_detector_layer_info): size chain, workspace bytes, batch limits, per-layer kernels;
+1. the four convolution kernels behind launch_conv2d_nhwc, in the instances the public gs_conv2d_nhwc launches (weights NOT
+   packed: conv2d_nhwc_tiled_kernel<false>, conv2d_nhwc_wide_kernel<4,false>; the packed-weight instances every layer of the
+   detector runs, and the detector's glue kernels one step at a time, are in tests/test_detector_steps.py): CONV_CASES holds
+   hand-written known answers for its choice, which a CPU test asks of the product itself (gs_conv2d_nhwc_form: conv_nhwc_form
+   of csrc/detect_plan.h, the function the launcher switches over), one float64 reference, one bound for the family, and a CPU
+   test showing that the bound rejects a dropped K-tail, a zeroed tap column and a one-pixel shift; likewise known answers for
+   the detector's host plan (gs_detector_plan, gs_detector_layer_info): size chain, workspace bytes, batch limits, per-layer
+   kernels;
 2. gs_roialign against the float32 oracle, on the border, beyond it, at crop 1 and on degenerate maps;
 3. gs_nms against a float32 restatement, exactly, on inputs whose arithmetic is exact;
 4. the selection stages of the assembled detector (top-k, NMS, decode, gather, output) stage by stage against
