@@ -1,4 +1,4 @@
-"""ctypes binding of libglomseg.so (include/glomseg.h).  No fallback: if the HIP library is
+"""ctypes binding of libglomseg.so (the headers under include/: HEADERS).  No fallback: if the HIP library is
 missing or fails to load this raises, so a GPU box can never pass on a silent CPU path."""
 import ctypes
 import os
@@ -111,7 +111,6 @@ _P = ctypes.c_void_p
 _FP = ctypes.POINTER(ctypes.c_float)
 _I = ctypes.c_int
 
-# every symbol include/glomseg.h declares: (restype, argtypes)
 PROTOTYPES = {
     "gs_last_error": (ctypes.c_char_p, []),
     "gs_abi_version": (_I, []),
@@ -168,13 +167,11 @@ PROTOTYPES = {
     "gs_detector_detect_host": (_I, [_P, ctypes.POINTER(_P), _I, _I, _I, _I, _P, _P, _P, _P]),
 }
 
-# every symbol include/glomseg_scoring.h declares (additions to ABI 8 with a header of their own)
 SCORING_PROTOTYPES = {
     "gs_espnet_score_crops": (_I, [_P, _P, ctypes.POINTER(CropDesc), _I, _I, _I, _I, _P, _P, _P]),
     "gs_espnet_segment_crops_host_scored": (_I, PROTOTYPES["gs_espnet_segment_crops_host"][1] + [ctypes.POINTER(CropScoring)]),
 }
 
-# every symbol include/glomseg_plan.h declares (an addition to ABI 9 with a header of its own)
 PLAN_PROTOTYPES = {
     "gs_espnet_plan_flags": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)]),
     "gs_espnet_pack_weights": (_I, [_P, ctypes.POINTER(LayerDesc), _I, _I, _I, _I, _I, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
@@ -183,18 +180,14 @@ PLAN_PROTOTYPES = {
 }
 GS_PLAN_LAZY_B2, GS_PLAN_L3C_IN_REDUCE, GS_PLAN_CLS_IN_L3 = 1, 2, 4
 
-# every symbol include/glomseg_lean.h declares (an addition with a header of its own)
 LEAN_PROTOTYPES = {
     "gs_espnet_plan_lean": (_I, [_I] * 9 + [ctypes.POINTER(_I)]),
 }
 
-# every symbol include/glomseg_instances.h declares (additions to ABI 10 with a header of their own)
-# every symbol include/glomseg_forms.h declares (an addition with a header of its own)
 FORMS_PROTOTYPES = {
     "gs_espnet_form_odd_2b": (_I, [_I, _I]),
 }
 
-# every symbol include/glomseg_detector_steps.h declares (test entries; an addition with a header of its own)
 DETECTOR_STEPS_PROTOTYPES = {
     "gs_conv2d_nhwc_pack4": (_I, [_P, _I, _I, _I, _I, _P]),
     "gs_conv2d_nhwc_packed": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P]),
@@ -207,26 +200,22 @@ INSTANCE_PROTOTYPES = {
     "gs_slide_instances": (_I, [_P, _I, _I, _I, _I, _P, ctypes.c_size_t, _I, _P, _P, _P, _P, _P]),
 }
 
-# every symbol include/glomseg_instance_match.h declares (additions to ABI 10 with a header of their own)
 MATCH_PROTOTYPES = {
     "gs_instance_match_plan": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_size_t)]),
     "gs_instance_overlaps": (_I, [_P, _P, _P, _P, _I, _I, _P, ctypes.c_size_t, _I, _P, _P, _P, _P]),
     "gs_instance_match": (_I, [_P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
 }
 
-# every symbol include/glomseg_boundary_dist.h declares (additions to ABI 10 with a header of their own)
 BOUNDARY_PROTOTYPES = {
     "gs_boundary_dist_plan": (_I, [_I, _I, ctypes.POINTER(ctypes.c_size_t)]),
     "gs_instance_boundary_dist": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P, _P]),
 }
 
-# every symbol include/glomseg_morphometry.h declares (additions to ABI 10 with a header of their own)
 MORPH_PROTOTYPES = {
     "gs_morphometry_plan": (_I, [_I, _I, ctypes.c_longlong, ctypes.POINTER(ctypes.c_size_t)]),
     "gs_instance_morphometry": (_I, [_P, _P, _I, _I, _I, _P, ctypes.c_size_t, ctypes.c_longlong, _P, _P, _P, _P]),
 }
 
-# every symbol include/glomseg_split.h declares (additions to ABI 10 with a header of their own)
 SPLIT_PROTOTYPES = {
     "gs_edt_plan": (_I, [_I, _I, ctypes.POINTER(ctypes.c_size_t)]),
     "gs_label_peaks_plan": (_I, [_I, ctypes.POINTER(ctypes.c_size_t)]),
@@ -236,7 +225,6 @@ SPLIT_PROTOTYPES = {
     "gs_split_cut": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P, _P, _P]),
 }
 
-# every symbol include/glomseg_workspace.h declares (test tools; an addition with a header of its own)
 WORKSPACE_PROTOTYPES = {
     "gs_espnet_workspace_classes": (_I, [_I] * 8 + [ctypes.POINTER(WorkspacePiece), _P, ctypes.c_size_t, ctypes.POINTER(_I)]),
     "gs_espnet_workspace_audit_host": (_I, [_I] * 7 + [_P, ctypes.c_size_t, ctypes.POINTER(WorkspaceReport)]),
@@ -244,6 +232,26 @@ WORKSPACE_PROTOTYPES = {
     "gs_espnet_workspace_poison": (_I, [_P, _I, ctypes.c_uint]),
 }
 GS_WS_FREE, GS_WS_INTERIOR, GS_WS_MUST_BE_ZERO = 0, 1, 2
+
+# public header under include/ -> its table: every symbol the header declares, (restype, argtypes).  load() binds them in
+# this order.
+HEADERS = {
+    "glomseg.h": PROTOTYPES,
+    "glomseg_scoring.h": SCORING_PROTOTYPES,
+    "glomseg_plan.h": PLAN_PROTOTYPES,
+    "glomseg_instances.h": INSTANCE_PROTOTYPES,
+    "glomseg_instance_match.h": MATCH_PROTOTYPES,
+    "glomseg_boundary_dist.h": BOUNDARY_PROTOTYPES,
+    "glomseg_lean.h": LEAN_PROTOTYPES,
+    "glomseg_morphometry.h": MORPH_PROTOTYPES,
+    "glomseg_split.h": SPLIT_PROTOTYPES,
+    "glomseg_workspace.h": WORKSPACE_PROTOTYPES,
+    "glomseg_forms.h": FORMS_PROTOTYPES,
+    "glomseg_detector_steps.h": DETECTOR_STEPS_PROTOTYPES,
+}
+# the headers whose symbols an older library, loaded for an A/B (GLOMSEG_LIB), may lack; a symbol missing from any other is an
+# AttributeError in load()
+OPTIONAL_HEADERS = {"glomseg_plan.h", "glomseg_lean.h", "glomseg_workspace.h", "glomseg_forms.h", "glomseg_detector_steps.h"}
 
 _lib = None
 
@@ -259,16 +267,13 @@ def load():
             "%s is missing: build it with `python -m glomeruli_segmentation_amd.build` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in list(PROTOTYPES.items()) + list(SCORING_PROTOTYPES.items()) + list(PLAN_PROTOTYPES.items()) + \
-            list(INSTANCE_PROTOTYPES.items()) + list(MATCH_PROTOTYPES.items()) + list(BOUNDARY_PROTOTYPES.items()) + \
-            list(LEAN_PROTOTYPES.items()) + list(MORPH_PROTOTYPES.items()) + list(SPLIT_PROTOTYPES.items()) + \
-            list(WORKSPACE_PROTOTYPES.items()) + list(FORMS_PROTOTYPES.items()) + list(DETECTOR_STEPS_PROTOTYPES.items()):
-        if (name in PLAN_PROTOTYPES or name in LEAN_PROTOTYPES or name in WORKSPACE_PROTOTYPES or name in FORMS_PROTOTYPES or
-                name in DETECTOR_STEPS_PROTOTYPES) and not hasattr(lib, name):
-            continue   # (a library from before glomseg_plan.h / glomseg_lean.h / glomseg_workspace.h, loaded for an A/B: the engine's callers then raise)
-        fn = getattr(lib, name)   # AttributeError if the symbol is not exported
-        fn.restype = res
-        fn.argtypes = args
+    for header, table in HEADERS.items():
+        for name, (res, args) in table.items():
+            if header in OPTIONAL_HEADERS and not hasattr(lib, name):
+                continue   # (a library from before that header, loaded for an A/B: the callers of its entries then raise)
+            fn = getattr(lib, name)   # AttributeError if the symbol is not exported
+            fn.restype = res
+            fn.argtypes = args
     if lib.gs_abi_version() != ABI_VERSION:
         raise ImportError("libglomseg.so ABI %d != binding ABI %d: rebuild" % (lib.gs_abi_version(), ABI_VERSION))
     if (lib.gs_build_flags() & GS_BUILD_DIAG) and os.environ.get("GLOMSEG_ALLOW_DIAG") != "1":

@@ -25,14 +25,10 @@ from argparse import ArgumentParser
 import numpy as np
 import torch
 
-from . import _lib, imageops
+from . import _call, _lib, imageops
 
 MAGNIFICATION = 8
 WINDOW = 2400          # eval_wsi_segmentation.py: self.window_size
-
-
-def _sp(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _axis_lut(size, limit, window=WINDOW, ds=MAGNIFICATION):
@@ -90,10 +86,10 @@ class SlideCompositor:
             if self.luts is not None:
                 _lib.check(self.lib.gs_wsi_paste_max_lut(self.map.data_ptr(), self.map.shape[0], self.map.shape[1], self.ds,
                                                          self.luts[0].data_ptr(), self.luts[1].data_ptr(),
-                                                         crop_mask.data_ptr(), h, w, int(x1), int(y1), _sp(self.device)))
+                                                         crop_mask.data_ptr(), h, w, int(x1), int(y1), _call.stream_ptr(self.device)))
             else:
                 _lib.check(self.lib.gs_wsi_paste_max(self.map.data_ptr(), self.map.shape[0], self.map.shape[1], self.ds,
-                                                     crop_mask.data_ptr(), h, w, int(x1), int(y1), _sp(self.device)))
+                                                     crop_mask.data_ptr(), h, w, int(x1), int(y1), _call.stream_ptr(self.device)))
 
     def overlay(self, slide_bgr_small, wa=0.4, wb=0.6):
         """slide_bgr_small: uint8 [map_h,map_w,3] BGR (the 1/8-scale slide) -> blended prediction image."""
@@ -104,7 +100,7 @@ class SlideCompositor:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.gs_overlay_classmap(img.data_ptr(), self.map.data_ptr(), h, w, self.palette.data_ptr(),
                                                     self.palette.shape[0], ctypes.c_float(wa), ctypes.c_float(wb),
-                                                    out.data_ptr(), _sp(self.device)))
+                                                    out.data_ptr(), _call.stream_ptr(self.device)))
         return out
 
     def confusion(self, gt_map, classes=5, hist=None):
@@ -115,7 +111,7 @@ class SlideCompositor:
             hist = torch.zeros((classes, classes), dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.gs_confusion_u8(self.map.data_ptr(), gt.data_ptr(), self.map.numel(), classes, hist.data_ptr(),
-                                                _sp(self.device)))
+                                                _call.stream_ptr(self.device)))
         return hist
 
     def instances(self, classes=5, connectivity=8, **kw):

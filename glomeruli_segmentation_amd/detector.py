@@ -16,7 +16,7 @@ from functools import lru_cache
 import numpy as np
 import torch
 
-from . import _lib
+from . import _call, _lib
 from .engine import pack_state_dict
 
 
@@ -145,34 +145,25 @@ class FrcnnDetector:
         with torch.cuda.device(dev):
             _lib.check(self.lib.gs_detector_forward(
                 self.handle, images.data_ptr(), n, h, w, out["boxes"].data_ptr(), out["scores"].data_ptr(), out["classes"].data_ptr(),
-                out["num"].data_ptr(), dbg[0], dbg[1], dbg[2], dbg[3], ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                out["num"].data_ptr(), dbg[0], dbg[1], dbg[2], dbg[3], _call.stream_ptr(dev)))
         return out
 
     def step(self, name, inputs, outputs, **sizes):
         """one step of the forward on the caller's device buffers, with this handle's weights (module-level `step`; tests)"""
         with torch.cuda.device(self.device):
             step(name, inputs, outputs, handle=self.handle,
-                 stream=ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), **sizes)
+                 stream=_call.stream_ptr(self.device), **sizes)
 
     def detect_host(self, windows, batch=16):
         """gs_detector_detect_host: a list of equal-size uint8 RGB [H,W,3] windows in host memory (numpy; pinned CPU tensors are
         DMA'd in place) -> (boxes [n,D,4], scores [n,D], classes [n,D], num [n]) numpy.  Uploads run one batch ahead of the
         forward on a stream of their own; pageable windows are staged into pinned memory by a few threads."""
         n = len(windows)
-        keep, ptrs = [], (ctypes.c_void_p * n)()
-        h = w = None
-        for i, im in enumerate(windows):
-            if isinstance(im, torch.Tensor):
-                if im.is_cuda or im.dtype != torch.uint8 or not im.is_contiguous():
-                    raise ValueError("window %d: expected a contiguous uint8 CPU tensor" % i)
-                ptrs[i] = im.data_ptr()
-            else:
-                im = np.ascontiguousarray(im, dtype=np.uint8)
-                ptrs[i] = im.ctypes.data
-            if im.ndim != 3 or im.shape[2] != 3 or (h is not None and tuple(im.shape[:2]) != (h, w)):
+        ptrs, shapes, keep = _call.host_image_ptrs(windows, "window")      # keep: the converted windows, alive until the call returns
+        h, w = shapes[0] if shapes else (None, None)
+        for i, shape in enumerate(shapes):
+            if shape != (h, w):
                 raise ValueError("window %d: expected uint8 [H,W,3], every window of one size" % i)
-            h, w = int(im.shape[0]), int(im.shape[1])
-            keep.append(im)
         d = self.max_det
         boxes = np.empty((n, d, 4), dtype=np.float32)
         scores = np.empty((n, d), dtype=np.float32)

@@ -9,7 +9,7 @@ import functools
 import numpy as np
 import torch
 
-from . import _lib
+from . import _call, _lib
 
 
 def _to_numpy(v):
@@ -54,10 +54,6 @@ def _check_out(t, name, shape, dtype, device):
     if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous() or \
             t.device.type != torch.device(device).type or (t.is_cuda and t.device != torch.device(device)):
         raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, tuple(shape), device))
-
-
-def _stream_ptr(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class EspnetEngine:
@@ -131,6 +127,22 @@ class EspnetEngine:
             pass
 
     # ------------------------------------------------------------------ hot path
+    def _lane_call(self, lane, tensors):
+        """(workspace index, stream pointer) for a stream-ordered call that uses `tensors` (all on one device; None entries are
+        skipped).  lane=None: workspace 0 on the current stream.  lane=k: workspace k on that lane's own stream, which first waits
+        for the current one."""
+        dev = tensors[0].device
+        if lane is None:
+            if 0 in self._lane_streams:      # workspace 0 may still be in use on lane 0's own stream
+                torch.cuda.current_stream(dev).wait_stream(self._lane_streams[0])
+            return 0, _call.stream_ptr(dev)
+        st = self.lane_stream(lane)
+        st.wait_stream(torch.cuda.current_stream(dev))
+        for t in tensors:      # (allocator: these tensors are in use on the lane's stream)
+            if t is not None:
+                t.record_stream(st)
+        return lane, ctypes.c_void_p(st.cuda_stream)
+
     def reserve(self, n, height, width):
         with torch.cuda.device(self.device):
             _lib.check(self.lib.gs_espnet_reserve(self.handle, n, height, width))
@@ -146,7 +158,7 @@ class EspnetEngine:
         out = torch.empty((n, self.classes, oh, ow), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             _lib.check(self.lib.gs_espnet_forward(self.handle, x.data_ptr(), _lib.GS_IN_F32_NCHW, n, h, w, None, None,
-                                                  out.data_ptr(), None, None, _stream_ptr(x.device)))
+                                                  out.data_ptr(), None, None, _call.stream_ptr(x.device)))
         return out
 
     def segment(self, tiles_u8, mean, std, want_logits=False, want_hist=True, out_mask=None, out_hist=None, lane=None,
@@ -180,17 +192,7 @@ class EspnetEngine:
         lh, lw = (h // 8, w // 8) if self.encoder_only else (h, w)
         logits = torch.empty((n, self.classes, lh, lw), dtype=torch.float32, device=dev) if want_logits else None
         with torch.cuda.device(dev):
-            if lane is None:
-                if 0 in self._lane_streams:      # workspace 0 may still be in use on lane 0's own stream
-                    torch.cuda.current_stream(dev).wait_stream(self._lane_streams[0])
-                k, sp = 0, _stream_ptr(dev)
-            else:
-                st = self.lane_stream(lane)
-                st.wait_stream(torch.cuda.current_stream(dev))
-                for t in (tiles_u8, mask, hist, logits):      # (allocator: these tensors are in use on the lane's stream)
-                    if t is not None:
-                        t.record_stream(st)
-                k, sp = lane, ctypes.c_void_p(st.cuda_stream)
+            k, sp = self._lane_call(lane, (tiles_u8, mask, hist, logits))
             _lib.check(self.lib.gs_espnet_forward_lane(
                 self.handle, k, tiles_u8.data_ptr(), _lib.GS_IN_U8_BGR_NHWC, n, h, w, _lib.fptr3(mean), _lib.fptr3(std),
                 logits.data_ptr() if want_logits else None, mask.data_ptr(),
@@ -201,31 +203,31 @@ class EspnetEngine:
         """numpy uint8 [T,H,W,3] in host memory -> (masks [T,H,W], counts [T,classes]) through the
         pinned double-buffered H2D / compute / D2H pipeline of the library."""
         self.quiesce()
-        if isinstance(tiles, torch.Tensor):      # e.g. a pinned CPU tensor: DMA'd in place, no staging copy
+        from_tensor = isinstance(tiles, torch.Tensor)
+        if from_tensor:      # e.g. a pinned CPU tensor: DMA'd in place, no staging copy; the outputs are tensors pinned like it
             if tiles.is_cuda or tiles.dtype != torch.uint8 or not tiles.is_contiguous():
                 raise ValueError("expected a contiguous uint8 CPU tensor")
             t, h, w, _ = tiles.shape
-            in_ptr = ctypes.c_void_p(tiles.data_ptr())
             pin = tiles.is_pinned()
             _check_out(out_masks, "out_masks", (t, h, w), torch.uint8, torch.device("cpu"))
             _check_out(out_hist, "out_hist", (t, self.classes), torch.int64, torch.device("cpu"))
-            masks_t = out_masks if out_masks is not None else torch.empty((t, h, w), dtype=torch.uint8, pin_memory=pin)
-            hist_t = None
+            masks = out_masks if out_masks is not None else torch.empty((t, h, w), dtype=torch.uint8, pin_memory=pin)
+            hist = None
             if want_hist:
-                hist_t = out_hist if out_hist is not None else torch.zeros((t, self.classes), dtype=torch.int64, pin_memory=pin)
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.gs_espnet_segment_host(
-                    self.handle, in_ptr, t, h, w, _lib.fptr3(mean), _lib.fptr3(std), batch, ctypes.c_void_p(masks_t.data_ptr()),
-                    ctypes.c_void_p(hist_t.data_ptr()) if want_hist else None))
-            return masks_t.numpy(), (hist_t.numpy() if want_hist else None)
-        tiles = np.ascontiguousarray(tiles, dtype=np.uint8)
-        t, h, w, _ = tiles.shape
-        masks = np.empty((t, h, w), dtype=np.uint8)
-        hist = np.zeros((t, self.classes), dtype=np.uint64) if want_hist else None
+                hist = out_hist if out_hist is not None else torch.zeros((t, self.classes), dtype=torch.int64, pin_memory=pin)
+            in_ptr, mask_ptr, hist_ptr = tiles.data_ptr(), masks.data_ptr(), hist.data_ptr() if want_hist else None
+        else:
+            tiles = np.ascontiguousarray(tiles, dtype=np.uint8)
+            t, h, w, _ = tiles.shape
+            masks = np.empty((t, h, w), dtype=np.uint8)
+            hist = np.zeros((t, self.classes), dtype=np.uint64) if want_hist else None
+            in_ptr, mask_ptr, hist_ptr = tiles.ctypes.data, masks.ctypes.data, hist.ctypes.data if want_hist else None
         with torch.cuda.device(self.device):
             _lib.check(self.lib.gs_espnet_segment_host(
-                self.handle, tiles.ctypes.data_as(ctypes.c_void_p), t, h, w, _lib.fptr3(mean), _lib.fptr3(std), batch,
-                masks.ctypes.data_as(ctypes.c_void_p), hist.ctypes.data_as(ctypes.c_void_p) if want_hist else None))
+                self.handle, ctypes.c_void_p(in_ptr), t, h, w, _lib.fptr3(mean), _lib.fptr3(std), batch, ctypes.c_void_p(mask_ptr),
+                ctypes.c_void_p(hist_ptr)))
+        if from_tensor:
+            return masks.numpy(), (hist.numpy() if want_hist else None)
         return masks, (hist.astype(np.int64) if want_hist else None)
 
     scores_crops = True      # segment_crops takes labels= / want_gt_overlay= (segment.segment_batch asks)
@@ -246,17 +248,7 @@ class EspnetEngine:
         net = torch.empty((n, net_h, net_w), dtype=torch.uint8, device=dev) if want_net_maps else None
         hist = torch.empty((n, self.classes), dtype=torch.int64, device=dev) if want_hist else None
         with torch.cuda.device(dev):
-            if lane is None:
-                if 0 in self._lane_streams:
-                    torch.cuda.current_stream(dev).wait_stream(self._lane_streams[0])
-                k, sp = 0, _stream_ptr(dev)
-            else:
-                st = self.lane_stream(lane)
-                st.wait_stream(torch.cuda.current_stream(dev))
-                for t in (packed_in, packed_out, net, hist):
-                    if t is not None:
-                        t.record_stream(st)
-                k, sp = lane, ctypes.c_void_p(st.cuda_stream)
+            k, sp = self._lane_call(lane, (packed_in, packed_out, net, hist))
             _lib.check(self.lib.gs_espnet_segment_crops(
                 self.handle, k, packed_in.data_ptr(), tab, n, _lib.fptr3(mean), _lib.fptr3(std), net_h, net_w,
                 net.data_ptr() if net is not None else None, packed_out.data_ptr() if packed_out is not None else None,
@@ -337,21 +329,24 @@ def plan_forward(n, height, width, p, q, classes, num_cus):
     return {cls: forms[codes[k]][0] for k, (cls, forms) in enumerate(table) if codes[k] != _lib.GS_FORM_NONE}
 
 
+def _plan_flag_bits(n, height, width, p, q, classes, num_cus, encoder_only):
+    flags = ctypes.c_int()
+    _lib.check(_lib.load().gs_espnet_plan_flags(n, height, width, p, q, classes, int(bool(encoder_only)), num_cus, ctypes.byref(flags)))
+    return flags.value
+
+
 def plan_flags(n, height, width, p, q, classes, num_cus, encoder_only=False):
     """{"lazy_b2": bool, "l3c_in_reduce": bool}: the decisions of the same plan that are no form of a launch class
     (gs_espnet_plan_flags, include/glomseg_plan.h).  Host-only: needs no GPU."""
-    flags = ctypes.c_int()
-    _lib.check(_lib.load().gs_espnet_plan_flags(n, height, width, p, q, classes, int(bool(encoder_only)), num_cus, ctypes.byref(flags)))
-    return {"lazy_b2": bool(flags.value & _lib.GS_PLAN_LAZY_B2), "l3c_in_reduce": bool(flags.value & _lib.GS_PLAN_L3C_IN_REDUCE)}
+    bits = _plan_flag_bits(n, height, width, p, q, classes, num_cus, encoder_only)
+    return {"lazy_b2": bool(bits & _lib.GS_PLAN_LAZY_B2), "l3c_in_reduce": bool(bits & _lib.GS_PLAN_L3C_IN_REDUCE)}
 
 
 def plan_cls_in_l3(n, height, width, p, q, classes, num_cus, encoder_only=False):
     """Whether the same plan sums the encoder classifier in the epilogues of the level-3 down-sampler and of the last
     level-3 ESP block (GS_PLAN_CLS_IN_L3 of gs_espnet_plan_flags; dec1_sums_kernel then adds the partial planes in
     dec1_kernel's place).  Host-only: needs no GPU."""
-    flags = ctypes.c_int()
-    _lib.check(_lib.load().gs_espnet_plan_flags(n, height, width, p, q, classes, int(bool(encoder_only)), num_cus, ctypes.byref(flags)))
-    return bool(flags.value & _lib.GS_PLAN_CLS_IN_L3)
+    return bool(_plan_flag_bits(n, height, width, p, q, classes, num_cus, encoder_only) & _lib.GS_PLAN_CLS_IN_L3)
 
 
 def plan_lean(n, height, width, p, q, classes, num_cus, encoder_only=False, want_logits=False):
@@ -381,9 +376,7 @@ def pack_weights(state_dict, classes=5, p=2, q=8, encoder_only=False):
 def workspace_bytes(n, height, width, p, q, classes, encoder_only=False):
     """The bytes of activation workspace EspnetEngine.reserve(n, height, width) allocates per lane for ESPNet(classes, p, q)
     (gs_espnet_workspace_plan); raises GlomsegError for a shape no forward takes.  Host-only: needs no GPU."""
-    b = ctypes.c_size_t()
-    _lib.check(_lib.load().gs_espnet_workspace_plan(n, height, width, p, q, classes, int(bool(encoder_only)), ctypes.byref(b)))
-    return b.value
+    return _call.planned_bytes(_lib.load().gs_espnet_workspace_plan, n, height, width, p, q, classes, bool(encoder_only))
 
 
 def _workspace_report(rep):
@@ -434,7 +427,7 @@ def crop_preprocess(crop_u8, mean, std, out_h, out_w, out=None):
         out = torch.empty((3, out_h, out_w), dtype=torch.float32, device=crop_u8.device)
     with torch.cuda.device(crop_u8.device):
         _lib.check(lib.gs_crop_preprocess(crop_u8.data_ptr(), h, w, _lib.fptr3(mean), _lib.fptr3(std), out_h, out_w,
-                                          out.data_ptr(), _stream_ptr(crop_u8.device)))
+                                          out.data_ptr(), _call.stream_ptr(crop_u8.device)))
     return out
 
 
@@ -445,7 +438,7 @@ def mask_resize_nearest(mask, out_h, out_w):
     h, w = mask.shape
     out = torch.empty((out_h, out_w), dtype=torch.uint8, device=mask.device)
     with torch.cuda.device(mask.device):
-        _lib.check(lib.gs_mask_resize_nearest(mask.data_ptr(), h, w, out_h, out_w, out.data_ptr(), _stream_ptr(mask.device)))
+        _lib.check(lib.gs_mask_resize_nearest(mask.data_ptr(), h, w, out_h, out_w, out.data_ptr(), _call.stream_ptr(mask.device)))
     return out
 
 
@@ -487,7 +480,7 @@ def score_crops_resident(net_masks, packed_labels, descs, classes, want_seen=Tru
     seen = torch.empty((n, 4), dtype=torch.int64, device=dev) if want_seen else None
     with torch.cuda.device(dev):
         _lib.check(lib.gs_espnet_score_crops(net_masks.data_ptr(), packed_labels.data_ptr(), tab, n, net_h, net_w, classes,
-                                             conf.data_ptr(), seen.data_ptr() if seen is not None else None, _stream_ptr(dev)))
+                                             conf.data_ptr(), seen.data_ptr() if seen is not None else None, _call.stream_ptr(dev)))
     return conf, seen
 
 
@@ -521,35 +514,14 @@ def segment_crops_host(engines, mean_stds, crops, net_h=512, net_w=1024, batch=3
     if n == 0:
         return {"masks": [] if want_masks else None, "net_maps": None, "counts": None, "overlays": [] if overlay is not None else None,
                 "conf": None, "seen": [] if labels is not None else None, "gt_overlays": [] if want_gt_overlay else None}
-    keep = []      # keeps converted inputs alive for the duration of the call
-    ptrs = (ctypes.c_void_p * n)()
-    hs, ws = (ctypes.c_int * n)(), (ctypes.c_int * n)()
-    for i, c in enumerate(crops):
-        if isinstance(c, torch.Tensor):
-            if c.is_cuda or c.dtype != torch.uint8 or c.dim() != 3 or c.shape[2] != 3 or not c.is_contiguous():
-                raise ValueError("crop %d: expected a contiguous uint8 [h,w,3] CPU tensor" % i)
-            ptrs[i] = c.data_ptr()
-        else:
-            c = np.ascontiguousarray(c, dtype=np.uint8)
-            if c.ndim != 3 or c.shape[2] != 3:
-                raise ValueError("crop %d: expected uint8 [h,w,3]" % i)
-            ptrs[i] = c.ctypes.data
-        keep.append(c)
-        hs[i], ws[i] = int(c.shape[0]), int(c.shape[1])
+    ptrs, shapes, keep = _call.host_image_ptrs(crops, "crop")      # keep: the converted inputs, alive for the duration of the call
+    hs, ws = (ctypes.c_int * n)(*[h for h, _ in shapes]), (ctypes.c_int * n)(*[w for _, w in shapes])
     eng0 = engines[0]
     handles = (ctypes.c_void_p * len(engines))(*[e.handle for e in engines])
-    means = (ctypes.c_float * (3 * len(engines)))(*[float(v) for ms in mean_stds for v in ms[0]])
-    stds = (ctypes.c_float * (3 * len(engines)))(*[float(v) for ms in mean_stds for v in ms[1]])
+    means, stds = _call.mean_std_arrays(mean_stds, len(engines))
     out_ptrs, out_buf, offs = None, None, None
     if want_masks:       # one pinned buffer for all maps: the library DMAs every map straight to its place
-        sizes = [int(hs[i]) * int(ws[i]) for i in range(n)]
-        offs = np.zeros(n + 1, dtype=np.int64)
-        # 256-byte slots, the alignment of the library's packed device buffer: a batch's maps then sit exactly as they do on the
-        # device and leave it as one DMA instead of one per crop (gs_espnet_segment_crops_host)
-        np.cumsum([(s + 255) // 256 * 256 for s in sizes], out=offs[1:])
-        out_buf = torch.empty(int(offs[-1]), dtype=torch.uint8, pin_memory=True)
-        base = out_buf.data_ptr()
-        out_ptrs = (ctypes.c_void_p * n)(*[base + int(offs[i]) for i in range(n)])
+        out_buf, offs, out_ptrs = _call.packed_pinned([h * w for h, w in shapes])
     net = torch.empty((n, net_h, net_w), dtype=torch.uint8, pin_memory=True) if want_net_maps else None
     hist = torch.zeros((n, eng0.classes), dtype=torch.int64, pin_memory=True) if want_hist else None
     x1 = y1 = None
@@ -562,22 +534,19 @@ def segment_crops_host(engines, mean_stds, crops, net_h=512, net_w=1024, batch=3
     if overlay is not None:     # one pinned buffer laid out like the library's packed input: a batch's overlays leave in one DMA
         palette, wa, wb = overlay
         pal = np.ascontiguousarray(palette, dtype=np.uint8).reshape(-1, 3)
-        ov_offs = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum([(int(hs[i]) * int(ws[i]) * 3 + 255) // 256 * 256 for i in range(n)], out=ov_offs[1:])
-        ov_buf = torch.empty(int(ov_offs[-1]), dtype=torch.uint8, pin_memory=True)
+        ov_buf, ov_offs, ov_ptrs = _call.packed_pinned([h * w * 3 for h, w in shapes])
         ov = _lib.CropOverlay()
         ov.palette_rgb = pal.ctypes.data
         ov.n_colours = int(pal.shape[0])
         ov.wa, ov.wb = float(wa), float(wb)
-        ov_ptrs = (ctypes.c_void_p * n)(*[ov_buf.data_ptr() + int(ov_offs[i]) for i in range(n)])
         ov.out_bgr = ctypes.cast(ov_ptrs, ctypes.POINTER(ctypes.c_void_p))
         keep.append(ov_ptrs)
     sc, conf, seen, gt_buf = None, None, None, None
     if labels is not None:
         lab_ptrs = (ctypes.c_void_p * n)()
         for i, lb in enumerate(labels):
-            if not isinstance(lb, np.ndarray) or lb.dtype != np.uint8 or lb.shape != (int(hs[i]), int(ws[i])):
-                raise ValueError("label %d: expected a uint8 [%d,%d] array" % (i, int(hs[i]), int(ws[i])))
+            if not isinstance(lb, np.ndarray) or lb.dtype != np.uint8 or lb.shape != shapes[i]:
+                raise ValueError("label %d: expected a uint8 [%d,%d] array" % ((i,) + shapes[i]))
             lb = np.ascontiguousarray(lb)
             keep.append(lb)
             lab_ptrs[i] = lb.ctypes.data
@@ -589,8 +558,7 @@ def segment_crops_host(engines, mean_stds, crops, net_h=512, net_w=1024, batch=3
         sc.gt_clamp = 1
         keep.append(lab_ptrs)
         if want_gt_overlay:     # laid out like the overlays
-            gt_buf = torch.empty(int(ov_offs[-1]), dtype=torch.uint8, pin_memory=True)
-            gt_ptrs = (ctypes.c_void_p * n)(*[gt_buf.data_ptr() + int(ov_offs[i]) for i in range(n)])
+            gt_buf, _, gt_ptrs = _call.packed_pinned([h * w * 3 for h, w in shapes])
             sc.gt_overlay_bgr = ctypes.cast(gt_ptrs, ctypes.POINTER(ctypes.c_void_p))
             keep.append(gt_ptrs)
     for e in engines:
@@ -604,18 +572,10 @@ def segment_crops_host(engines, mean_stds, crops, net_h=512, net_w=1024, batch=3
             _lib.check(lib.gs_espnet_segment_crops_host(*args))
         else:
             _lib.check(lib.gs_espnet_segment_crops_host_scored(*args, ctypes.byref(sc)))
-    masks = None
-    if want_masks:
-        flat = out_buf.numpy()
-        masks = [flat[int(offs[i]):int(offs[i]) + int(hs[i]) * int(ws[i])].reshape(int(hs[i]), int(ws[i])) for i in range(n)]
-    overlays = None
-    if ov is not None:
-        flat = ov_buf.numpy()
-        overlays = [flat[int(ov_offs[i]):int(ov_offs[i]) + int(hs[i]) * int(ws[i]) * 3].reshape(int(hs[i]), int(ws[i]), 3) for i in range(n)]
-    gt_overlays = None
-    if gt_buf is not None:
-        flat = gt_buf.numpy()
-        gt_overlays = [flat[int(ov_offs[i]):int(ov_offs[i]) + int(hs[i]) * int(ws[i]) * 3].reshape(int(hs[i]), int(ws[i]), 3) for i in range(n)]
+    masks = _call.packed_views(out_buf, offs, shapes) if want_masks else None
+    bgr_shapes = [(h, w, 3) for h, w in shapes]
+    overlays = _call.packed_views(ov_buf, ov_offs, bgr_shapes) if ov is not None else None
+    gt_overlays = _call.packed_views(gt_buf, ov_offs, bgr_shapes) if gt_buf is not None else None
     return {"masks": masks, "net_maps": net.numpy() if net is not None else None,
             "counts": hist.numpy() if hist is not None else None, "overlays": overlays,
             "conf": conf.astype(np.int64) if conf is not None else None,
@@ -633,11 +593,10 @@ def ensemble_segment(engines, tiles_u8, mean_stds):
     n, h, w, _ = tiles_u8.shape
     dev = tiles_u8.device
     handles = (ctypes.c_void_p * len(engines))(*[e.handle for e in engines])
-    means = (ctypes.c_float * (3 * len(engines)))(*[float(v) for ms in mean_stds for v in ms[0]])
-    stds = (ctypes.c_float * (3 * len(engines)))(*[float(v) for ms in mean_stds for v in ms[1]])
+    means, stds = _call.mean_std_arrays(mean_stds, len(engines))
     mask = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
     hist = torch.empty((n, engines[0].classes), dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         _lib.check(lib.gs_espnet_ensemble_forward(handles, len(engines), tiles_u8.data_ptr(), n, h, w, means, stds,
-                                                  mask.data_ptr(), hist.data_ptr(), _stream_ptr(dev)))
+                                                  mask.data_ptr(), hist.data_ptr(), _call.stream_ptr(dev)))
     return mask, hist

@@ -17,7 +17,6 @@ exact squared distances between the boundary pixels of the pair, on the GPU): th
 average surface distance and the root mean square, in map pixels.
 """
 import csv
-import ctypes
 import glob
 import os
 import sys
@@ -26,7 +25,7 @@ from fractions import Fraction
 
 import numpy as np
 
-from . import _lib
+from . import _call, _lib
 from . import instances
 
 GT_SUFFIX, PRED_SUFFIX = "_gt_classmap.png", "_pred_classmap.png"           # what wsi_eval writes
@@ -56,25 +55,12 @@ def parse_threshold(text):
 
 def workspace_bytes(height, width, pair_cap=4096):
     """gs_instance_match_plan: host-only"""
-    need = ctypes.c_size_t(0)
-    _lib.check(_lib.load().gs_instance_match_plan(int(height), int(width), int(pair_cap), ctypes.byref(need)))
-    return need.value
-
-
-def _device_map(m):
-    import torch
-    if not isinstance(m, torch.Tensor):
-        m = torch.from_numpy(np.array(m, dtype=np.uint8)).cuda()
-    if m.dtype != torch.uint8 or m.dim() != 2 or not m.is_cuda:
-        raise ValueError("a class map must be a uint8 [h,w] map on the GPU")
-    return m.contiguous()
+    return _call.planned_bytes(_lib.load().gs_instance_match_plan, height, width, pair_cap)
 
 
 def boundary_workspace_bytes(height, width):
     """gs_boundary_dist_plan: host-only"""
-    need = ctypes.c_size_t(0)
-    _lib.check(_lib.load().gs_boundary_dist_plan(int(height), int(width), ctypes.byref(need)))
-    return need.value
+    return _call.planned_bytes(_lib.load().gs_boundary_dist_plan, height, width)
 
 
 def boundary_ratios(stats, samples):
@@ -124,7 +110,7 @@ def boundary_distances(result):
     lg, lp = lg.contiguous(), lp.contiguous()
     match_gt, match_pred = result["match_gt"].contiguous(), result["match_pred"].contiguous()
     with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _call.stream_ptr(dev)
         ws = torch.empty(boundary_workspace_bytes(h, w), dtype=torch.uint8, device=dev)
         dist_gt = torch.empty((h, w), dtype=torch.int32, device=dev)
         dist_pred = torch.empty((h, w), dtype=torch.int32, device=dev)
@@ -154,7 +140,7 @@ def match_instances(gt_map, pred_map, classes=5, connectivity=8, iou=(1, 2), pai
     import torch
     lib = _lib.load()
     num, den = check_threshold(iou)
-    gt_map, pred_map = _device_map(gt_map), _device_map(pred_map)
+    gt_map, pred_map = (_call.device_map(m, "uint8", "a class map", upload=True) for m in (gt_map, pred_map))
     if gt_map.shape != pred_map.shape or gt_map.device != pred_map.device:
         raise ValueError("ground truth %s and prediction %s differ in size or device" % (tuple(gt_map.shape), tuple(pred_map.shape)))
     dev = gt_map.device
@@ -163,7 +149,7 @@ def match_instances(gt_map, pred_map, classes=5, connectivity=8, iou=(1, 2), pai
     with torch.cuda.device(dev):
         gt = instances.label_instances(gt_map, classes=classes, connectivity=connectivity, want_labels=True)
         pred = instances.label_instances(pred_map, classes=classes, connectivity=connectivity, want_labels=True)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _call.stream_ptr(dev)
         n_pairs = torch.empty(2, dtype=torch.int32, device=dev)
         while True:
             ws = torch.empty(workspace_bytes(h, w, pair_cap), dtype=torch.uint8, device=dev)

@@ -15,7 +15,6 @@ csrc/morphometry.hip) reduces the label map to ten exact integer sums and the sq
 morph_measures derives the float64 columns from those integers on the host.
 """
 import csv
-import ctypes
 import glob
 import math
 import os
@@ -24,7 +23,7 @@ from argparse import ArgumentParser
 
 import numpy as np
 
-from . import _lib
+from . import _call, _lib
 
 CLASS_NAMES = ['glomerulus', 'crescent', 'sclerosis', 'mesangium']        # area_stats.py:68
 MAP_SUFFIX = "_pred_classmap.png"                                          # what composite writes
@@ -35,9 +34,7 @@ MORPH_LENGTHS = ('equiv_diameter', 'major_axis', 'minor_axis', 'perimeter', 'fer
 
 def workspace_bytes(height, width, classes=5, cap=4096):
     """gs_instances_plan: host-only"""
-    need = ctypes.c_size_t(0)
-    _lib.check(_lib.load().gs_instances_plan(int(height), int(width), int(classes), int(cap), ctypes.byref(need)))
-    return need.value
+    return _call.planned_bytes(_lib.load().gs_instances_plan, height, width, classes, cap)
 
 
 def label_instances(class_map, classes=5, connectivity=8, cap=4096, want_labels=False):
@@ -46,11 +43,7 @@ def label_instances(class_map, classes=5, connectivity=8, cap=4096, want_labels=
     tensors on the map's device.  With more than `cap` instances it runs once more with cap = n."""
     import torch
     lib = _lib.load()
-    if not isinstance(class_map, torch.Tensor):
-        class_map = torch.from_numpy(np.array(class_map, dtype=np.uint8)).cuda()      # (a copy: the array may be read-only)
-    if class_map.dtype != torch.uint8 or class_map.dim() != 2 or not class_map.is_cuda:
-        raise ValueError("class_map must be a uint8 [h,w] map on the GPU")
-    class_map = class_map.contiguous()
+    class_map = _call.device_map(class_map, "uint8", "class_map", upload=True)
     dev = class_map.device
     h, w = class_map.shape
     with torch.cuda.device(dev):
@@ -63,7 +56,7 @@ def label_instances(class_map, classes=5, connectivity=8, cap=4096, want_labels=
             _lib.check(lib.gs_slide_instances(class_map.data_ptr(), h, w, int(classes), int(connectivity), ws.data_ptr(), ws.numel(),
                                               int(cap), boxes.data_ptr(), counts.data_ptr(),
                                               labels.data_ptr() if want_labels else None, n_found.data_ptr(),
-                                              ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                              _call.stream_ptr(dev)))
             n = int(n_found.item())
             if n <= cap:
                 break
@@ -73,9 +66,7 @@ def label_instances(class_map, classes=5, connectivity=8, cap=4096, want_labels=
 
 def morphometry_workspace_bytes(height, width, rows_cap):
     """gs_morphometry_plan: host-only"""
-    need = ctypes.c_size_t(0)
-    _lib.check(_lib.load().gs_morphometry_plan(int(height), int(width), int(rows_cap), ctypes.byref(need)))
-    return need.value
+    return _call.planned_bytes(_lib.load().gs_morphometry_plan, height, width, rows_cap)
 
 
 def morph_measures(stats, feret2, connectivity=8, mpp=None):
@@ -132,9 +123,7 @@ def morphometry(result, connectivity=8, mpp=None):
         raise ValueError("morphometry needs the label map: label_instances(..., want_labels=True)")
     if n > len(boxes):
         raise ValueError("%d instances but %d boxes: label_instances hit its cap and was not run again" % (n, len(boxes)))
-    if labels.dtype != torch.int32 or labels.dim() != 2 or not labels.is_cuda:
-        raise ValueError("labels must be an int32 [h,w] map on the GPU")
-    labels = labels.contiguous()
+    labels = _call.device_map(labels, "int32", "labels")
     boxes = boxes.to(torch.int32).contiguous()
     dev = labels.device
     h, w = labels.shape
@@ -150,7 +139,7 @@ def morphometry(result, connectivity=8, mpp=None):
         needed = torch.empty(1, dtype=torch.int64, device=dev)
         _lib.check(lib.gs_instance_morphometry(labels.data_ptr(), boxes.data_ptr() if n else None, n, h, w, ws.data_ptr(), ws.numel(),
                                                rows_cap, stats.data_ptr() if n else None, feret2.data_ptr() if n else None,
-                                               needed.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                               needed.data_ptr(), _call.stream_ptr(dev)))
         host_stats, host_feret2, rows_needed = stats.cpu().numpy(), feret2.cpu().numpy(), int(needed.item())
     if rows_needed != rows_cap:
         raise RuntimeError("gs_instance_morphometry needs %d rows, the boxes gave %d" % (rows_needed, rows_cap))

@@ -14,7 +14,6 @@ reads every <slide>_pred_classmap.png of DIR and writes the split map under the 
 --mpp (micrometres per MAP pixel) R is in micrometres.  The report has one row per original instance (REPORT_COLUMNS).
 """
 import csv
-import ctypes
 import glob
 import math
 import os
@@ -23,46 +22,32 @@ from argparse import ArgumentParser
 
 import numpy as np
 
-from . import _lib
+from . import _call, _lib
 from .instances import MAP_SUFFIX, label_instances
 
 REPORT_COLUMNS = ['slide', 'xmin', 'ymin', 'xmax', 'ymax', 'area', 'inscribed_radius', 'inscribed_x', 'inscribed_y', 'cores', 'parts_after']
 MIN_CORES, MAX_CORES = 2, 1024
 
 
-def _plan(fn, *args):
-    need = ctypes.c_size_t(0)
-    _lib.check(fn(*[int(a) for a in args], ctypes.byref(need)))
-    return need.value
-
-
 def edt_workspace_bytes(height, width):
     """gs_edt_plan: host-only"""
-    return _plan(_lib.load().gs_edt_plan, height, width)
+    return _call.planned_bytes(_lib.load().gs_edt_plan, height, width)
 
 
 def peaks_workspace_bytes(n):
     """gs_label_peaks_plan: host-only"""
-    return _plan(_lib.load().gs_label_peaks_plan, n)
+    return _call.planned_bytes(_lib.load().gs_label_peaks_plan, n)
 
 
 def split_workspace_bytes(height, width, n, c):
     """gs_split_plan: host-only"""
-    return _plan(_lib.load().gs_split_plan, height, width, n, c)
+    return _call.planned_bytes(_lib.load().gs_split_plan, height, width, n, c)
 
 
 def _label_map(labels):
-    import torch
     if labels is None:
         raise ValueError("the label map is needed: label_instances(..., want_labels=True)")
-    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or labels.dim() != 2 or not labels.is_cuda:
-        raise ValueError("labels must be an int32 [h,w] map on the GPU")
-    return labels.contiguous()
-
-
-def _stream(dev):
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    return _call.device_map(labels, "int32", "labels")
 
 
 def distance_map(result):
@@ -76,7 +61,7 @@ def distance_map(result):
     with torch.cuda.device(dev):
         ws = torch.empty(edt_workspace_bytes(h, w), dtype=torch.uint8, device=dev)
         d2 = torch.empty((h, w), dtype=torch.int32, device=dev)
-        _lib.check(lib.gs_foreground_edt(labels.data_ptr(), n, h, w, ws.data_ptr(), ws.numel(), d2.data_ptr(), _stream(dev)))
+        _lib.check(lib.gs_foreground_edt(labels.data_ptr(), n, h, w, ws.data_ptr(), ws.numel(), d2.data_ptr(), _call.stream_ptr(dev)))
     return d2
 
 
@@ -96,7 +81,7 @@ def label_peaks(labels, values, n):
         value = torch.empty(n, dtype=torch.int32, device=dev)
         pos = torch.empty(n, dtype=torch.int32, device=dev)
         _lib.check(lib.gs_label_peaks(labels.data_ptr(), values.data_ptr(), n, h, w, ws.data_ptr(), ws.numel(),
-                                      value.data_ptr() if n else None, pos.data_ptr() if n else None, _stream(dev)))
+                                      value.data_ptr() if n else None, pos.data_ptr() if n else None, _call.stream_ptr(dev)))
     return value, pos
 
 
@@ -141,7 +126,7 @@ def split_cut(class_map, labels, n, core_pos, core_r2, max_cores=64):
         cut = torch.empty(1, dtype=torch.int64, device=dev)
         _lib.check(lib.gs_split_cut(class_map.data_ptr(), labels.data_ptr(), n, core_pos.data_ptr() if c else None,
                                     core_r2.data_ptr() if c else None, c, int(max_cores), h, w, ws.data_ptr(), ws.numel(), parts.data_ptr(),
-                                    out_map.data_ptr(), per_instance.data_ptr() if n else None, cut.data_ptr(), _stream(dev)))
+                                    out_map.data_ptr(), per_instance.data_ptr() if n else None, cut.data_ptr(), _call.stream_ptr(dev)))
         cut_pixels = int(cut.item())
     return {"parts": parts, "map": out_map, "cores": per_instance, "cut_pixels": cut_pixels}
 
@@ -164,10 +149,8 @@ def split_touching(class_map, core_radius, classes=5, connectivity=8, min_core_a
     core_d2 = core_d2_of(core_radius)
     if not MIN_CORES <= int(max_cores) <= MAX_CORES:
         raise ValueError("max_cores must be %d..%d" % (MIN_CORES, MAX_CORES))
-    if not isinstance(class_map, torch.Tensor):
-        class_map = torch.from_numpy(np.array(class_map, dtype=np.uint8)).cuda()
+    class_map = _call.device_map(class_map, "uint8", "class_map", upload=True)
     res = label_instances(class_map, classes=classes, connectivity=connectivity, want_labels=True)
-    class_map = class_map.contiguous()
     d2 = distance_map(res)
     insc = inscribed(res, d2)
     with torch.cuda.device(class_map.device):

@@ -31,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import _lib, composite, detect, imageops, merge
+from . import _call, _lib, composite, detect, imageops, merge
 from .segment import metric_right
 
 MAGNIFICATION = 8
@@ -242,7 +242,7 @@ class WindowEvaluator:
             _lib.check(self.lib.gs_wsi_eval_windows(self.W, self.H, self.window, self.classes, ctypes.byref(st["sets"][0]),
                                                     ctypes.byref(st["sets"][1]), sx.data_ptr() if sx is not None else None,
                                                     sy.data_ptr() if sy is not None else None, st["mh"], st["mw"],
-                                                    st["hist"].data_ptr(), st["err"].data_ptr(), composite._sp(self.device)))
+                                                    st["hist"].data_ptr(), st["err"].data_ptr(), _call.stream_ptr(self.device)))
         out = {"hist_win": st["hist"], "hist": st["hist"].sum(0)}
         if st["maps"]:
             out["gt_map"], out["pred_map"] = st["small"]
@@ -263,7 +263,7 @@ def overlay_map(class_map, slide_bgr_small, wa=0.4, wb=0.6):
     if h and w:
         with torch.cuda.device(dev):
             _lib.check(lib.gs_overlay_classmap(img.data_ptr(), class_map.contiguous().data_ptr(), h, w, pal.data_ptr(), pal.shape[0],
-                                               ctypes.c_float(wa), ctypes.c_float(wb), out.data_ptr(), composite._sp(dev)))
+                                               ctypes.c_float(wa), ctypes.c_float(wb), out.data_ptr(), _call.stream_ptr(dev)))
     return out.cpu().numpy()
 
 

@@ -7,8 +7,8 @@ from conftest import REPO
 
 
 def assert_declared_exported_prototyped(header, table, names):
-    """the entries include/<header> declares are exactly `names` and exactly `table`'s (one of _lib's *_PROTOTYPES), none of them is
-    in another table, the library exports each, and each has the table's argument types and as many parameters as the header
+    """the entries include/<header> declares are exactly `names` and exactly `table`'s (_lib.HEADERS[header]), none of them is
+    in another header's table, the library exports each, and each has the table's argument types and as many parameters as the header
     gives it.  -> the header's text, for the caller's own phrase checks"""
     from glomeruli_segmentation_amd import _lib
     with open(os.path.join(REPO, "include", header)) as fh:
@@ -16,8 +16,9 @@ def assert_declared_exported_prototyped(header, table, names):
     code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     declared = set(re.findall(r"\b(gs_[a-z0-9_]+)\s*\(", code))
     assert declared == set(table) == set(names)
-    others = [t for k, t in vars(_lib).items() if k.endswith("PROTOTYPES") and t is not table]
-    assert others and not any(declared & set(t) for t in others)
+    assert _lib.HEADERS[header] is table
+    others = [t for h, t in _lib.HEADERS.items() if h != header]
+    assert others and not any(t is table or declared & set(t) for t in others)
     lib = _lib.load()
     assert lib.gs_abi_version() == _lib.ABI_VERSION == 10         # not bumped: the entries are found by looking them up
     out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
