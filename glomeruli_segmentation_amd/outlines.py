@@ -1,0 +1,270 @@
+"""Per-glomerulus outlines of a slide map: the closed loops of every instance, traced on the GPU, as GeoJSON or labelme files.
+
+The reference's end product per crop is a set of polygons (module/common/boundary_extractor.py, bound2line, restated per crop in
+contours.py).  Here the polygons are per INSTANCE of the composited slide map: gs_instance_outlines (csrc/outlines_abi.h,
+csrc/outlines.hip) follows the crack edges of every instance of the label map that instances.label_instances leaves on the device
+and returns one loop for its outer boundary and one for each hole, as lattice corner points (point (x, y) is the top-left corner
+of pixel (x, y)).  Everything is integer and exact; the definitions are in the header.
+
+    python -m glomeruli_segmentation_amd.outlines --classmap_dir DIR --output_dir DIR2
+           [--format geojson|labelme] [--classes 5] [--connectivity 8] [--min_area 0]
+           [--scale 1] [--epsilon 0] [--class_regions] [--gpu_id 0]
+
+One file per <slide>_pred_classmap.png: <slide>_outlines.geojson (a FeatureCollection QuPath opens; --scale 8 puts a 1/8 map's
+outlines on the slide) or <slide>_outlines.json (labelme; outer rings only, labelme has no holes).
+"""
+import ctypes
+import glob
+import json
+import os
+import sys
+from argparse import ArgumentParser
+
+import numpy as np
+
+from . import _call, _lib
+from .instances import CLASS_NAMES, MAP_SUFFIX, header, label_instances
+
+TABLES = ("loop_label", "loop_first", "loop_edges", "loop_area2")
+FORMATS = {"geojson": "_outlines.geojson", "labelme": "_outlines.json"}
+MAX_EDGES = 2 ** 31 - 1
+
+_P, _I = ctypes.c_void_p, ctypes.c_int
+# The two entries of csrc/outlines_abi.h, (restype, argtypes).  They are bound here and not in _lib.HEADERS: that maps the public
+# headers under include/, whose entry sets are fixed, and these two are declared beside their sources.
+OUTLINE_ENTRIES = {
+    "gs_outlines_plan": (_I, [_I, _I, ctypes.c_longlong, ctypes.POINTER(ctypes.c_size_t)]),
+    "gs_instance_outlines": (_I, [_P, _I, _I, _I, _I, _P, ctypes.c_size_t, ctypes.c_longlong, _P, _P, _P, _P, _P, _P, _P, _P]),
+}
+
+
+def load():
+    """_lib.load() with OUTLINE_ENTRIES bound; AttributeError where the library does not export them (there is no fallback)"""
+    lib = _lib.load()
+    for name, (res, args) in OUTLINE_ENTRIES.items():
+        fn = getattr(lib, name)
+        if fn.argtypes != args:
+            fn.restype, fn.argtypes = res, args
+    return lib
+
+
+def outlines_workspace_bytes(height, width, edges_cap):
+    """gs_outlines_plan: host-only"""
+    return _call.planned_bytes(load().gs_outlines_plan, height, width, edges_cap)
+
+
+def trace_outlines(result, connectivity=8, edges_cap=None):
+    """result: label_instances(..., want_labels=True)'s dict -> {"loop_label", "loop_first", "loop_edges" int32 [n_loops],
+    "loop_area2" int64 [n_loops], "loop_offsets" int32 [n_loops + 1], "points" int32 [n_points,2] (tensors on the map's device),
+    "edges", "n_loops", "n_points", "calls"}.  connectivity is the one the map was labelled with.  edges_cap: the edges the first
+    call has room for (None: a quarter of the pixels); where the map has more, one more call with exactly edges_needed."""
+    import torch
+    lib = load()
+    labels, n = result["labels"], int(result["n"])
+    if labels is None:
+        raise ValueError("trace_outlines needs the label map: label_instances(..., want_labels=True)")
+    if connectivity not in (4, 8):
+        raise ValueError("connectivity must be 4 or 8")
+    labels = _call.device_map(labels, "int32", "labels")
+    dev = labels.device
+    h, w = labels.shape
+    cap = max(4096, h * w // 4) if edges_cap is None else int(edges_cap)
+    cap = min(cap, 4 * h * w, MAX_EDGES)
+    with torch.cuda.device(dev):
+        counts = torch.empty(3, dtype=torch.int64, device=dev)
+        for calls in (1, 2):
+            ws = torch.empty(outlines_workspace_bytes(h, w, cap), dtype=torch.uint8, device=dev)
+            rows = cap // 4
+            out = {k: torch.empty(rows, dtype=torch.int64 if k == "loop_area2" else torch.int32, device=dev) for k in TABLES}
+            out["loop_offsets"] = torch.empty(rows + 1, dtype=torch.int32, device=dev)
+            out["points"] = torch.empty((cap, 2), dtype=torch.int32, device=dev)
+            ptr = {k: v.data_ptr() if v.numel() else None for k, v in out.items()}
+            _lib.check(lib.gs_instance_outlines(labels.data_ptr(), n, h, w, int(connectivity), ws.data_ptr(), ws.numel(), cap,
+                                                ptr["loop_label"], ptr["loop_first"], ptr["loop_edges"], ptr["loop_area2"],
+                                                ptr["loop_offsets"], ptr["points"], counts.data_ptr(), _call.stream_ptr(dev)))
+            edges, n_loops, n_points = [int(v) for v in counts.tolist()]
+            if edges <= cap:
+                break
+            if calls == 2 or edges > MAX_EDGES:
+                raise RuntimeError("gs_instance_outlines needs room for %d edges (had %d)" % (edges, cap))
+            cap = edges          # the one retry
+    traced = {k: out[k][:n_loops] for k in TABLES}
+    traced.update(loop_offsets=out["loop_offsets"][:n_loops + 1], points=out["points"][:n_points], edges=edges, n_loops=n_loops,
+                  n_points=n_points, calls=calls)
+    return traced
+
+
+def _host(v):
+    return np.asarray(v.cpu() if hasattr(v, "cpu") else v)
+
+
+def instance_polygons(traced):
+    """-> {instance id: {"outer": [ring, ...], "holes": [ring, ...]}}, ids ascending, every ring an int64 [m,2] array of (x, y)
+    corners, not closed.  A loop of positive loop_area2 is an outer ring (clockwise on screen), a negative one a hole; within an
+    instance the rings keep the loops' order."""
+    label, area2 = _host(traced["loop_label"]).astype(np.int64), _host(traced["loop_area2"]).astype(np.int64)
+    offsets, points = _host(traced["loop_offsets"]).astype(np.int64), _host(traced["points"]).astype(np.int64).reshape(-1, 2)
+    out = {}
+    for l in np.argsort(label, kind="stable").tolist():
+        entry = out.setdefault(int(label[l]), {"outer": [], "holes": []})
+        entry["outer" if area2[l] > 0 else "holes"].append(points[offsets[l]:offsets[l + 1]].copy())
+    return out
+
+
+def ring_area2(ring):
+    """the shoelace sum of a ring: twice its signed area, positive for clockwise on screen"""
+    r = np.asarray(ring).astype(np.int64).reshape(-1, 2)
+    nxt = np.roll(r, -1, axis=0)
+    return int((r[:, 0] * nxt[:, 1] - nxt[:, 0] * r[:, 1]).sum())
+
+
+def ring_length(ring):
+    """the crack edges of a ring of lattice corners"""
+    r = np.asarray(ring).astype(np.int64).reshape(-1, 2)
+    return int(np.abs(np.roll(r, -1, axis=0) - r).sum())
+
+
+def _inside(ring, px, py):
+    """even-odd rule for a point off the lattice against a ring of axis-parallel edges"""
+    r = np.asarray(ring).astype(np.float64).reshape(-1, 2)
+    nxt = np.roll(r, -1, axis=0)
+    vertical = (r[:, 0] == nxt[:, 0]) & (r[:, 0] > px)
+    lo, hi = np.minimum(r[:, 1], nxt[:, 1]), np.maximum(r[:, 1], nxt[:, 1])
+    return int((vertical & (lo < py) & (py < hi)).sum()) % 2 == 1
+
+
+def _parts(entry):
+    """[(outer, [holes])]: every hole with the outer ring that contains it (the pixel at a hole's topmost-leftmost corner lies
+    inside the hole)"""
+    parts = [(outer, []) for outer in entry["outer"]]
+    for hole in entry["holes"]:
+        hx, hy = min(np.asarray(hole).reshape(-1, 2).tolist(), key=lambda p: (p[1], p[0]))
+        owner = next((k for k, (outer, _) in enumerate(parts) if _inside(outer, hx + 0.5, hy + 0.5)), 0)
+        if parts:
+            parts[owner][1].append(hole)
+    return parts
+
+
+def _closed(ring, scale):
+    pts = [[x * scale, y * scale] for x, y in np.asarray(ring).reshape(-1, 2).tolist()]
+    return pts + [pts[0]]
+
+
+def class_names(classes=5):
+    return header(classes)[7:]
+
+
+def geojson(polygons, result, slide, classes=5, scale=1, label=None):
+    """polygons: instance_polygons' dict; result: label_instances' dict (boxes and counts) -> a FeatureCollection: one Polygon per
+    instance -- the outer ring first, then its holes, every ring closed, coordinates times `scale` -- or a MultiPolygon where an
+    instance has several outer rings (labels and rule disagree).  Properties: the instance id, its box, its pixels per class
+    (instances.header's names), area_px, perimeter_cracks and classification.name, the class with the most pixels.  label: the
+    rings are regions of that class inside the instances (--class_regions): classification.name is `label`, area_px the rings'."""
+    boxes, counts = _host(result["boxes"]).astype(np.int64), _host(result["counts"]).astype(np.int64)
+    names = class_names(classes)
+    features = []
+    for inst, entry in polygons.items():
+        parts = _parts(entry)
+        if not parts:
+            continue
+        rings = [[_closed(outer, scale)] + [_closed(hole, scale) for hole in holes] for outer, holes in parts]
+        geometry = {"type": "Polygon", "coordinates": rings[0]} if len(rings) == 1 else {"type": "MultiPolygon", "coordinates": rings}
+        all_rings = entry["outer"] + entry["holes"]
+        props = {"slide": slide, "instance": int(inst), "box": boxes[inst - 1].tolist() if 1 <= inst <= len(boxes) else None,
+                 "perimeter_cracks": sum(ring_length(r) for r in all_rings)}
+        if label is None and 1 <= inst <= len(counts):
+            c = counts[inst - 1].tolist()
+            props.update(dict(zip(names, c[1:])))
+            props["area_px"] = int(sum(c))
+            props["classification"] = {"name": names[int(np.argmax(c[1:]))]}
+        else:
+            props["area_px"] = sum(ring_area2(r) for r in all_rings) // 2
+            props["classification"] = {"name": label if label is not None else names[0]}
+        features.append({"type": "Feature", "id": "%s:%d" % (slide, inst) if label is None else "%s:%d:%s" % (slide, inst, label),
+                         "geometry": geometry, "properties": props})
+    return {"type": "FeatureCollection", "features": features}
+
+
+def labelme(polygons, image_name, label=CLASS_NAMES[0]):
+    """-> a dict with the keys of contours.labelme_dict: one shape per outer ring (labelme has no holes)"""
+    shapes = [{"line_color": None, "points": np.asarray(outer).reshape(-1, 2).tolist(), "fill_color": None, "label": label}
+              for entry in polygons.values() for outer in entry["outer"]]
+    return {"shapes": shapes, "lineColor": [0, 0, 0, 255], "imagePath": image_name, "flags": {}, "fillColor": [0, 0, 0, 255]}
+
+
+def simplified(polygons, epsilon):
+    """every ring through contours.approx_poly(ring, epsilon * contours.arc_length(ring)), as bound2line does; rings left with
+    fewer than 3 points are dropped, and an instance without an outer ring with them"""
+    from . import contours
+    out = {}
+    for inst, entry in polygons.items():
+        kept = {}
+        for kind in ("outer", "holes"):
+            rings = [contours.approx_poly(r, epsilon * contours.arc_length(r)).reshape(-1, 2).astype(np.int64) for r in entry[kind]]
+            kept[kind] = [r for r in rings if len(r) >= 3]
+        if kept["outer"]:
+            out[inst] = kept
+    return out
+
+
+def build_parser():
+    p = ArgumentParser(description='per-glomerulus outlines of the composited slide class maps, traced on the GPU')
+    p.add_argument('--classmap_dir', required=True, help='directory of the <slide>_pred_classmap.png files composite writes')
+    p.add_argument('--output_dir', required=True)
+    p.add_argument('--format', default='geojson', choices=sorted(FORMATS))
+    p.add_argument('--classes', type=int, default=5)
+    p.add_argument('--connectivity', type=int, default=8, choices=[4, 8])
+    p.add_argument('--min_area', type=int, default=0, help='drop instances with fewer foreground pixels')
+    p.add_argument('--scale', type=float, default=1, help='multiplies every coordinate (8 puts a 1/8 map on its slide)')
+    p.add_argument('--epsilon', type=float, default=0, help='above 0: simplify every ring to within this fraction of its length')
+    p.add_argument('--class_regions', action='store_true', help='also the regions of every class >= 2 inside the instances')
+    p.add_argument('--gpu_id', type=int, default=0)
+    return p
+
+
+def main(argv=None, out=sys.stdout):
+    args = build_parser().parse_args(argv)
+    import torch
+    from PIL import Image
+    from .composite import relabel
+    if not torch.cuda.is_available():
+        raise RuntimeError("no HIP device: the outlines are traced on the GPU, there is no host path")
+    paths = sorted(glob.glob(os.path.join(args.classmap_dir, "*" + MAP_SUFFIX)))
+    if not paths:
+        raise FileNotFoundError("no *%s under %s" % (MAP_SUFFIX, args.classmap_dir))
+    os.makedirs(args.output_dir, exist_ok=True)
+    scale = int(args.scale) if float(args.scale).is_integer() else args.scale
+    names = class_names(args.classes)
+
+    def polygons_of(res, keep):
+        polys = instance_polygons(trace_outlines(res, args.connectivity))
+        polys = {i: e for i, e in polys.items() if i in keep}
+        return simplified(polys, args.epsilon) if args.epsilon > 0 else polys
+    with torch.cuda.device(args.gpu_id):
+        for path in paths:
+            slide = os.path.basename(path)[:-len(MAP_SUFFIX)]
+            cm = relabel(np.ascontiguousarray(np.asarray(Image.open(path)), dtype=np.uint8))
+            if cm.ndim != 2:
+                raise ValueError("%s is not a single-channel class map" % path)
+            cm = torch.from_numpy(np.array(cm)).cuda()
+            res = label_instances(cm, classes=args.classes, connectivity=args.connectivity, want_labels=True)
+            keep = set((np.nonzero(_host(res["counts"]).sum(axis=1) >= args.min_area)[0] + 1).tolist())
+            polys = polygons_of(res, keep)
+            image_name = os.path.basename(path)
+            doc = geojson(polys, res, slide, args.classes, scale) if args.format == "geojson" else labelme(polys, image_name)
+            if args.class_regions:
+                for c in range(2, args.classes):
+                    region = dict(res, labels=torch.where(cm == c, res["labels"], torch.zeros_like(res["labels"])))
+                    part = polygons_of(region, keep)
+                    if args.format == "geojson":
+                        doc["features"] += geojson(part, res, slide, args.classes, scale, label=names[c - 1])["features"]
+                    else:
+                        doc["shapes"] += labelme(part, image_name, label=names[c - 1])["shapes"]
+            with open(os.path.join(args.output_dir, slide + FORMATS[args.format]), 'w') as f:
+                json.dump(doc, f)
+            print("{}: {} instances, {} outlined".format(slide, res["n"], len(polys)), file=out)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
