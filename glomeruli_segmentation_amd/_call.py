@@ -14,6 +14,17 @@ _IMAGE_ERRORS = {"crop": ("crop %d: expected a contiguous uint8 [h,w,3] CPU tens
                  "window": ("window %d: expected a contiguous uint8 CPU tensor",) + ("window %d: expected uint8 [H,W,3], every window of one size",) * 2}
 
 
+def bound(entries):
+    """_lib.load() with a module's own table {name: (restype, argtypes)} bound; AttributeError where the library does not export
+    an entry (there is no fallback)"""
+    lib = _lib.load()
+    for name, (res, args) in entries.items():
+        fn = getattr(lib, name)
+        if fn.argtypes != args:
+            fn.restype, fn.argtypes = res, args
+    return lib
+
+
 def stream_ptr(device):
     """torch's current stream on `device`, as the hipStream_t argument of a library call"""
     import torch

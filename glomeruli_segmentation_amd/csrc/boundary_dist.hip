@@ -6,11 +6,11 @@
 //   1 bdist_zero_kernel    stats = 0
 //   2 bdist_rows_kernel    one wave per (row, side): the row in chunks of 64 pixels left to right, then right to left, four
 //                          chunks' tests ahead of their links so that the loads overlap.  A lane
-//                          tests its pixel (the label and its four neighbours), the wave's ballot of the tests gives every lane
+//                          tests its pixel (boundary_links.h's boundary_pixel), the wave's ballot of the tests gives every lane
 //                          the nearest set bit at or below / at or above its own, and the nearest column of the chunks already
 //                          done is carried in a register: a segmented scan in the wave, no atomics, no LDS.  It writes, per
 //                          side, the column of the nearest boundary pixel OF ANY VALID INSTANCE at or left of x and at or right
-//                          of x, 0xFFFF for none.
+//                          of x, kLinkNone for none.
 //   3 bdist_query_kernel   direction 0: one lane per pixel of LG.  A boundary pixel of a paired g reads its partner id once and
 //                          walks the rows y, y-1, y+1, y-2, ... of LP's tables while k*k < best; in a row it hops from x to the
 //                          left and to the right along the links, skips boundary pixels of other instances and stops at the
@@ -38,7 +38,7 @@
 //   a hop sequence    the column strictly falls (left) or rises (right) with every hop: a link at c-1 is at most c-1, one at
 //                     c+1 at least c+1; it ends at none, at the row's end, at the partner or at dx*dx + k*k >= best: at most
 //                     width hops
-// A link is a column the row pass itself stored (< width) or 0xFFFF, so no link leads out of its row, and an id is used as an
+// A link is a column the row pass itself stored (< width) or kLinkNone, so no link leads out of its row, and an id is used as an
 // index only after its range test.
 //
 // Inconsistent match arrays.  A pair is believed only when both arrays agree and both ids are in range; a partner that owns no
@@ -46,6 +46,7 @@
 #include "gs_internal.h"
 #include "boundary_dist_plan.h"
 #include "wave_block.h"
+#include "boundary_links.h"
 #include "../../include/glomseg_boundary_dist.h"
 
 #include <climits>
@@ -60,19 +61,6 @@ typedef unsigned short u16;
 constexpr int kThreads = kBdistThreads;
 static_assert(kThreads == 256, "four waves per workgroup: the row pass's wave index");
 constexpr int kBatch = 4, kSpan = 64 * kBatch;     // the row pass tests this many chunks of 64 pixels before it links them
-
-// Is (x, y), a pixel of the map, a boundary pixel of a valid instance of L?  id: its label (any value where the answer is no).
-// No branch: the five loads go out together.  A neighbour beyond the map's edge is read at the pixel itself, and the edge
-// test beside it decides.
-__device__ inline bool boundary_pixel(const int *__restrict__ L, int n, int H, int W, int y, int x, int &id)
-{
-    const size_t i = (size_t)y * W + x;
-    const int a = L[i];
-    const int l = L[i - (x > 0 ? 1 : 0)], r = L[i + (x < W - 1 ? 1 : 0)];
-    const int u = L[i - (y > 0 ? (size_t)W : 0)], d = L[i + (y < H - 1 ? (size_t)W : 0)];
-    id = a;
-    return (a >= 1) & (a <= n) & ((x == 0) | (l != a) | (x == W - 1) | (r != a) | (y == 0) | (u != a) | (y == H - 1) | (d != a));
-}
 
 // 1 ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void bdist_zero_kernel(u64 *__restrict__ stats, long long words)
@@ -109,7 +97,7 @@ __global__ __launch_bounds__(kThreads) void bdist_rows_kernel(const int *__restr
     u16 *__restrict__ left = (pred ? left_pred : left_gt) + (size_t)y * W;
     u16 *__restrict__ right = (pred ? right_pred : right_gt) + (size_t)y * W;
     int id;
-    int carry = kBdistNone;
+    int carry = kLinkNone;
     for (int x0 = 0; x0 < W; x0 += kSpan) {        // wave-uniform
         u64 m[kBatch];
 #pragma unroll
@@ -127,7 +115,7 @@ __global__ __launch_bounds__(kThreads) void bdist_rows_kernel(const int *__restr
                 carry = xb + 63 - __clzll((long long)m[b]);
         }
     }
-    carry = kBdistNone;
+    carry = kLinkNone;
     for (int x0 = (W - 1) / kSpan * kSpan; x0 >= 0; x0 -= kSpan) {
         u64 m[kBatch];
 #pragma unroll
@@ -165,7 +153,7 @@ __device__ inline int nearest_of_partner(const int *__restrict__ T, const u16 *_
                 continue;
             const size_t row = (size_t)(s == 0 ? y - k : y + k) * W;
             int c = left[row + x];
-            while (c != kBdistNone) {              // c falls with every hop
+            while (c != kLinkNone) {              // c falls with every hop
                 const int d = (x - c) * (x - c) + kk;
                 if (d >= best)
                     break;
@@ -178,7 +166,7 @@ __device__ inline int nearest_of_partner(const int *__restrict__ T, const u16 *_
                 c = left[row + c - 1];
             }
             c = right[row + x];
-            while (c != kBdistNone) {              // c rises with every hop
+            while (c != kLinkNone) {              // c rises with every hop
                 const int d = (c - x) * (c - x) + kk;
                 if (d >= best)
                     break;

@@ -10,6 +10,7 @@ namespace gs {
 constexpr int kBdistThreads = 256;          // threads of every launch: four waves
 constexpr int kBdistMaxSide = 32768;        // a column fits a uint16 beside the "none" word, and 2 * 32767^2 < 2^31: d2 is an int32
 constexpr unsigned short kBdistNone = 0xFFFF;
+static_assert(kBdistNone == kLinkNone, "the link tables of every row pass end in one sentinel");
 
 struct BoundaryDistPlan {
     int n_pixels = 0;          // height * width <= INT_MAX

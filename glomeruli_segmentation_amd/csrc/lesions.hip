@@ -3,8 +3,8 @@
 // map the covered unit edges, the arcs they form on the cycle and the longest arc.  Plans: lesions_plan.h.
 //
 // gs_rim_classes, one launch.
-//   rim_kernel   a workgroup per tile of 64 x 16 pixels, four pixels a thread.  Every thread tests its pixels (the label and its
-//                four neighbours, from global memory); a tile without a boundary pixel writes its zeros and leaves.  Otherwise the
+//   rim_kernel   a workgroup per tile of 64 x 16 pixels, four pixels a thread.  Every thread tests its pixels (boundary_links.h's
+//                boundary_pixel, from global memory); a tile without a boundary pixel writes its zeros and leaves.  Otherwise the
 //                boundary pixels go into a list in LDS (an LDS counter hands out the places; the order does not matter, every
 //                pixel's word is a function of the inputs alone), every other pixel gets its 0, and the workgroup stages the tile
 //                with a halo of R = floor(sqrt(max_d2)) cells: the label and the class of every cell, label 0 outside the map, and
@@ -74,6 +74,7 @@
 #include "lesions_abi.h"
 #include "lesions_plan.h"
 #include "wave_block.h"
+#include "boundary_links.h"
 
 namespace gs {
 
@@ -87,18 +88,6 @@ static_assert(kThreads == 256 && kRimTileW * kRimTileH == 4 * kThreads, "four wa
 static_assert(kRimTileW == 64, "a tile pixel's index is row * 64 + column");
 
 // ------------------------------------------------------------------------------------------------------------------- the rim
-// Is (x, y), a pixel of the map, a boundary pixel of a valid instance of L?  id: its label.  No branch: the five loads go out
-// together; a neighbour beyond the map's edge is read at the pixel itself, and the edge test beside it decides (zones.hip's).
-__device__ inline bool boundary_pixel(const int *__restrict__ L, int n, int H, int W, int y, int x, int &id)
-{
-    const size_t i = (size_t)y * W + x;
-    const int a = L[i];
-    const int l = L[i - (x > 0 ? 1 : 0)], r = L[i + (x < W - 1 ? 1 : 0)];
-    const int u = L[i - (y > 0 ? (size_t)W : 0)], d = L[i + (y < H - 1 ? (size_t)W : 0)];
-    id = a;
-    return (a >= 1) & (a <= n) & ((x == 0) | (l != a) | (x == W - 1) | (r != a) | (y == 0) | (u != a) | (y == H - 1) | (d != a));
-}
-
 __global__ __launch_bounds__(kThreads) void rim_kernel(const int *__restrict__ L, const unsigned char *__restrict__ C, int n, int classes,
                                                        int H, int W, int max_d2, int reach, int tiles_x, int cw, int ch,
                                                        int *__restrict__ out)

@@ -14,6 +14,10 @@ namespace gs {
 constexpr size_t kPlanAlign = 256;   // every part of a workspace starts at a multiple of it
 inline size_t plan_align(size_t v) { return (v + kPlanAlign - 1) / kPlanAlign * kPlanAlign; }
 
+// A uint16 link table of a row pass (bdist_rows_kernel, foreign_rows_kernel) holds a column, below the 32768 a plan allows a side,
+// or this: no boundary pixel on that side of the row.
+constexpr int kLinkNone = 0xFFFF;
+
 // The parts of a workspace one behind the other: take(n) is the offset of a part of n bytes, and `off`, when all are taken, the
 // size of the whole.
 struct PlanCursor {

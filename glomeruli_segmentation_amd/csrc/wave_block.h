@@ -6,7 +6,7 @@
 // two-level -- count per block, scan, rank per block -- with the kernel boundary in between); every loop has a monotone bound, so
 // there is no spin loop; a barrier is reached by every thread of its workgroup; counters are written with ordinary vector atomics
 // and stores; an entry allocates nothing and writes every byte of workspace and output that it later reads.  The .hip files
-// state only the bounds of their own loops.
+// state only the bounds of their own loops.  boundary_links.h (the boundary-pixel test) stands under the same rules.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -25,10 +25,10 @@
 // is beyond max_d2.
 // gs_foreign_dist, two launches.
 //   1 foreign_rows_kernel   one wave per row: the row in chunks of 64 pixels left to right, then right to left.  A lane tests its
-//                           pixel (the label and its four neighbours), the wave's ballot of the tests gives every lane the nearest
+//                           pixel (boundary_links.h's boundary_pixel), the wave's ballot of the tests gives every lane the nearest
 //                           set bit at or below / at or above its own, and the nearest column of the chunks already done is carried
 //                           in a register: a segmented scan in the wave.  It writes the column of the nearest boundary pixel of any
-//                           instance at or left of x and at or right of x, kZoneNone for none.
+//                           instance at or left of x and at or right of x, kLinkNone for none.
 //   2 foreign_query_kernel  one lane per pixel.  A boundary pixel of instance a walks the rows y, y-1, y+1, y-2, ... while
 //                           k^2 <= min(best, max_d2); in a row it hops from x to the left and to the right along the links, skips
 //                           the pixels of a and takes the first pixel of another instance on each side; a hop sequence ends at
@@ -58,11 +58,12 @@
 //                         y + k lie outside the map
 //   a hop sequence        the column strictly falls (left) or rises (right) with every hop: a link at c - 1 is at most c - 1, one
 //                         at c + 1 at least c + 1: at most width hops
-// A link is a column the row pass itself stored (< width) or kZoneNone, so no link leads out of its row.  Nothing is indexed by a
+// A link is a column the row pass itself stored (< width) or kLinkNone, so no link leads out of its row.  Nothing is indexed by a
 // label: a label is only compared, after its range test.
 #include "gs_internal.h"
 #include "zones_plan.h"
 #include "zones_abi.h"
+#include "boundary_links.h"
 
 namespace gs {
 
@@ -265,19 +266,6 @@ __global__ __launch_bounds__(kThreads) void zone_row_kernel(const u16 *__restric
 }
 
 // ------------------------------------------------------------------------------------------------------------------- the gaps
-// Is (x, y), a pixel of the map, a boundary pixel of a valid instance of L?  id: its label (any value where the answer is no).
-// No branch: the five loads go out together.  A neighbour beyond the map's edge is read at the pixel itself, and the edge
-// test beside it decides.
-__device__ inline bool boundary_pixel(const int *__restrict__ L, int n, int H, int W, int y, int x, int &id)
-{
-    const size_t i = (size_t)y * W + x;
-    const int a = L[i];
-    const int l = L[i - (x > 0 ? 1 : 0)], r = L[i + (x < W - 1 ? 1 : 0)];
-    const int u = L[i - (y > 0 ? (size_t)W : 0)], d = L[i + (y < H - 1 ? (size_t)W : 0)];
-    id = a;
-    return (a >= 1) & (a <= n) & ((x == 0) | (l != a) | (x == W - 1) | (r != a) | (y == 0) | (u != a) | (y == H - 1) | (d != a));
-}
-
 __global__ __launch_bounds__(kThreads) void foreign_rows_kernel(const int *__restrict__ L, int n, int H, int W, u16 *__restrict__ left_all,
                                                                 u16 *__restrict__ right_all)
 {
@@ -288,7 +276,7 @@ __global__ __launch_bounds__(kThreads) void foreign_rows_kernel(const int *__res
     u16 *__restrict__ left = left_all + (size_t)y * W;
     u16 *__restrict__ right = right_all + (size_t)y * W;
     int id;
-    int carry = kZoneNone;
+    int carry = kLinkNone;
     for (int x0 = 0; x0 < W; x0 += kSpan) {        // wave-uniform
         u64 m[kBatch];
 #pragma unroll
@@ -306,7 +294,7 @@ __global__ __launch_bounds__(kThreads) void foreign_rows_kernel(const int *__res
                 carry = xb + 63 - __clzll((long long)m[b]);
         }
     }
-    carry = kZoneNone;
+    carry = kLinkNone;
     for (int x0 = (W - 1) / kSpan * kSpan; x0 >= 0; x0 -= kSpan) {
         u64 m[kBatch];
 #pragma unroll
@@ -345,7 +333,7 @@ __device__ inline void nearest_foreign(const int *__restrict__ L, const u16 *__r
                 continue;
             const size_t row = (size_t)(s == 0 ? y - k : y + k) * W;
             int c = left[row + x];
-            while (c != kZoneNone) {               // c falls with every hop
+            while (c != kLinkNone) {               // c falls with every hop
                 const int d = (x - c) * (x - c) + kk;                  // < 2^31
                 if (d > best || d > max_d2)
                     break;
@@ -362,7 +350,7 @@ __device__ inline void nearest_foreign(const int *__restrict__ L, const u16 *__r
                 c = left[row + c - 1];
             }
             c = right[row + x];
-            while (c != kZoneNone) {               // c rises with every hop
+            while (c != kLinkNone) {               // c rises with every hop
                 const int d = (c - x) * (c - x) + kk;
                 if (d > best || d > max_d2)
                     break;

@@ -18,7 +18,7 @@ constexpr int kZoneMaxSide = 32768;             // a column distance is at most 
 constexpr int kZoneMaxD2 = 1 << 30;             // max_d2 at the most: max_d2 + 1 and every dx*dx up to it stay inside int32
 constexpr int kZoneBand = 32;                   // rows of a band of the column pass
 constexpr int kZoneLdsCols = 16384;             // the row pass stages a row of g in LDS up to this width (32 KB), beyond it reads global
-constexpr int kZoneNone = 0xFFFF;               // g: no instance pixel within reach; a link: no boundary pixel on that side
+constexpr int kZoneNone = 0xFFFF;               // g: no instance pixel within reach (a link without a target is kLinkNone)
 
 struct ZonePlan {
     int bands = 0;             // ceil(height / kZoneBand)

@@ -16,7 +16,6 @@ integers.
 exact squared distances between the boundary pixels of the pair, on the GPU): the Hausdorff distance, its 95th percentile, the
 average surface distance and the root mean square, in map pixels.
 """
-import csv
 import glob
 import os
 import sys
@@ -25,8 +24,9 @@ from fractions import Fraction
 
 import numpy as np
 
-from . import _call, _lib
+from . import _call, _lib, _slides
 from . import instances
+from ._slides import host as _host
 
 GT_SUFFIX, PRED_SUFFIX = "_gt_classmap.png", "_pred_classmap.png"           # what wsi_eval writes
 IOU_DEN_MAX = 65535
@@ -186,10 +186,6 @@ def header(classes=5, boundary=False):
             + ['gt_' + c for c in names] + ['pred_' + c for c in names] + (BOUNDARY_COLUMNS if boundary else []))
 
 
-def _host(v):
-    return np.asarray(v.cpu() if hasattr(v, "cpu") else v)
-
-
 def on_host(result):
     """the result as numpy arrays, without the label maps: what instance_rows and summary need of it"""
     def side(t):
@@ -322,21 +318,12 @@ def main(argv=None, out=sys.stdout):
     args = build_parser().parse_args(argv)
     iou = parse_threshold(args.iou_threshold)
     import torch
-    from PIL import Image
-    from .composite import relabel
-    if not torch.cuda.is_available():
-        raise RuntimeError("no HIP device: the instances are labelled and matched on the GPU, there is no host path")
+    _slides.require_device("the instances are labelled and matched on the GPU")
     triples = find_pairs(args.eval_dir)
-
-    def read(path):
-        cm = relabel(np.ascontiguousarray(np.asarray(Image.open(path)), dtype=np.uint8))
-        if cm.ndim != 2:
-            raise ValueError("%s is not a single-channel class map" % path)
-        return cm
     rows, lines, results = [], [], []
     with torch.cuda.device(args.gpu_id):
         for slide, gt_path, pred_path in triples:
-            gt, pred = read(gt_path), read(pred_path)
+            gt, pred = _slides.read_map(gt_path), _slides.read_map(pred_path)
             if gt.shape != pred.shape:
                 raise ValueError("%s is %d x %d but %s is %d x %d" % ((pred_path,) + pred.shape[::-1] + (gt_path,) + gt.shape[::-1]))
             res = match_instances(gt, pred, classes=args.classes, connectivity=args.connectivity, iou=iou, boundary=args.boundary)
@@ -352,14 +339,8 @@ def main(argv=None, out=sys.stdout):
     if args.boundary:
         s.update(boundary_summary(results))
     lines.append(summary_row("all", s))
-    with open(args.output_csv, 'w') as f:
-        writer = csv.writer(f)
-        writer.writerow(header(args.classes, args.boundary))
-        writer.writerows(rows)
-    with open(args.summary_tsv, 'w') as f:
-        writer = csv.writer(f, delimiter='\t')
-        writer.writerow(['slide'] + SUMMARY_KEYS + (BOUNDARY_SUMMARY_KEYS if args.boundary else []))
-        writer.writerows(lines)
+    _slides.write_table(args.output_csv, header(args.classes, args.boundary), rows)
+    _slides.write_table(args.summary_tsv, ['slide'] + SUMMARY_KEYS + (BOUNDARY_SUMMARY_KEYS if args.boundary else []), lines, delimiter='\t')
     return 0
 
 

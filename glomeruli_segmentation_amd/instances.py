@@ -14,16 +14,13 @@ gs_slide_instances (include/glomseg_instances.h, csrc/instances.hip) labels the 
 csrc/morphometry.hip) reduces the label map to ten exact integer sums and the squared Feret diameter per instance on the GPU, and
 morph_measures derives the float64 columns from those integers on the host.
 """
-import csv
-import glob
 import math
-import os
 import sys
 from argparse import ArgumentParser
 
 import numpy as np
 
-from . import _call, _lib
+from . import _call, _lib, _slides
 
 CLASS_NAMES = ['glomerulus', 'crescent', 'sclerosis', 'mesangium']        # area_stats.py:68
 MAP_SUFFIX = "_pred_classmap.png"                                          # what composite writes
@@ -166,8 +163,7 @@ def instance_rows(result, key, min_area=0, morph=None):
     pixels.  file_name follows merge.crop_name's pattern, built from the box: on the 1/8 map the box is already in the crop
     names' units.  background: box area minus the instance's pixels.  morph: morphometry's or morph_measures' dict, whose
     MORPH_COLUMNS are appended (area in pixels and holes as integers where they are whole)."""
-    def host(v):
-        return np.asarray(v.cpu() if hasattr(v, "cpu") else v)
+    host = _slides.host
     boxes, counts = host(result["boxes"]).astype(np.int64), host(result["counts"]).astype(np.int64)
     rows = []
     for i, ((x0, y0, x1, y1), c) in enumerate(zip(boxes.tolist(), counts.tolist())):
@@ -204,28 +200,17 @@ def main(argv=None, out=sys.stdout):
     if args.mpp is not None and not args.morphometry:
         parser.error("--mpp needs --morphometry")
     import torch
-    from PIL import Image
-    from .composite import relabel
-    if not torch.cuda.is_available():
-        raise RuntimeError("no HIP device: the instances are labelled on the GPU, there is no host path")
-    paths = sorted(glob.glob(os.path.join(args.classmap_dir, "*" + MAP_SUFFIX)))
-    if not paths:
-        raise FileNotFoundError("no *%s under %s" % (MAP_SUFFIX, args.classmap_dir))
+    _slides.require_device("the instances are labelled on the GPU")
+    paths = _slides.map_paths(args.classmap_dir, MAP_SUFFIX)
     rows = []
     with torch.cuda.device(args.gpu_id):
         for path in paths:
-            slide = os.path.basename(path)[:-len(MAP_SUFFIX)]
-            cm = relabel(np.ascontiguousarray(np.asarray(Image.open(path)), dtype=np.uint8))
-            if cm.ndim != 2:
-                raise ValueError("%s is not a single-channel class map" % path)
+            slide, cm = _slides.read_slide(path, MAP_SUFFIX)
             res = label_instances(cm, classes=args.classes, connectivity=args.connectivity, want_labels=args.morphometry)
             morph = morphometry(res, args.connectivity, args.mpp) if args.morphometry else None
             rows += instance_rows(res, slide, args.min_area, morph)
             print("{}: {} instances".format(slide, res["n"]), file=out)
-    with open(args.output_csv, 'w') as f:
-        writer = csv.writer(f)
-        writer.writerow(header(args.classes, args.morphometry, args.mpp))
-        writer.writerows(rows)
+    _slides.write_table(args.output_csv, header(args.classes, args.morphometry, args.mpp), rows)
     return 0
 
 

@@ -18,17 +18,15 @@ the columns).  With --mpp (micrometres per MAP pixel) --depth is in micrometres.
 glomeruli that carry each class at all, globally (_frac >= area_threshold), segmentally (0 < _frac < area_threshold) and along at
 least rim_threshold of the outer perimeter.
 """
-import csv
 import ctypes
-import glob
-import os
 import sys
 from argparse import ArgumentParser
 from fractions import Fraction
 
 import numpy as np
 
-from . import _call, _lib
+from . import _call, _lib, _slides
+from ._slides import host as _host
 from .instances import MAP_SUFFIX, label_instances
 from .outlines import class_names, trace_outlines
 from .split import core_d2_of
@@ -48,12 +46,7 @@ LESION_ENTRIES = {
 
 def load():
     """_lib.load() with LESION_ENTRIES bound; AttributeError where the library does not export them (there is no fallback)"""
-    lib = _lib.load()
-    for name, (res, args) in LESION_ENTRIES.items():
-        fn = getattr(lib, name)
-        if fn.argtypes != args:
-            fn.restype, fn.argtypes = res, args
-    return lib
+    return _call.bound(LESION_ENTRIES)
 
 
 def loop_arcs_workspace_bytes(edges, n_points, n_loops, bits):
@@ -108,10 +101,6 @@ def loop_arcs(traced, mask, bits):
         _lib.check(lib.gs_loop_arcs(mask.data_ptr(), h, w, int(bits), loop_edges.data_ptr(), loop_offsets.data_ptr(), points.data_ptr(),
                                     n_loops, n_points, edges, ws.data_ptr(), ws.numel(), arcs.data_ptr(), _call.stream_ptr(dev)))
     return arcs
-
-
-def _host(v):
-    return np.asarray(v.cpu() if hasattr(v, "cpu") else v)
 
 
 def outer_loops(loop_label, loop_area2, n):
@@ -277,34 +266,21 @@ def main(argv=None, out=sys.stdout):
     except (ValueError, ZeroDivisionError) as e:
         parser.error(str(e))
     import torch
-    from PIL import Image
-    from .composite import relabel
-    if not torch.cuda.is_available():
-        raise RuntimeError("no HIP device: the lesion table is computed on the GPU, there is no host path")
-    paths = sorted(glob.glob(os.path.join(args.classmap_dir, "*" + MAP_SUFFIX)))
-    if not paths:
-        raise FileNotFoundError("no *%s under %s" % (MAP_SUFFIX, args.classmap_dir))
+    _slides.require_device("the lesion table is computed on the GPU")
+    paths = _slides.map_paths(args.classmap_dir, MAP_SUFFIX)
     rows, summaries, lines = [], [], []
     with torch.cuda.device(args.gpu_id):
         for path in paths:
-            slide = os.path.basename(path)[:-len(MAP_SUFFIX)]
-            cm = relabel(np.ascontiguousarray(np.asarray(Image.open(path)), dtype=np.uint8))
-            if cm.ndim != 2:
-                raise ValueError("%s is not a single-channel class map" % path)
+            slide, cm = _slides.read_slide(path, MAP_SUFFIX)
             table = lesion_table(cm, classes=args.classes, connectivity=args.connectivity, depth=depth)
             rows += lesion_rows(table, slide, args.classes, args.min_area)
             summaries.append(slide_summary(table, args.rim_threshold, args.area_threshold, args.min_area))
             lines += summary_rows(summaries[-1], slide, args.classes)
             print("{}: {} instances, {} of at least {} pixels".format(slide, table["n"], summaries[-1]["glomeruli"], args.min_area), file=out)
-    with open(args.output_csv, 'w') as f:
-        writer = csv.writer(f)
-        writer.writerow(header(args.classes))
-        writer.writerows(rows)
+    _slides.write_table(args.output_csv, header(args.classes), rows)
     if args.summary_tsv:
-        with open(args.summary_tsv, 'w') as f:
-            writer = csv.writer(f, delimiter='\t')
-            writer.writerow(SUMMARY_COLUMNS)
-            writer.writerows(lines + summary_rows(add_summaries(summaries, args.classes), "all", args.classes))
+        _slides.write_table(args.summary_tsv, SUMMARY_COLUMNS, lines + summary_rows(add_summaries(summaries, args.classes), "all", args.classes),
+                            delimiter='\t')
     return 0
 
 

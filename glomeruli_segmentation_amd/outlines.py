@@ -14,7 +14,6 @@ One file per <slide>_pred_classmap.png: <slide>_outlines.geojson (a FeatureColle
 outlines on the slide) or <slide>_outlines.json (labelme; outer rings only, labelme has no holes).
 """
 import ctypes
-import glob
 import json
 import os
 import sys
@@ -22,7 +21,8 @@ from argparse import ArgumentParser
 
 import numpy as np
 
-from . import _call, _lib
+from . import _call, _lib, _slides
+from ._slides import host as _host
 from .instances import CLASS_NAMES, MAP_SUFFIX, header, label_instances
 
 TABLES = ("loop_label", "loop_first", "loop_edges", "loop_area2")
@@ -40,12 +40,7 @@ OUTLINE_ENTRIES = {
 
 def load():
     """_lib.load() with OUTLINE_ENTRIES bound; AttributeError where the library does not export them (there is no fallback)"""
-    lib = _lib.load()
-    for name, (res, args) in OUTLINE_ENTRIES.items():
-        fn = getattr(lib, name)
-        if fn.argtypes != args:
-            fn.restype, fn.argtypes = res, args
-    return lib
+    return _call.bound(OUTLINE_ENTRIES)
 
 
 def outlines_workspace_bytes(height, width, edges_cap):
@@ -92,10 +87,6 @@ def trace_outlines(result, connectivity=8, edges_cap=None):
     traced.update(loop_offsets=out["loop_offsets"][:n_loops + 1], points=out["points"][:n_points], edges=edges, n_loops=n_loops,
                   n_points=n_points, calls=calls)
     return traced
-
-
-def _host(v):
-    return np.asarray(v.cpu() if hasattr(v, "cpu") else v)
 
 
 def instance_polygons(traced):
@@ -225,13 +216,8 @@ def build_parser():
 def main(argv=None, out=sys.stdout):
     args = build_parser().parse_args(argv)
     import torch
-    from PIL import Image
-    from .composite import relabel
-    if not torch.cuda.is_available():
-        raise RuntimeError("no HIP device: the outlines are traced on the GPU, there is no host path")
-    paths = sorted(glob.glob(os.path.join(args.classmap_dir, "*" + MAP_SUFFIX)))
-    if not paths:
-        raise FileNotFoundError("no *%s under %s" % (MAP_SUFFIX, args.classmap_dir))
+    _slides.require_device("the outlines are traced on the GPU")
+    paths = _slides.map_paths(args.classmap_dir, MAP_SUFFIX)
     os.makedirs(args.output_dir, exist_ok=True)
     scale = int(args.scale) if float(args.scale).is_integer() else args.scale
     names = class_names(args.classes)
@@ -242,10 +228,7 @@ def main(argv=None, out=sys.stdout):
         return simplified(polys, args.epsilon) if args.epsilon > 0 else polys
     with torch.cuda.device(args.gpu_id):
         for path in paths:
-            slide = os.path.basename(path)[:-len(MAP_SUFFIX)]
-            cm = relabel(np.ascontiguousarray(np.asarray(Image.open(path)), dtype=np.uint8))
-            if cm.ndim != 2:
-                raise ValueError("%s is not a single-channel class map" % path)
+            slide, cm = _slides.read_slide(path, MAP_SUFFIX)
             cm = torch.from_numpy(np.array(cm)).cuda()
             res = label_instances(cm, classes=args.classes, connectivity=args.connectivity, want_labels=True)
             keep = set((np.nonzero(_host(res["counts"]).sum(axis=1) >= args.min_area)[0] + 1).tolist())

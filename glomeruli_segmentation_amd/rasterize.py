@@ -17,7 +17,6 @@ writes and instances reads, so instance_eval --eval_dir runs on a directory that
 exactly.
 """
 import ctypes
-import glob
 import json
 import os
 import sys
@@ -25,7 +24,7 @@ from argparse import ArgumentParser
 
 import numpy as np
 
-from . import _call, _lib
+from . import _call, _lib, _slides
 from .instances import MAP_SUFFIX
 from .outlines import FORMATS, class_names
 
@@ -43,12 +42,7 @@ RASTER_ENTRIES = {
 
 def load():
     """_lib.load() with RASTER_ENTRIES bound; AttributeError where the library does not export them (there is no fallback)"""
-    lib = _lib.load()
-    for name, (res, args) in RASTER_ENTRIES.items():
-        fn = getattr(lib, name)
-        if fn.argtypes != args:
-            fn.restype, fn.argtypes = res, args
-    return lib
+    return _call.bound(RASTER_ENTRIES)
 
 
 def raster_workspace_bytes(height, width, n_points, n_rings, n_features, words_cap):
@@ -89,8 +83,7 @@ def rasterize(rings, ring_feature, n_features, height, width, frac_bits=0, featu
         if len(feature_class) != n_features:
             raise ValueError("feature_class has %d values for %d features" % (len(feature_class), n_features))
     lib = load()
-    if not torch.cuda.is_available():
-        raise RuntimeError("no HIP device: polygons are rasterised on the GPU, there is no host path")
+    _slides.require_device("polygons are rasterised on the GPU")
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     cap = max(4096, height * width // 16) if words_cap is None else int(words_cap)
     n_points, n_rings = len(points), len(feature)
@@ -230,16 +223,13 @@ def main(argv=None, out=sys.stdout):
         parser.error("give either --like_dir or both --height and --width")
     import torch
     from PIL import Image
-    if not torch.cuda.is_available():
-        raise RuntimeError("no HIP device: polygons are rasterised on the GPU, there is no host path")
+    _slides.require_device("polygons are rasterised on the GPU")
     ending = FORMATS[args.format]
-    paths = sorted(glob.glob(os.path.join(args.outlines_dir, "*" + ending)))
-    if not paths:
-        raise FileNotFoundError("no *%s under %s" % (ending, args.outlines_dir))
+    paths = _slides.map_paths(args.outlines_dir, ending)
     os.makedirs(args.output_dir, exist_ok=True)
     with torch.cuda.device(args.gpu_id):
         for path in paths:
-            slide = os.path.basename(path)[:-len(ending)]
+            slide = _slides.slide_name(path, ending)
             with open(path) as f:
                 doc = json.load(f)
             if args.format == "geojson":

@@ -13,8 +13,6 @@ definitions: include/glomseg_split.h; the kernels: csrc/split.hip.
 reads every <slide>_pred_classmap.png of DIR and writes the split map under the same name into DIR2 (never DIR itself).  With
 --mpp (micrometres per MAP pixel) R is in micrometres.  The report has one row per original instance (REPORT_COLUMNS).
 """
-import csv
-import glob
 import math
 import os
 import sys
@@ -22,7 +20,7 @@ from argparse import ArgumentParser
 
 import numpy as np
 
-from . import _call, _lib
+from . import _call, _lib, _slides
 from .instances import MAP_SUFFIX, label_instances
 
 REPORT_COLUMNS = ['slide', 'xmin', 'ymin', 'xmax', 'ymax', 'area', 'inscribed_radius', 'inscribed_x', 'inscribed_y', 'cores', 'parts_after']
@@ -189,8 +187,7 @@ def report_header(mpp=None):
 
 def report_rows(result, slide, after, mpp=None):
     """one row per original instance, in REPORT_COLUMNS' order"""
-    def host(v):
-        return np.asarray(v.cpu() if hasattr(v, "cpu") else v)
+    host = _slides.host
     boxes, area = host(result["boxes"]).astype(np.int64), host(result["counts"]).astype(np.int64).sum(axis=1)
     insc, cores = result["inscribed"], host(result["cores"]).astype(np.int64)
     rows = []
@@ -232,21 +229,14 @@ def main(argv=None, out=sys.stdout):
         parser.error("--core_radius must not be negative")
     import torch
     from PIL import Image
-    from .composite import relabel
-    if not torch.cuda.is_available():
-        raise RuntimeError("no HIP device: the maps are split on the GPU, there is no host path")
-    paths = sorted(glob.glob(os.path.join(args.classmap_dir, "*" + MAP_SUFFIX)))
-    if not paths:
-        raise FileNotFoundError("no *%s under %s" % (MAP_SUFFIX, args.classmap_dir))
+    _slides.require_device("the maps are split on the GPU")
+    paths = _slides.map_paths(args.classmap_dir, MAP_SUFFIX)
     radius = args.core_radius / args.mpp if args.mpp is not None else args.core_radius
     os.makedirs(args.output_dir, exist_ok=True)
     rows = []
     with torch.cuda.device(args.gpu_id):
         for path in paths:
-            slide = os.path.basename(path)[:-len(MAP_SUFFIX)]
-            cm = relabel(np.ascontiguousarray(np.asarray(Image.open(path)), dtype=np.uint8))
-            if cm.ndim != 2:
-                raise ValueError("%s is not a single-channel class map" % path)
+            slide, cm = _slides.read_slide(path, MAP_SUFFIX)
             res = split_touching(cm, radius, classes=args.classes, connectivity=args.connectivity, min_core_area=args.min_core_area,
                                  max_cores=args.max_cores)
             after = parts_after(res, args.classes, args.connectivity)
@@ -255,10 +245,7 @@ def main(argv=None, out=sys.stdout):
             print("{}: {} instances, {} cores, {} cut pixels, {} instances after".format(slide, res["n"], res["n_cores"], res["cut_pixels"],
                                                                                          int(after.sum())), file=out)
     if args.report_csv:
-        with open(args.report_csv, 'w') as f:
-            writer = csv.writer(f)
-            writer.writerow(report_header(args.mpp))
-            writer.writerows(rows)
+        _slides.write_table(args.report_csv, report_header(args.mpp), rows)
     return 0
 
 

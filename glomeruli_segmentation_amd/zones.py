@@ -16,9 +16,7 @@ reads every <slide>_pred_classmap.png of DIR and writes one row per instance (CO
 and G are in micrometres and the lengths and areas get the suffixes _um / _um2.  --neighbours_csv: one row per pair of adjacent
 zones (NEIGHBOUR_COLUMNS); --zones_dir: <slide>_zones.png, a 16-bit grey PNG of the zone ids (never into DIR itself).
 """
-import csv
 import ctypes
-import glob
 import math
 import os
 import sys
@@ -26,7 +24,7 @@ from argparse import ArgumentParser
 
 import numpy as np
 
-from . import _call, _lib
+from . import _call, _lib, _slides
 from .instance_eval import workspace_bytes as overlaps_workspace_bytes
 from .instances import MAP_SUFFIX, label_instances
 from .split import core_d2_of, label_peaks
@@ -50,12 +48,7 @@ ZONE_ENTRIES = {
 
 def load():
     """_lib.load() with ZONE_ENTRIES bound; AttributeError where the library does not export them (there is no fallback)"""
-    lib = _lib.load()
-    for name, (res, args) in ZONE_ENTRIES.items():
-        fn = getattr(lib, name)
-        if fn.argtypes != args:
-            fn.restype, fn.argtypes = res, args
-    return lib
+    return _call.bound(ZONE_ENTRIES)
 
 
 def zones_workspace_bytes(height, width):
@@ -223,8 +216,7 @@ def header(mpp=None):
 def table_rows(result, slide, mpp=None):
     """one row per instance, in COLUMNS' order, from analyse's dict (tensors or numpy arrays); the gap and the pixel it is measured
     from are empty where the instance has no neighbour within max_gap"""
-    def host(v):
-        return np.asarray(v.cpu() if hasattr(v, "cpu") else v)
+    host = _slides.host
     n = int(result["n"])
     boxes, area = host(result["boxes"]).astype(np.int64), host(result["counts"]).astype(np.int64).sum(axis=1)
     territory, nn_id = host(result["territory"]).astype(np.int64), host(result["nn_id"]).astype(np.int64)
@@ -273,12 +265,8 @@ def main(argv=None, out=sys.stdout):
         parser.error("--radius and --max_gap must not be negative")
     import torch
     from PIL import Image
-    from .composite import relabel
-    if not torch.cuda.is_available():
-        raise RuntimeError("no HIP device: the zones are computed on the GPU, there is no host path")
-    paths = sorted(glob.glob(os.path.join(args.classmap_dir, "*" + MAP_SUFFIX)))
-    if not paths:
-        raise FileNotFoundError("no *%s under %s" % (MAP_SUFFIX, args.classmap_dir))
+    _slides.require_device("the zones are computed on the GPU")
+    paths = _slides.map_paths(args.classmap_dir, MAP_SUFFIX)
     unit = 1.0 if args.mpp is None else args.mpp
     radius = args.radius / unit
     max_gap = 2 * radius if args.max_gap is None else args.max_gap / unit
@@ -287,10 +275,7 @@ def main(argv=None, out=sys.stdout):
     rows, pair_rows = [], []
     with torch.cuda.device(args.gpu_id):
         for path in paths:
-            slide = os.path.basename(path)[:-len(MAP_SUFFIX)]
-            cm = relabel(np.ascontiguousarray(np.asarray(Image.open(path)), dtype=np.uint8))
-            if cm.ndim != 2:
-                raise ValueError("%s is not a single-channel class map" % path)
+            slide, cm = _slides.read_slide(path, MAP_SUFFIX)
             res = analyse(cm, radius, max_gap, classes=args.classes, connectivity=args.connectivity)
             rows += table_rows(res, slide, args.mpp)
             pair_rows += neighbour_rows(res, slide)
@@ -301,15 +286,9 @@ def main(argv=None, out=sys.stdout):
                     print("{}: {} instances do not fit a 16-bit PNG: no zone map written".format(slide, res["n"]), file=out)
                 else:
                     Image.fromarray(res["zone"].cpu().numpy().astype(np.uint16)).save(os.path.join(args.zones_dir, slide + ZONES_SUFFIX))
-    with open(args.output_csv, 'w') as f:
-        writer = csv.writer(f)
-        writer.writerow(header(args.mpp))
-        writer.writerows(rows)
+    _slides.write_table(args.output_csv, header(args.mpp), rows)
     if args.neighbours_csv:
-        with open(args.neighbours_csv, 'w') as f:
-            writer = csv.writer(f)
-            writer.writerow(NEIGHBOUR_COLUMNS)
-            writer.writerows(pair_rows)
+        _slides.write_table(args.neighbours_csv, NEIGHBOUR_COLUMNS, pair_rows)
     return 0
 
 

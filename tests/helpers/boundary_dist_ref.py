@@ -14,14 +14,7 @@ from scipy import ndimage
 
 from helpers import instance_maps as maps
 from helpers import instance_match_ref as match_ref
-
-
-def boundary_mask(labels, n):
-    """pixels with 1 <= label <= n that have an edge neighbour outside the map or with another label"""
-    lab = np.asarray(labels, dtype=np.int64)
-    pad = np.pad(lab, 1, constant_values=-1)                # no valid id: the map's edge counts
-    differs = (pad[:-2, 1:-1] != lab) | (pad[2:, 1:-1] != lab) | (pad[1:-1, :-2] != lab) | (pad[1:-1, 2:] != lab)
-    return (lab >= 1) & (lab <= n) & differs
+from helpers.instance_maps import boundary_mask
 
 
 def pairs_of(match_gt, match_pred):

@@ -76,6 +76,15 @@ def make_map(name, classes):
     return m
 
 
+def boundary_mask(labels, n):
+    """the numpy counterpart of csrc/boundary_links.h's boundary_pixel: a label in 1..n and a 4-neighbour that carries another
+    value or lies outside the map.  The pad is -1, no valid label, so the map's edge counts as another value."""
+    lab = np.asarray(labels).astype(np.int64)
+    pad = np.pad(lab, 1, constant_values=-1)
+    other = (pad[:-2, 1:-1] != lab) | (pad[2:, 1:-1] != lab) | (pad[1:-1, :-2] != lab) | (pad[1:-1, 2:] != lab)
+    return (lab >= 1) & (lab <= n) & other
+
+
 @functools.lru_cache(maxsize=None)
 def reference(name, classes, connectivity):
     return label_instances_ref(make_map(name, classes), classes, connectivity)

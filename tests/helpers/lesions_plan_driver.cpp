@@ -4,65 +4,25 @@
 // cover their items, the parts of the workspace are aligned, in order, large enough and inside the figure, the figure never shrinks
 // when an argument grows, nothing overflows at the limits (2^31 - 1 edges and points, 31 bits), and refusals leave a text and a
 // zero figure.  Built with g++ only: no device code in here.
-#include <climits>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <initializer_list>
-
 #include "lesions_plan.h"
-
-namespace gs {
-static char g_err[1024];
-void set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-}  // namespace gs
-using namespace gs;
+#include "plan_driver.h"
 
 static const int kSizes[] = {1, 2, 15, 16, 17, 63, 64, 65, 513, 5000, 32767, 32768};
 static const long long kCounts[] = {0, 4, 5, 255, 256, 257, 1024, 300000, 24200000, (long long)INT_MAX - 1, (long long)INT_MAX};
-
-static int fail(const char *what, long long a, long long b)
-{
-    std::fprintf(stderr, "FAILED: %s (%lld, %lld): %s\n", what, a, b, g_err);
-    return 1;
-}
-
-static bool covers(long long blocks, long long per_block, long long items)
-{
-    return blocks * per_block >= items && (blocks - 1) * per_block < items;
-}
-
-template <int N>
-static bool laid_out(const size_t (&offs)[N], const size_t (&need)[N - 1])
-{
-    if (offs[0] != 0)
-        return false;
-    for (int k = 0; k + 1 < N; ++k)
-        if (offs[k] % kPlanAlign != 0 || offs[k + 1] < offs[k] + need[k] || offs[k + 1] >= offs[k] + need[k] + kPlanAlign)
-            return false;
-    return true;
-}
 
 static bool rim_refused(int n, int classes, int h, int w, long long d2, gs_status want, const char *word)
 {
     RimPlan p;
     g_err[0] = 0;
     const gs_status st = plan_rim(n, classes, h, w, d2, p);
-    return st == want && std::strstr(g_err, word) && std::strstr(g_err, "gs_rim_classes: ") && p.blocks == 0 && p.lds_bytes == 0;
+    return refused(st, want, word, "gs_rim_classes: ", (size_t)(p.blocks | p.lds_bytes));     // both figures zero
 }
 
 static bool arcs_refused(long long edges, long long points, long long loops, int bits, const char *word)
 {
     ArcsPlan p;
     g_err[0] = 0;
-    const gs_status st = plan_arcs(edges, points, loops, bits, p);
-    return st == GS_ERR_INVALID && std::strstr(g_err, word) && std::strstr(g_err, "gs_loop_arcs: ") && p.bytes == 0;
+    return refused(plan_arcs(edges, points, loops, bits, p), GS_ERR_INVALID, word, "gs_loop_arcs: ", p);
 }
 
 int main()

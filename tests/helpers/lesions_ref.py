@@ -11,18 +11,11 @@ from scipy import ndimage
 
 from helpers import morphometry_ref as mref
 from helpers import outlines_ref as oref
+from helpers.instance_maps import boundary_mask
 from helpers.instances_ref import label_instances_ref
 
 CLASSES = 5
 HIGH = (None, 31, 32, 255)               # None: the value `classes` itself; all of them must set no bit
-
-
-def boundary_mask(labels, n):
-    """a pixel of an instance with a 4-neighbour that carries another value or lies outside the map"""
-    lab = np.asarray(labels).astype(np.int64)
-    pad = np.pad(lab, 1, constant_values=np.iinfo(np.int64).min)
-    other = (pad[:-2, 1:-1] != lab) | (pad[2:, 1:-1] != lab) | (pad[1:-1, :-2] != lab) | (pad[1:-1, 2:] != lab)
-    return (lab >= 1) & (lab <= n) & other
 
 
 def rim_direct(labels, class_map, n, classes, max_d2):

@@ -3,41 +3,14 @@
 // (height + 1) x (width + 1) windows in tiles of 256 x kMorphRows, the stride grid is 1..kMorphMaxGrid, the parts of the workspace are aligned, in order, large
 // enough and inside the figure, the figure never shrinks with rows_cap and does not depend on the map, refusals leave a text and
 // a zero figure, and the tiles and tasks of an instance cover its candidates.  Built with g++ only: no HIP in here.
-#include <climits>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-
 #include "morphometry_plan.h"
-
-namespace gs {
-static char g_err[1024];
-void set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-}  // namespace gs
-using namespace gs;
+#include "plan_driver.h"
 
 static const int kSizes[] = {1, 2, 3, 63, 64, 65, 255, 256, 257, 300, 517, 5000, 32767, 32768, 32769, 46341, 65536, 1 << 20, INT_MAX};
 static const long long kCaps[] = {0, 1, 2, 5, 6, 255, 256, 1023, 1024, 1025, 28700, 1 << 20, (1ll << 31) - 1, 1ll << 31, 1ll << 40,
                                   kMorphMaxRows - 1, kMorphMaxRows, kMorphMaxRows + 1, LLONG_MAX};
 
-static int fail(const char *what, long long a, long long b, long long c = 0)
-{
-    std::fprintf(stderr, "FAILED: %s (%lld, %lld, %lld): %s\n", what, a, b, c, g_err);
-    return 1;
-}
-
-static bool refused(gs_status got, gs_status want, const char *word, const MorphometryPlan &p)
-{
-    const bool ok = got == want && std::strstr(g_err, word) && std::strstr(g_err, "gs_instance_morphometry: ") && p.bytes == 0;
-    g_err[0] = 0;
-    return ok;
-}
+static const char kEntry[] = "gs_instance_morphometry: ";
 
 int main()
 {
@@ -50,7 +23,7 @@ int main()
                 g_err[0] = 0;
                 const gs_status st = plan_morphometry(h, w, cap, p);
                 if (h > kMorphMaxSide || w > kMorphMaxSide) {        // the side limit comes first, whatever the number of pixels
-                    if (!refused(st, GS_ERR_UNSUPPORTED, "32768", p))
+                    if (!refused(st, GS_ERR_UNSUPPORTED, "32768", kEntry, p))
                         return fail("a map beyond 32768 pixels a side is not refused", h, w, cap);
                     ++refusals;
                     continue;
@@ -82,21 +55,21 @@ int main()
     const int bad[] = {0, -1, INT_MIN};
     for (int b : bad) {
         MorphometryPlan p;
-        if (!refused(plan_morphometry(b, 10, 10, p), GS_ERR_INVALID, "positive", p) ||
-            !refused(plan_morphometry(10, b, 10, p), GS_ERR_INVALID, "positive", p))
+        if (!refused(plan_morphometry(b, 10, 10, p), GS_ERR_INVALID, "positive", kEntry, p) ||
+            !refused(plan_morphometry(10, b, 10, p), GS_ERR_INVALID, "positive", kEntry, p))
             return fail("a non-positive side is not refused", b, b);
         ++refusals;
     }
     const long long bad_caps[] = {-1, -2, LLONG_MIN};
     for (long long c : bad_caps) {
         MorphometryPlan p;
-        if (!refused(plan_morphometry(10, 10, c, p), GS_ERR_INVALID, "rows_cap", p))
+        if (!refused(plan_morphometry(10, 10, c, p), GS_ERR_INVALID, "rows_cap", kEntry, p))
             return fail("a negative rows_cap is not refused", c, 0);
         ++refusals;
     }
     // 46341^2 > INT_MAX pixels lies behind the side limit: both refusals are GS_ERR_UNSUPPORTED
     MorphometryPlan p;
-    if (!refused(plan_morphometry(46341, 46341, 1, p), GS_ERR_UNSUPPORTED, "32768", p))
+    if (!refused(plan_morphometry(46341, 46341, 1, p), GS_ERR_UNSUPPORTED, "32768", kEntry, p))
         return fail("46341 x 46341", 46341, 46341);
     // the diameter: the largest feret2 of the largest map fits an int32 and packs into x | y << 16; one side longer does not
     const long long far = 2ll * (kMorphMaxSide - 1) * (kMorphMaxSide - 1), beyond = 2ll * kMorphMaxSide * kMorphMaxSide;

@@ -3,42 +3,14 @@
 // and the edge grid the cap in workgroups of kOutThreads, 2^rounds covers the cap and 2^(rounds - 1) does not, the parts of the
 // workspace are aligned, in order, large enough and inside the figure, the figure never shrinks with the cap nor with the map,
 // and refusals leave a text and a zero figure.  Built with g++ only: no HIP in here.
-#include <climits>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <initializer_list>
-
 #include "outlines_plan.h"
-
-namespace gs {
-static char g_err[1024];
-void set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-}  // namespace gs
-using namespace gs;
+#include "plan_driver.h"
 
 static const int kSizes[] = {1, 2, 3, 63, 64, 65, 255, 256, 257, 300, 517, 5000, 32768, 46340, 46341, 65536, 1 << 20, INT_MAX};
 static const long long kCaps[] = {0, 1, 2, 3, 4, 5, 255, 256, 257, 258, 1023, 1024, 1025, 28700, 1 << 20, (1ll << 30) - 1, 1ll << 30,
                                   (1ll << 30) + 1, (1ll << 31) - 2, (1ll << 31) - 1};
 
-static int fail(const char *what, long long a, long long b, long long c = 0)
-{
-    std::fprintf(stderr, "FAILED: %s (%lld, %lld, %lld): %s\n", what, a, b, c, g_err);
-    return 1;
-}
-
-static bool refused(gs_status got, gs_status want, const char *word, const OutlinesPlan &p)
-{
-    const bool ok = got == want && std::strstr(g_err, word) && std::strstr(g_err, "gs_instance_outlines: ") && p.bytes == 0;
-    g_err[0] = 0;
-    return ok;
-}
+static const char kEntry[] = "gs_instance_outlines: ";
 
 int main()
 {
@@ -54,7 +26,7 @@ int main()
                 const gs_status st = plan_outlines(h, w, cap, p);
                 const long long pixels = (long long)h * w;
                 if (pixels > INT_MAX) {
-                    if (!refused(st, GS_ERR_UNSUPPORTED, "pixels", p))
+                    if (!refused(st, GS_ERR_UNSUPPORTED, "pixels", kEntry, p))
                         return fail("a map of more than 2^31 - 1 pixels is not refused", h, w, cap);
                     ++refusals;
                     continue;
@@ -102,15 +74,15 @@ int main()
     const int bad[] = {0, -1, INT_MIN};
     for (int b : bad) {
         OutlinesPlan p;
-        if (!refused(plan_outlines(b, 10, 10, p), GS_ERR_INVALID, "positive", p) ||
-            !refused(plan_outlines(10, b, 10, p), GS_ERR_INVALID, "positive", p))
+        if (!refused(plan_outlines(b, 10, 10, p), GS_ERR_INVALID, "positive", kEntry, p) ||
+            !refused(plan_outlines(10, b, 10, p), GS_ERR_INVALID, "positive", kEntry, p))
             return fail("a non-positive side is not refused", b, b);
         ++refusals;
     }
     const long long bad_caps[] = {-1, -2, LLONG_MIN, 1ll << 31, 1ll << 40, LLONG_MAX};
     for (long long c : bad_caps) {
         OutlinesPlan p;
-        if (!refused(plan_outlines(10, 10, c, p), GS_ERR_INVALID, "edges_cap", p))
+        if (!refused(plan_outlines(10, 10, c, p), GS_ERR_INVALID, "edges_cap", kEntry, p))
             return fail("an edges_cap out of range is not refused", c, 0);
         ++refusals;
     }

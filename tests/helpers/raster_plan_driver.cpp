@@ -4,41 +4,13 @@
 // aligned, in order, large enough and inside the figure, the figure never shrinks with any argument, and refusals leave a text
 // and a zero figure.  The two integer functions of the rule are compared with a plain search, and the box words with the
 // header's formula.  Built with g++ only: no device code in here.
-#include <climits>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <initializer_list>
-
 #include "raster_plan.h"
-
-namespace gs {
-static char g_err[1024];
-void set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-}  // namespace gs
-using namespace gs;
+#include "plan_driver.h"
 
 static const int kSizes[] = {1, 2, 63, 64, 65, 255, 256, 257, 517, 5000, 46340, 46341, 1 << 20, INT_MAX};
 static const long long kCounts[] = {0, 1, 2, 255, 256, 257, 1023, 1024, 1025, 28700, 1 << 20, (1ll << 31) - 2, (1ll << 31) - 1};
 
-static int fail(const char *what, long long a, long long b, long long c = 0)
-{
-    std::fprintf(stderr, "FAILED: %s (%lld, %lld, %lld): %s\n", what, a, b, c, g_err);
-    return 1;
-}
-
-static bool refused(gs_status got, gs_status want, const char *word, const RasterPlan &p)
-{
-    const bool ok = got == want && std::strstr(g_err, word) && std::strstr(g_err, "gs_polygon_raster: ") && p.bytes == 0;
-    g_err[0] = 0;
-    return ok;
-}
+static const char kEntry[] = "gs_polygon_raster: ";
 
 static bool grid_covers(int blocks, long long items, int least)
 {
@@ -60,7 +32,7 @@ int main()
                     const long long points = n, rings = n / 3, features = n / 2;
                     const gs_status st = plan_raster(h, w, points, rings, features, cap, p);
                     if (pixels > INT_MAX) {
-                        if (!refused(st, GS_ERR_UNSUPPORTED, "pixels", p))
+                        if (!refused(st, GS_ERR_UNSUPPORTED, "pixels", kEntry, p))
                             return fail("a map of more than 2^31 - 1 pixels is not refused", h, w, cap);
                         ++refusals;
                         continue;
@@ -98,18 +70,18 @@ int main()
     const int bad[] = {0, -1, INT_MIN};
     for (int b : bad) {
         RasterPlan p;
-        if (!refused(plan_raster(b, 10, 1, 1, 1, 10, p), GS_ERR_INVALID, "positive", p) ||
-            !refused(plan_raster(10, b, 1, 1, 1, 10, p), GS_ERR_INVALID, "positive", p))
+        if (!refused(plan_raster(b, 10, 1, 1, 1, 10, p), GS_ERR_INVALID, "positive", kEntry, p) ||
+            !refused(plan_raster(10, b, 1, 1, 1, 10, p), GS_ERR_INVALID, "positive", kEntry, p))
             return fail("a non-positive side is not refused", b, b);
         ++refusals;
     }
     const long long bad_counts[] = {-1, -2, LLONG_MIN, 1ll << 31, 1ll << 40, LLONG_MAX};
     for (long long c : bad_counts) {
         RasterPlan p;
-        if (!refused(plan_raster(10, 10, c, 1, 1, 10, p), GS_ERR_INVALID, "n_points", p) ||
-            !refused(plan_raster(10, 10, 1, c, 1, 10, p), GS_ERR_INVALID, "n_rings", p) ||
-            !refused(plan_raster(10, 10, 1, 1, c, 10, p), GS_ERR_INVALID, "n_features", p) ||
-            !refused(plan_raster(10, 10, 1, 1, 1, c, p), GS_ERR_INVALID, "words_cap", p))
+        if (!refused(plan_raster(10, 10, c, 1, 1, 10, p), GS_ERR_INVALID, "n_points", kEntry, p) ||
+            !refused(plan_raster(10, 10, 1, c, 1, 10, p), GS_ERR_INVALID, "n_rings", kEntry, p) ||
+            !refused(plan_raster(10, 10, 1, 1, c, 10, p), GS_ERR_INVALID, "n_features", kEntry, p) ||
+            !refused(plan_raster(10, 10, 1, 1, 1, c, p), GS_ERR_INVALID, "words_cap", kEntry, p))
             return fail("a count out of range is not refused", c, 0);
         refusals += 4;
     }

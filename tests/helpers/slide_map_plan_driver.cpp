@@ -3,55 +3,14 @@
 // pixels, a single row and column of the largest side, the largest maps taken, one pixel beyond each limit -- swept through every
 // plan, and what the launchers rely on checked: grids and tiles cover the map, the parts of a workspace are aligned, in order,
 // large enough and inside the figure, refusals leave a text and a zero figure.  Built with g++ only: no HIP in here.
-#include <climits>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-
 #include "boundary_dist_plan.h"
 #include "instance_match_plan.h"
 #include "instance_plan.h"
-
-namespace gs {
-static char g_err[1024];
-void set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-}  // namespace gs
-using namespace gs;
+#include "plan_driver.h"
 
 static const int kSizes[] = {1, 2, 3, 63, 64, 65, 127, 128, 129, 255, 256, 257, 300, 517, 5000, 32767, 32768, 32769, 46340, 46341, 65535, 65536,
                              1 << 20, INT_MAX / 2, INT_MAX - 1, INT_MAX};
 static const int kBad[] = {0, -1, INT_MIN};
-
-static int fail(const char *what, int a, int b, int c = 0)
-{
-    std::fprintf(stderr, "FAILED: %s (%d, %d, %d): %s\n", what, a, b, c, g_err);
-    return 1;
-}
-
-// offs: n + 1 offsets, the last one the size of the whole; need: the bytes of each of the n parts
-static bool laid_out(const size_t *offs, const size_t *need, int n)
-{
-    for (int k = 0; k < n; ++k)
-        if (offs[k] % kPlanAlign != 0 || offs[k + 1] < offs[k] + need[k] || offs[k + 1] >= offs[k] + need[k] + kPlanAlign)
-            return false;
-    return offs[0] == 0;
-}
-
-// covers(n, unit, total): n units of `unit` cover `total`, n - 1 do not
-static bool covers(long long n, long long unit, long long total) { return n * unit >= total && (n - 1) * unit < total; }
-
-static bool refused(gs_status got, gs_status want, const char *word, size_t bytes = 0)
-{
-    const bool ok = got == want && std::strstr(g_err, word) && bytes == 0;
-    g_err[0] = 0;
-    return ok;
-}
 
 // ---- slide_map_plan.h itself
 static int shared_checks()
@@ -90,7 +49,7 @@ static int shared_checks()
     for (int k = 0; k < 10; ++k)
         offs[k] = ws.take(parts[k]);
     offs[10] = ws.off;
-    if (!laid_out(offs, parts, 10) || offs[1] != 0 || offs[2] != 256 || offs[5] - offs[4] != 512 || plan_align(0) != 0 || plan_align(257) != 512)
+    if (!laid_out(offs, parts) || offs[1] != 0 || offs[2] != 256 || offs[5] - offs[4] != 512 || plan_align(0) != 0 || plan_align(257) != 512)
         return fail("PlanCursor", 0, 0);
     std::printf("shared checks ok: %d sizes\n", n);
     return 0;
@@ -108,7 +67,7 @@ static int instance_plans()
                 g_err[0] = 0;
                 const gs_status st = plan_instances(h, w, 5, cap, p);
                 if ((long long)h * w > (long long)INT_MAX) {
-                    if (!refused(st, GS_ERR_UNSUPPORTED, "2^31 - 1", p.bytes))
+                    if (!refused(st, GS_ERR_UNSUPPORTED, "2^31 - 1", "gs_slide_instances: ", p))
                         return fail("a map beyond 2^31 - 1 pixels is not refused", h, w, cap);
                     ++refusals;
                     continue;
@@ -120,7 +79,7 @@ static int instance_plans()
                     !covers(p.n_blocks, kInstThreads, p.n_pixels))
                     return fail("tiles and blocks", h, w, cap);
                 const size_t offs[] = {p.parent_off, p.block_off, p.bytes}, need[] = {(size_t)p.n_pixels * 4, (size_t)p.n_blocks * 4};
-                if (!laid_out(offs, need, 2))
+                if (!laid_out(offs, need))
                     return fail("workspace layout", h, w, cap);
             }
     InstancePlan p;
@@ -153,7 +112,7 @@ static int match_plans()
                 g_err[0] = 0;
                 const gs_status st = plan_instance_match(h, w, cap, p);
                 if ((long long)h * w > (long long)INT_MAX) {
-                    if (!refused(st, GS_ERR_UNSUPPORTED, "2^31 - 1", p.bytes))
+                    if (!refused(st, GS_ERR_UNSUPPORTED, "2^31 - 1", "gs_instance_overlaps: ", p))
                         return fail("a map beyond 2^31 - 1 pixels is not refused", h, w, cap);
                     ++refusals;
                     continue;
@@ -174,7 +133,7 @@ static int match_plans()
                     return fail("n_blocks", h, w, cap);
                 const size_t offs[] = {p.state_off, p.key_off, p.val_off, p.block_off, p.dense_key_off, p.dense_slot_off, p.bytes};
                 const size_t need[] = {16, p.slots * 8, p.slots * 16, (size_t)p.n_blocks * 4, (size_t)p.cap * 8, (size_t)p.cap * 4};
-                if (!laid_out(offs, need, 6))
+                if (!laid_out(offs, need))
                     return fail("workspace layout", h, w, cap);
             }
     for (int b : kBad) {
@@ -218,7 +177,7 @@ static int boundary_plans()
             g_err[0] = 0;
             const gs_status st = plan_boundary_dist(h, w, p);
             if (h > 32768 || w > 32768) {             // the side limit comes first, whatever the number of pixels
-                if (!refused(st, GS_ERR_UNSUPPORTED, "32768", p.bytes))
+                if (!refused(st, GS_ERR_UNSUPPORTED, "32768", "gs_instance_boundary_dist: ", p))
                     return fail("a map beyond 32768 pixels a side is not refused", h, w);
                 ++refusals;
                 continue;
@@ -230,7 +189,7 @@ static int boundary_plans()
                 return fail("n_pixels and grids", h, w);
             const size_t offs[] = {p.left_gt_off, p.right_gt_off, p.left_pred_off, p.right_pred_off, p.bytes};
             const size_t table = (size_t)p.n_pixels * 2, need[] = {table, table, table, table};
-            if (!laid_out(offs, need, 4))
+            if (!laid_out(offs, need))
                 return fail("workspace layout", h, w);
             if (p.bytes > largest)
                 largest = p.bytes;

@@ -3,52 +3,12 @@
 // and column tiles cover the map, the grids are positive and within their limits, the row pass's LDS holds the row or is not used,
 // the parts of every workspace are aligned, in order, large enough and inside the figure, no figure shrinks when an argument
 // grows, and refusals leave a text and a zero figure.  Built with g++ only: no HIP in here.
-#include <climits>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-
 #include "split_plan.h"
-
-namespace gs {
-static char g_err[1024];
-void set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-}  // namespace gs
-using namespace gs;
+#include "plan_driver.h"
 
 static const int kSizes[] = {1, 2, 3, 31, 32, 33, 63, 64, 65, 255, 256, 257, 300, 517, 5000, 16383, 16384, 16385, 32767, 32768, 32769, 46341,
                              65536, 1 << 20, INT_MAX};
 static const int kCounts[] = {0, 1, 2, 63, 64, 65, 255, 256, 257, 4096, 262143, 262144, 262145, 1 << 24, INT_MAX - 1, INT_MAX};
-
-static int fail(const char *what, long long a, long long b, long long c = 0, long long d = 0)
-{
-    std::fprintf(stderr, "FAILED: %s (%lld, %lld, %lld, %lld): %s\n", what, a, b, c, d, g_err);
-    return 1;
-}
-
-static bool refused(gs_status got, gs_status want, const char *word, const char *entry, size_t bytes)
-{
-    const bool ok = got == want && std::strstr(g_err, word) && std::strstr(g_err, entry) == g_err && bytes == 0;
-    g_err[0] = 0;
-    return ok;
-}
-
-// parts one behind the other: aligned, large enough, less than one alignment of slack, the last one ending at `bytes`
-static bool layout_ok(const size_t *offs, const size_t *need, int parts)
-{
-    if (offs[0] != 0)
-        return false;
-    for (int k = 0; k < parts; ++k)
-        if (offs[k] % kPlanAlign != 0 || offs[k + 1] < offs[k] + need[k] || offs[k + 1] >= offs[k] + need[k] + kPlanAlign)
-            return false;
-    return true;
-}
 
 int main()
 {
@@ -62,9 +22,9 @@ int main()
             const gs_status st = plan_edt(h, w, p);
             const bool side = h > kSplitMaxSide || w > kSplitMaxSide, pixels = (long long)h * w > (long long)INT_MAX;
             if (side || pixels) {                  // the side limit comes first
-                if (!refused(st, GS_ERR_UNSUPPORTED, side ? "32768" : "2^31", "gs_foreground_edt: ", p.bytes))
+                if (!refused(st, GS_ERR_UNSUPPORTED, side ? "32768" : "2^31", "gs_foreground_edt: ", p))
                     return fail("a map beyond the limits is not refused", h, w);
-                if (!refused(plan_split(h, w, 1, 1, q), GS_ERR_UNSUPPORTED, side ? "32768" : "2^31", "gs_split_cut: ", q.bytes))
+                if (!refused(plan_split(h, w, 1, 1, q), GS_ERR_UNSUPPORTED, side ? "32768" : "2^31", "gs_split_cut: ", q))
                     return fail("a map beyond the limits is not refused by the cut", h, w);
                 ++refusals;
                 continue;
@@ -81,7 +41,7 @@ int main()
             const size_t table = (size_t)p.bands * (size_t)w * 2;
             const size_t offs[] = {p.g_off, p.top_off, p.bot_off, p.down_off, p.up_off, p.bytes};
             const size_t need[] = {(size_t)h * (size_t)w * 2, table, table, table, table};
-            if (!layout_ok(offs, need, 5))
+            if (!laid_out(offs, need))
                 return fail("workspace layout of the distance map", h, w);
             // the largest distances fit: a column distance 16 bits, a carry 16 bits, a squared distance an int32
             if ((h + 1) / 2 > 16384 || h > 65535)
@@ -107,7 +67,7 @@ int main()
                     if (n > 0 || c > 0) {
                         const size_t o[] = {q.off_off, q.cursor_off, q.owner_off, q.list_off, q.bytes};
                         const size_t nd[] = {(size_t)n * 4, (size_t)n * 4, (size_t)c * 4, (size_t)c * sizeof(SplitCore)};
-                        if (!layout_ok(o, nd, 4))
+                        if (!laid_out(o, nd))
                             return fail("workspace layout of the cut", h, w, n, c);
                     }
                     if (q.bytes < kPlanAlign || q.bytes < before_c)
@@ -142,10 +102,10 @@ int main()
     for (int b : bad) {
         EdtPlan p;
         SplitPlan q;
-        if (!refused(plan_edt(b, 10, p), GS_ERR_INVALID, "positive", "gs_foreground_edt: ", p.bytes) ||
-            !refused(plan_edt(10, b, p), GS_ERR_INVALID, "positive", "gs_foreground_edt: ", p.bytes) ||
-            !refused(plan_split(b, 10, 1, 1, q), GS_ERR_INVALID, "positive", "gs_split_cut: ", q.bytes) ||
-            !refused(plan_split(10, b, 1, 1, q), GS_ERR_INVALID, "positive", "gs_split_cut: ", q.bytes))
+        if (!refused(plan_edt(b, 10, p), GS_ERR_INVALID, "positive", "gs_foreground_edt: ", p) ||
+            !refused(plan_edt(10, b, p), GS_ERR_INVALID, "positive", "gs_foreground_edt: ", p) ||
+            !refused(plan_split(b, 10, 1, 1, q), GS_ERR_INVALID, "positive", "gs_split_cut: ", q) ||
+            !refused(plan_split(10, b, 1, 1, q), GS_ERR_INVALID, "positive", "gs_split_cut: ", q))
             return fail("a non-positive side is not refused", b, b);
         refusals += 4;
     }
@@ -153,9 +113,9 @@ int main()
     for (int v : negative) {
         PeaksPlan p;
         SplitPlan q;
-        if (!refused(plan_peaks(v, p), GS_ERR_INVALID, "negative", "gs_label_peaks: ", p.bytes) ||
-            !refused(plan_split(10, 10, v, 1, q), GS_ERR_INVALID, "n must", "gs_split_cut: ", q.bytes) ||
-            !refused(plan_split(10, 10, 1, v, q), GS_ERR_INVALID, "c must", "gs_split_cut: ", q.bytes))
+        if (!refused(plan_peaks(v, p), GS_ERR_INVALID, "negative", "gs_label_peaks: ", p) ||
+            !refused(plan_split(10, 10, v, 1, q), GS_ERR_INVALID, "n must", "gs_split_cut: ", q) ||
+            !refused(plan_split(10, 10, 1, v, q), GS_ERR_INVALID, "c must", "gs_split_cut: ", q))
             return fail("a negative count is not refused", v, 0);
         refusals += 3;
     }

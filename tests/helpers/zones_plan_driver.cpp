@@ -4,57 +4,17 @@
 // beyond, the parts of the workspace are aligned, in order, large enough and inside the figure, the figure never shrinks when a
 // side grows, and refusals leave a text and a zero figure.  zone_isqrt is compared with a plain search and the cap check with its
 // range.  Built with g++ only: no device code in here.
-#include <climits>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <initializer_list>
-
 #include "zones_plan.h"
-
-namespace gs {
-static char g_err[1024];
-void set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-}  // namespace gs
-using namespace gs;
+#include "plan_driver.h"
 
 static const int kSizes[] = {1, 2, 31, 32, 33, 63, 64, 65, 255, 256, 257, 513, 5000, 16383, 16384, 16385, 32767, 32768};
-
-static int fail(const char *what, long long a, long long b)
-{
-    std::fprintf(stderr, "FAILED: %s (%lld, %lld): %s\n", what, a, b, g_err);
-    return 1;
-}
-
-static bool covers(long long blocks, long long per_block, long long items)
-{
-    return blocks * per_block >= items && (blocks - 1) * per_block < items;
-}
-
-template <int N>
-static bool laid_out(const size_t (&offs)[N], const size_t (&need)[N - 1])
-{
-    if (offs[0] != 0)
-        return false;
-    for (int k = 0; k + 1 < N; ++k)
-        if (offs[k] % kPlanAlign != 0 || offs[k + 1] < offs[k] + need[k] || offs[k + 1] >= offs[k] + need[k] + kPlanAlign)
-            return false;
-    return true;
-}
 
 template <typename Plan, typename Fn>
 static bool refused(Fn plan_fn, int h, int w, gs_status want, const char *word, const char *entry)
 {
     Plan p;
     g_err[0] = 0;
-    const gs_status st = plan_fn(h, w, p);
-    return st == want && std::strstr(g_err, word) && std::strstr(g_err, entry) && p.bytes == 0;
+    return refused(plan_fn(h, w, p), want, word, entry, p);
 }
 
 int main()

@@ -9,7 +9,7 @@ import math
 import numpy as np
 
 from helpers import instance_maps
-from helpers.instance_maps import _disc
+from helpers.instance_maps import _disc, boundary_mask
 from helpers.instances_ref import label_instances_ref
 
 CLASSES = 5
@@ -152,14 +152,6 @@ def zones_edt(labels, n):
 
 
 # ------------------------------------------------------------------------------------------------------------------- the gaps
-def boundary_mask(labels, n):
-    """a label in 1..n and a 4-neighbour that carries another value or lies outside the map"""
-    labels = np.asarray(labels).astype(np.int64)
-    p = np.pad(labels, 1, constant_values=np.iinfo(np.int64).min)
-    other = (p[:-2, 1:-1] != labels) | (p[2:, 1:-1] != labels) | (p[1:-1, :-2] != labels) | (p[1:-1, 2:] != labels)
-    return sites(labels, n) & other
-
-
 def foreign_direct(labels, n, max_d2):
     """the definition, at the boundary pixels only: offset by offset, the candidates the instance pixels with label != own
     -> (near_d2 int32 [h,w], near_id int32 [h,w])"""
