@@ -11,12 +11,6 @@
 
 #include "../../include/glomseg.h"
 
-// lists shorter than four full batches -- 0: four equal batches; 1: a small first batch (a seventh of the list, at least 8 crops: its
-// upload is the pipeline's fill), the rest in three (56 crops: 7.6 -> 6.9 ms, profiles/README.md round 4)
-#ifndef CFG_SHORT_LIST_SPLIT
-#define CFG_SHORT_LIST_SPLIT 1
-#endif
-
 namespace gs {
 
 constexpr size_t kCropSlotAlign = 256;          // every crop / map starts on a 256-byte boundary of its packed buffer
@@ -50,7 +44,9 @@ static inline CropBatchPlan plan_crop_batches(const int *heights, const int *wid
         const int floor8 = std::min(batch0, 8);
         const int equal4 = std::max(floor8, (n_crops + 3) / 4);   // <= batch0: n_crops < 4 * batch0
         first_batch = rest = equal4;
-        if (CFG_SHORT_LIST_SPLIT && n_crops >= 32) {
+        // a small first batch (a seventh of the list, at least 8 crops: its upload is the pipeline's fill), the rest in three:
+        // 56 crops 7.6 -> 6.9 ms against four equal batches (profiles/README.md round 4)
+        if (n_crops >= 32) {
             const int f = std::max(floor8, (n_crops + 6) / 7);
             const int r = std::max(floor8, (n_crops - f + 2) / 3);
             if (f <= batch0 && r <= batch0) {

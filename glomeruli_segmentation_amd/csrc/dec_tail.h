@@ -63,12 +63,6 @@ constexpr bool kDtNoEpi = true;
 #else
 constexpr bool kDtNoEpi = false;
 #endif
-#ifndef DT_PRIO
-#define DT_PRIO 1      // second half of the workgroup's waves at s_setprio 1 (see below)
-#endif
-#ifndef DT_MAIN_WAVES
-#define DT_MAIN_WAVES 8
-#endif
 // EXCH (round 5): the strips of a row are cut at multiples of 128 columns WITHOUT overlap and the waves that hold horizontally
 // adjacent strips of one band -- a "team" of 1, 2, 4 or 8 waves of one workgroup -- hand each other the two values per class a
 // finished row needs from across the cut (the left neighbour's tx = 0 partial sums of its last column, the right neighbour's
@@ -122,7 +116,7 @@ __global__ void __launch_bounds__(WAVES * 64) dec_tail_kernel(const DecTailArgs 
     // (VALU / LDS) epilogues together and the matrix pipe idles through every epilogue.  With the later half at a higher
     // static priority the pair falls into anti-phase by itself: the preferred wave takes the pipe, and while it is in an
     // epilogue the other one computes.
-    if (DT_PRIO && wid >= WAVES / 2)
+    if (wid >= WAVES / 2)
         __builtin_amdgcn_s_setprio(1);
     // (a launch with fewer tasks than wave slots is spread over more CUs, a.wu waves of each taking tasks: launch_dec_tail_p)
     // EXCH: tasks are (image, band) pairs taken by TEAMS (a.team waves: wave t of a team owns strip t); a.wu counts the teams
@@ -595,7 +589,7 @@ gs_status launch_dec_tail(DecTailArgs a, int num_cus, hipStream_t stream)
     if (full_strips > 0) {
         a.xbase = 0;
         a.nstrips = full_strips;
-        gs_status st = launch_dec_tail_p<8, DT_MAIN_WAVES>(a, num_cus, stream);
+        gs_status st = launch_dec_tail_p<8, 8>(a, num_cus, stream);
         if (st != GS_OK) return st;
     }
     if (rest > 0) {

@@ -29,38 +29,19 @@ __device__ __forceinline__ float ldz(const ActV &t, int n, int c, int y, int x)
     const float v = *at(t, n, c, yc, xc);
     return ok ? v : 0.0f;
 }
-// Once-only streams are marked non-temporal (see F_RES_NT in conv_mfma.h); per-kernel switches for measurement:
+// Once-only streams are marked non-temporal (see F_RES_NT in conv_mfma.h); measured per kernel against plain loads and stores:
 // dec2 0.117 -> 0.100 ms, dec1 0.070 -> 0.067, the stride-2 reduce after the stem 0.107 -> 0.095, dec4 unchanged; dec3_cat_kernel's
 // 84 MB of stores 0.0434 -> 0.0414 ms (profiles/lean_forward_ab.txt).
-#ifndef NT_STEM_ST
-#define NT_STEM_ST 1
-#endif
-#ifndef NT_DEC1_LD
-#define NT_DEC1_LD 1
-#endif
-#ifndef NT_DEC2_LD
-#define NT_DEC2_LD 1
-#endif
-#ifndef NT_DEC4_ST
-#define NT_DEC4_ST 1
-#endif
-#ifndef NT_DEC3_ST
-#define NT_DEC3_ST 1
-#endif
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
-template <bool NT>
 __device__ __forceinline__ float ld_stream(const float *p)
 {
-    return NT ? __builtin_nontemporal_load(p) : *p;
+    return __builtin_nontemporal_load(p);
 }
-template <bool NT, typename T>
+template <typename T>
 __device__ __forceinline__ void st_stream(T *p, T v)
 {
-    if (NT)
-        __builtin_nontemporal_store(v, p);
-    else
-        *p = v;
+    __builtin_nontemporal_store(v, p);
 }
 
 // PReLU as max/min arithmetic (bit-identical to the select: one of the two terms is always zero).  Written as
@@ -107,20 +88,7 @@ struct StemArgs {
 // reference's three fp32 roundings (numpy: x - mean, / std, / 255; VisualizeResults_iou.py:109,111,116),
 // so it is bit-identical to computing them per pixel but costs one LDS read instead of two IEEE
 // divisions per value.
-template <bool U8>
-__device__ __forceinline__ float stem_fetch(const StemArgs &a, const float (*lut)[256], int n, int c, int y, int x)
-{
-    // branch-free (see ldz): clamp, load, select; padding acts on the normalised tensor
-    const bool ok = (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
-    const int yc = min(max(y, 0), a.H - 1), xc = min(max(x, 0), a.W - 1);
-    float v;
-    if (U8)
-        v = lut[c][static_cast<const unsigned char *>(a.in)[(((long long)n * a.H + yc) * a.W + xc) * 3 + c]];
-    else
-        v = static_cast<const float *>(a.in)[(((long long)n * 3 + c) * a.H + yc) * a.W + xc];
-    return ok ? v : 0.0f;
-}
-
+//
 // Two horizontally adjacent output pixels per thread: the 3x5 input window is fetched once (15 values per channel
 // instead of 18), every weight that arrives in an SGPR feeds two FMAs, and the 19 + 3 results leave as 8-byte stores.
 constexpr int STEM_PX = 2;
@@ -128,21 +96,14 @@ constexpr int STEM_PX = 2;
 // (x is even, so byte 6x - 3), i.e. bytes 1..15 of four consecutive dwords: 12 dword loads + 45 bit-field extracts per thread
 // instead of 45 single-byte loads with a 64-bit address, a clamp and a select each -- the kernel was VALU-bound on exactly
 // that bookkeeping (1 935 VALU instructions per wave for 864 FMAs): 0.1227 -> 0.0850 ms per launch at batch 32
-// (profiles/README.md, round 3).  STEM_LUT_COPIES lane-swizzled copies of the table (copy = lane % COPIES; a ds_read_b32
-// banks by (a/4) % 32 within each 32-lane half) were measured on top: 1 copy 0.0850, 8 copies 0.0876, 16 copies 0.1090 ms --
+// (profiles/README.md, round 3).  Lane-swizzled copies of the table (copy = lane % copies; a ds_read_b32 banks by
+// (a/4) % 32 within each 32-lane half) were measured on top: 1 copy 0.0850, 8 copies 0.0876, 16 copies 0.1090 ms --
 // the bank conflicts of the data-dependent lookups are not what bounds the kernel, the extra address arithmetic and table
 // fill cost more than they save.  One copy ships.
-#ifndef STEM_DWORD
-#define STEM_DWORD 1
-#endif
-#ifndef STEM_LUT_COPIES
-#define STEM_LUT_COPIES 1
-#endif
 template <bool U8>
 __global__ void __launch_bounds__(256) stem_kernel(const StemArgs a)
 {
-    constexpr int NC = (U8 && STEM_DWORD) ? STEM_LUT_COPIES : 1;
-    __shared__ float lut[3][256 * NC];
+    __shared__ float lut[3][256];
     if (U8) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -150,9 +111,7 @@ __global__ void __launch_bounds__(256) stem_kernel(const StemArgs a)
             v = v - a.mean[c];
             v = v / a.std[c];
             v = v / 255.0f;
-#pragma unroll
-            for (int k = 0; k < NC; ++k)
-                lut[c][threadIdx.x * NC + k] = v;
+            lut[c][threadIdx.x] = v;
         }
         __syncthreads();
     }
@@ -170,11 +129,10 @@ __global__ void __launch_bounds__(256) stem_kernel(const StemArgs a)
     const bool two = x + 1 < W1;
 
     float v[3][3][2 * STEM_PX + 1];
-    if (U8 && STEM_DWORD) {
+    if (U8) {
         // rows 2y-1 .. 2y+1, bytes [6x-4, 6x+12) of each (W is a multiple of 8: rows start dword-aligned and the last
         // thread of a row ends exactly at the row's end)
         const unsigned char *img = static_cast<const unsigned char *>(a.in) + (long long)n * a.H * a.W * 3;
-        const int cp = (threadIdx.x & (NC - 1));
         unsigned d[3][4];
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
@@ -201,12 +159,12 @@ __global__ void __launch_bounds__(256) stem_kernel(const StemArgs a)
                 for (int c = 0; c < 3; ++c) {
                     const int pos = 1 + kx * 3 + c;                       // byte 1..15 of the 16
                     const unsigned b = (d[ky][pos >> 2] >> (8 * (pos & 3))) & 0xffu;
-                    float t = lut[c][b * NC + cp];
+                    float t = lut[c][b];
                     if ((ky == 0 && top) || (kx == 0 && left))
                         t = 0.0f;                                          // padding acts on the normalised tensor
                     v[c][ky][kx] = t;
                 }
-    } else if (!U8 && STEM_DWORD) {
+    } else {
         // fp32 NCHW input (the tensor the crop pipeline resamples into): five consecutive floats per window row and channel,
         // the same bookkeeping-free form -- only the top row and the left column can be padding
         const float *img = static_cast<const float *>(a.in) + (long long)n * 3 * a.H * a.W;
@@ -229,14 +187,6 @@ __global__ void __launch_bounds__(256) stem_kernel(const StemArgs a)
                     v[c][ky][kx] = t;
                 }
             }
-    } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 2 * STEM_PX + 1; ++kx)
-                    v[c][ky][kx] = stem_fetch<U8>(a, reinterpret_cast<const float(*)[256]>(&lut[0][0]), n, c, 2 * y - 1 + ky, 2 * x - 1 + kx);
     }
 
     // all arithmetic first, all stores last: a store between two weight reads would force hipcc to
@@ -283,16 +233,16 @@ __global__ void __launch_bounds__(256) stem_kernel(const StemArgs a)
 #pragma unroll
     for (int o = 0; o < 19; ++o) {
         if (two)
-            st_stream<NT_STEM_ST>(reinterpret_cast<f32x2_t *>(at(a.a0, n, o, y, x)), f32x2_t{outv[o][0], outv[o][1]});
+            st_stream(reinterpret_cast<f32x2_t *>(at(a.a0, n, o, y, x)), f32x2_t{outv[o][0], outv[o][1]});
         else
-            st_stream<NT_STEM_ST>(at(a.a0, n, o, y, x), outv[o][0]);
+            st_stream(at(a.a0, n, o, y, x), outv[o][0]);
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         if (two)
-            st_stream<NT_STEM_ST>(reinterpret_cast<f32x2_t *>(at(a.inp1, n, c, y, x)), f32x2_t{poolv[c][0], poolv[c][1]});
+            st_stream(reinterpret_cast<f32x2_t *>(at(a.inp1, n, c, y, x)), f32x2_t{poolv[c][0], poolv[c][1]});
         else
-            st_stream<NT_STEM_ST>(at(a.inp1, n, c, y, x), poolv[c][0]);
+            st_stream(at(a.inp1, n, c, y, x), poolv[c][0]);
     }
 }
 
@@ -428,7 +378,7 @@ __global__ void __launch_bounds__(256) dec1_kernel(const Dec1Args a)
     auto fetch = [&](int c0, float *dst) {
 #pragma unroll
         for (int j = 0; j < CB; ++j)
-            dst[j] = ld_stream<NT_DEC1_LD>(plane0 + (long long)(c0 + j) * a.c0.sc);
+            dst[j] = ld_stream(plane0 + (long long)(c0 + j) * a.c0.sc);
     };
     float cur[CB], nxt[CB];
     fetch(0, cur);
@@ -607,7 +557,7 @@ __global__ void __launch_bounds__(256) dec2_kernel(const Dec2Args a)
     if (cb >= a.raw_c0 && cb < a.raw_c0 + a.raw_cn) {   // (uniform) lazy b2: these planes are raw; BN + PReLU of the cat's BR here
 #pragma unroll 16
         for (int c = cb; c < cb + 32; ++c) {
-            const float v = bn_prelu(ld_stream<NT_DEC2_LD>(at(a.raw, n, c - a.raw_c0, y, x)), a.b2, 131, c);
+            const float v = bn_prelu(ld_stream(at(a.raw, n, c - a.raw_c0, y, x)), a.b2, 131, c);
             const float *pc = a.w3c + c * dec2_record<CLS>();   // level3_C weights packed [c][record]: one scalar load per channel
 #pragma unroll
             for (int k = 0; k < CLS; ++k)
@@ -616,7 +566,7 @@ __global__ void __launch_bounds__(256) dec2_kernel(const Dec2Args a)
     } else {
 #pragma unroll 16
         for (int c = cb; c < cb + 32; ++c) {
-            const float v = ld_stream<NT_DEC2_LD>(at(a.a1, n, c, y, x));
+            const float v = ld_stream(at(a.a1, n, c, y, x));
             const float *pc = a.w3c + c * dec2_record<CLS>();
 #pragma unroll
             for (int k = 0; k < CLS; ++k)
@@ -626,7 +576,7 @@ __global__ void __launch_bounds__(256) dec2_kernel(const Dec2Args a)
     if (w == 3) {
 #pragma unroll
         for (int c = 128; c < 131; ++c) {
-            const float v = ld_stream<NT_DEC2_LD>(at(a.a1, n, c, y, x));
+            const float v = ld_stream(at(a.a1, n, c, y, x));
             const float *pc = a.w3c + c * dec2_record<CLS>();
 #pragma unroll
             for (int k = 0; k < CLS; ++k)
@@ -853,7 +803,7 @@ __global__ void __launch_bounds__(256) dec3_cat_kernel(const Dec3CatArgs a)
                     up[dx] = bn_prelu2(t, a.bnu, CLS, o);
                 }
                 // output columns 2x .. 2x + 3: (pixel 0: dx 0, 1), (pixel 1: dx 0, 1)
-                st_stream<NT_DEC3_ST>(reinterpret_cast<f32x4_t *>(at(a.e, n, o, 2 * (y + r) + dy, 2 * x)), f32x4_t{up[0][0], up[1][0], up[0][1], up[1][1]});
+                st_stream(reinterpret_cast<f32x4_t *>(at(a.e, n, o, 2 * (y + r) + dy, 2 * x)), f32x4_t{up[0][0], up[1][0], up[0][1], up[1][1]});
             }
     }
 }
@@ -1017,8 +967,8 @@ __global__ void __launch_bounds__(256) dec4_kernel(const Dec4Args a)
                 cls_of[q][dy * 2 + dx] = live[q] ? bi : -1;   // -1: no pixel here
             }
             if (a.mask && live[q] && (!ENS || a.ens_mode >= 3))
-                st_stream<NT_DEC4_ST>(reinterpret_cast<unsigned short *>(a.mask + ((long long)n * H + 2 * y + dy) * W + 2 * x),
-                                      (unsigned short)(m[0] | (m[1] << 8)));
+                st_stream(reinterpret_cast<unsigned short *>(a.mask + ((long long)n * H + 2 * y + dy) * W + 2 * x),
+                          (unsigned short)(m[0] | (m[1] << 8)));
         }
     }
     if (a.hist && (!ENS || a.ens_mode >= 3)) {

@@ -36,7 +36,10 @@ L2SP = 4    # `constexpr int L2SP` there: pixels per lane of the level-2 branch 
 # switches whose A/B was lost: removed from the sources, none of these names may come back under csrc/
 DELETED = ("F_EPI_PIPE", "CFG_EPI_SPLIT", "CFG_EPI_PRIO", "CFG_EPI_PRELOAD", "CFG_REFILL_MID", "CFG_L3_W16",
            "CFG_L3_FUSE_P4", "CFG_AGL_", "CFG_SKIP_PAD_L2", "CFG_RES_RING_DIV", "CFG_RES_TOP", "CFG_L2_MINW", "CFG_LAZY_B2",
-           "CFG_L2_C1S_REV", "rev_n", "F_XMERGE", "wconv_xm")
+           "CFG_L2_C1S_REV", "rev_n", "F_XMERGE", "wconv_xm",
+           # the switches that sat outside the table's three headers, with no variant build and no test behind their other value
+           "STEM_DWORD", "STEM_LUT_COPIES", "stem_fetch", "NT_STEM_ST", "NT_DEC1_LD", "NT_DEC2_LD", "NT_DEC3_ST", "NT_DEC4_ST",
+           "DT_PRIO", "DT_MAIN_WAVES", "CFG_SHORT_LIST_SPLIT")
 # the forms the library enumerates and no shape reaches with the shipped defaults, each with the switch that keeps it away
 # (found by the sweep of reachable_forms; test_every_enumerated_form_is_accounted_for), and the variant build and case of
 # test_variant_forms.py (helpers/variant_builds.py) that runs it against float64 all the same
@@ -93,7 +96,7 @@ def _read(name):
 
 def test_dispatch_tripwire():
     """CASES and UNREACHABLE_AT_DEFAULTS are answers for the shipped defaults: a changed default fails here, so that they are
-    revisited with it.  Deleted switches stay deleted, and every switch left is documented."""
+    revisited with it.  Deleted switches stay deleted, and every switch left anywhere under csrc/ is documented."""
     cfg = _read("espnet_config.h") + _read("espnet_facts.h")   # (CFG_FUSE_L2 / CFG_FUSE_L3: the weight packer reads them too)
     for name, value in CONFIG.items():
         m = re.search(r"#ifndef %s\n#define %s (\S+)" % (name, name), cfg)
@@ -108,14 +111,19 @@ def test_dispatch_tripwire():
         for name in DELETED:   # whole identifiers (`prev_n` is not `rev_n`); a name ending in "_" is a prefix
             pattern = r"\b%s" % re.escape(name) + ("" if name.endswith("_") else r"\b")
             assert not re.search(pattern, text), (fname, name)
-    # ... and a default nobody documents cannot ship: every overridable macro left is named in DESIGN.md's kernel section
+    # ... and a default nobody documents cannot ship: every overridable macro left anywhere under csrc/ (include guards, names
+    # ending in _H, apart) is named in the Build switches table of DESIGN.md's kernel section, and the table names nothing else
     with open(os.path.join(REPO, "DESIGN.md")) as fh:
         design = fh.read()
     kernels = design[design.index("\n## 4. Kernels"):design.index("\n## 5. ")]
-    macros = re.findall(r"#ifndef (\w+)\n#define \1\b", cfg + _read("conv_mfma.h"))
+    table = re.search(r"\n### Build switches\n(?:[^|\n][^\n]*\n|\n)*((?:\|[^\n]*\n)+)", kernels).group(1)   # the section's first table
+    macros = [m for f in sources if f.endswith((".h", ".hip", ".inc", ".cpp"))
+              for m in re.findall(r"#ifndef (\w+)\n#define \1\b", _read(f)) if not m.endswith("_H")]
     assert len(macros) >= 20 and len(set(macros)) == len(macros)
     for name in macros:
-        assert "`%s`" % name in kernels, name
+        assert "`%s`" % name in table, name
+    listed = [name for row in table.splitlines()[2:] for name in re.findall(r"`(\w+)`", row.split("|")[1])]
+    assert len(listed) >= 20 and set(listed) == set(macros), sorted(set(listed) ^ set(macros))
 
 
 # ---------------------------------------------------------------------------------------------- the cases
