@@ -17,8 +17,8 @@ import time
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libglomseg.so")
-SOURCES = ["espnet.hip", "dec_tail.hip", "crops.hip", "detect_ops.hip", "detector.hip", "wsi_eval.hip", "instances.hip", "instance_match.hip", "boundary_dist.hip", "morphometry.hip", "split.hip", "outlines.hip", "raster.hip", "zones.hip", "lesions.hip", "contours.cpp"]
-HEADERS = ["gs_internal.h", "conv_mfma.h", "dec_tail.h", "dec_tail_args.h", "espnet_kernels.h", "espnet_facts.h", "espnet_weights.h", "workspace_plan.h", "workspace_audit.h", "crop_sample.h", "crop_plan.h", "wave_block.h", "boundary_links.h", "slide_map_plan.h", "instance_plan.h", "instance_match_plan.h", "boundary_dist_plan.h", "morphometry_plan.h", "split_plan.h", "outlines_plan.h", "outlines_abi.h", "raster_plan.h", "raster_abi.h", "zones_plan.h", "zones_abi.h", "lesions_plan.h", "lesions_abi.h", "detect_math.h", "detect_plan.h", "host_copy.h", "host_jobs.h", "host_pipe.h",
+SOURCES = ["espnet.hip", "dec_tail.hip", "crops.hip", "detect_ops.hip", "detector.hip", "wsi_eval.hip", "instances.hip", "instance_match.hip", "boundary_dist.hip", "morphometry.hip", "split.hip", "outlines.hip", "raster.hip", "zones.hip", "lesions.hip", "hulls.hip", "contours.cpp"]
+HEADERS = ["gs_internal.h", "conv_mfma.h", "dec_tail.h", "dec_tail_args.h", "espnet_kernels.h", "espnet_facts.h", "espnet_weights.h", "workspace_plan.h", "workspace_audit.h", "crop_sample.h", "crop_plan.h", "wave_block.h", "boundary_links.h", "slide_map_plan.h", "instance_plan.h", "instance_match_plan.h", "boundary_dist_plan.h", "morphometry_plan.h", "split_plan.h", "outlines_plan.h", "outlines_abi.h", "raster_plan.h", "raster_abi.h", "zones_plan.h", "zones_abi.h", "lesions_plan.h", "lesions_abi.h", "hulls_plan.h", "hulls_abi.h", "detect_math.h", "detect_plan.h", "host_copy.h", "host_jobs.h", "host_pipe.h",
            os.path.join("..", "..", "include", "glomseg.h"), os.path.join("..", "..", "include", "glomseg_scoring.h"),
            os.path.join("..", "..", "include", "glomseg_plan.h"), os.path.join("..", "..", "include", "glomseg_lean.h"), os.path.join("..", "..", "include", "glomseg_forms.h"), os.path.join("..", "..", "include", "glomseg_detector_steps.h"), os.path.join("..", "..", "include", "glomseg_instances.h"),
            os.path.join("..", "..", "include", "glomseg_instance_match.h"),

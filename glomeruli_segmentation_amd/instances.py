@@ -8,7 +8,7 @@ it (8-connected by default), numbered 1..n by the raster position of its first p
 gs_slide_instances (include/glomseg_instances.h, csrc/instances.hip) labels the map where the compositor leaves it.
 
     python -m glomeruli_segmentation_amd.instances --classmap_dir DIR --output_csv FILE
-           [--classes 5] [--connectivity 8] [--min_area 0] [--gpu_id 0] [--morphometry [--mpp F]]
+           [--classes 5] [--connectivity 8] [--min_area 0] [--gpu_id 0] [--morphometry] [--hull] [--mpp F]
 
 --morphometry appends the shape measures of every instance (MORPH_COLUMNS): gs_instance_morphometry (include/glomseg_morphometry.h,
 csrc/morphometry.hip) reduces the label map to ten exact integer sums and the squared Feret diameter per instance on the GPU, and
@@ -20,7 +20,7 @@ from argparse import ArgumentParser
 
 import numpy as np
 
-from . import _call, _lib, _slides
+from . import _call, _lib, _slides, hulls
 
 CLASS_NAMES = ['glomerulus', 'crescent', 'sclerosis', 'mesangium']        # area_stats.py:68
 MAP_SUFFIX = "_pred_classmap.png"                                          # what composite writes
@@ -152,17 +152,19 @@ def morph_header(mpp=None):
     return [k + "_um2" if k == 'area' else k + "_um" if k in MORPH_LENGTHS else k for k in MORPH_COLUMNS]
 
 
-def header(classes=5, morphometry=False, mpp=None):
-    """area_stats.py:68 for five classes; class1.. for any other class count"""
+def header(classes=5, morphometry=False, mpp=None, hull=False):
+    """area_stats.py:68 for five classes; class1.. for any other class count; hull: hulls.hull_header(mpp) at the end"""
     names = CLASS_NAMES if classes == 5 else ["class%d" % c for c in range(1, classes)]
-    return ['patient_id', 'file_name', 'xmin', 'ymin', 'xmax', 'ymax', 'background'] + names + (morph_header(mpp) if morphometry else [])
+    return (['patient_id', 'file_name', 'xmin', 'ymin', 'xmax', 'ymax', 'background'] + names + (morph_header(mpp) if morphometry else []) +
+            (hulls.hull_header(mpp) if hull else []))
 
 
-def instance_rows(result, key, min_area=0, morph=None):
+def instance_rows(result, key, min_area=0, morph=None, hull=None):
     """rows in area_stats.py's contract (header(classes) names the columns), one per instance with at least min_area foreground
     pixels.  file_name follows merge.crop_name's pattern, built from the box: on the 1/8 map the box is already in the crop
     names' units.  background: box area minus the instance's pixels.  morph: morphometry's or morph_measures' dict, whose
-    MORPH_COLUMNS are appended (area in pixels and holes as integers where they are whole)."""
+    MORPH_COLUMNS are appended (area in pixels and holes as integers where they are whole).  hull: hulls.hull_table's or
+    hulls.hull_measures' dict, whose HULL_COLUMNS come last (hull_vertices as an integer where it is whole)."""
     host = _slides.host
     boxes, counts = host(result["boxes"]).astype(np.int64), host(result["counts"]).astype(np.int64)
     rows = []
@@ -176,6 +178,10 @@ def instance_rows(result, key, min_area=0, morph=None):
             for k in MORPH_COLUMNS:
                 v = float(morph[k][i])
                 row.append(int(v) if k in ('area', 'holes') and v.is_integer() else v)
+        if hull is not None:
+            for k in hulls.HULL_COLUMNS:
+                v = float(hull[k][i])
+                row.append(int(v) if k == 'hull_vertices' and v.is_integer() else v)
         rows.append(row)
     return rows
 
@@ -189,16 +195,18 @@ def build_parser():
     p.add_argument('--min_area', type=int, default=0, help='drop instances with fewer foreground pixels')
     p.add_argument('--gpu_id', type=int, default=0)
     p.add_argument('--morphometry', action='store_true', help='append the shape measures of every instance (MORPH_COLUMNS)')
+    p.add_argument('--hull', action='store_true',
+                   help='append the convex-hull measures of every instance (hulls.HULL_COLUMNS), behind the shape measures')
     p.add_argument('--mpp', type=float, default=None,
-                   help='micrometres per MAP pixel (8 x the slide\'s on the 1/8 map): lengths in um, areas in um2; needs --morphometry')
+                   help='micrometres per MAP pixel (8 x the slide\'s on the 1/8 map): lengths in um, areas in um2; needs --morphometry or --hull')
     return p
 
 
 def main(argv=None, out=sys.stdout):
     parser = build_parser()
     args = parser.parse_args(argv)
-    if args.mpp is not None and not args.morphometry:
-        parser.error("--mpp needs --morphometry")
+    if args.mpp is not None and not (args.morphometry or args.hull):
+        parser.error("--mpp needs --morphometry or --hull")
     import torch
     _slides.require_device("the instances are labelled on the GPU")
     paths = _slides.map_paths(args.classmap_dir, MAP_SUFFIX)
@@ -206,11 +214,12 @@ def main(argv=None, out=sys.stdout):
     with torch.cuda.device(args.gpu_id):
         for path in paths:
             slide, cm = _slides.read_slide(path, MAP_SUFFIX)
-            res = label_instances(cm, classes=args.classes, connectivity=args.connectivity, want_labels=args.morphometry)
+            res = label_instances(cm, classes=args.classes, connectivity=args.connectivity, want_labels=args.morphometry or args.hull)
             morph = morphometry(res, args.connectivity, args.mpp) if args.morphometry else None
-            rows += instance_rows(res, slide, args.min_area, morph)
+            hull = hulls.hull_table(res, args.mpp) if args.hull else None
+            rows += instance_rows(res, slide, args.min_area, morph, hull)
             print("{}: {} instances".format(slide, res["n"]), file=out)
-    _slides.write_table(args.output_csv, header(args.classes, args.morphometry, args.mpp), rows)
+    _slides.write_table(args.output_csv, header(args.classes, args.morphometry, args.mpp, args.hull), rows)
     return 0
 
 
